@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X-native batched QP engine.
 
-    python bench.py --gpus N --steps K --warmup W [--workload mpc|qp_dense|ekf]
+    python bench.py --gpus N --steps K --warmup W [--workload mpc|qp_dense|ekf] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic QPs that is already resident in
 HBM: by default the MPC configuration the BASELINE metric is quoted on (8 192 agents, nx=12, nu=2,
@@ -11,8 +11,13 @@ torch.distributed.run; every rank owns an independent shard of the batch (weak s
 batch fixed), the data path has no collective, and only the per-QP (code, iter) words are
 gathered over RCCL at the end of each step.  Rank 0 prints ONE JSON line.
 
-The single-GPU default run also reports the other two BASELINE configurations (`secondary`: dense QPs,
-EKF ticks) with their own kernel time, roofline and parity figures, so that ONE driver-run line covers all three.
+A plain run sets up, warms up, times the K steps and prints the line.  With `--full`, a single-GPU run also
+reports the CPU baseline and a parity spot-check against the oracle, the multi-stream / swarm-order / phase /
+closed-loop figures of the mpc workload, and the other two BASELINE configurations (`secondary`: dense QPs,
+EKF ticks) with their own kernel time, roofline and parity figures, so that ONE line covers all three.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller (rank 0's shard) as float64
+DIR/<name>.npy files; inputs are seeded, so two builds can be compared output for output.
 
 The CPU oracle (oracle/) is used here ONLY for the `cpu_baseline` leg and a parity spot-check of a
 bounded sample; it is never the thing measured as `value`.
@@ -89,6 +94,10 @@ class DenseQPWorkload:
                                           l.data_ptr(), u.data_ptr(), self.x.data_ptr(), self.y.data_ptr(),
                                           self.obj.data_ptr(), self.out[0].data_ptr(), self.out[1].data_ptr(),
                                           self.ws, self.prm, stream=stream.cuda_stream)
+
+    def outputs(self):
+        """What a caller of the solve receives: primal, dual, objective, iteration count and status code per QP."""
+        return {"x": self.x, "y": self.y, "obj": self.obj, "iter": self.out[0], "code": self.out[1]}
 
     def small_outputs(self):
         if not hasattr(self, "small"):
@@ -200,6 +209,10 @@ class MPCWorkload:
                                      self.x.data_ptr(), self.y.data_ptr(), self.obj.data_ptr(),
                                      self.out[0].data_ptr(), self.out[1].data_ptr(), self.ws.data_ptr(), self.prm,
                                      stream=stream.cuda_stream)
+
+    def outputs(self):
+        """What a caller of the solve receives: primal, dual, objective, iteration count and status code per QP."""
+        return {"x": self.x, "y": self.y, "obj": self.obj, "iter": self.out[0], "code": self.out[1]}
 
     def small_outputs(self):
         self.small[:, 0:2] = self.x[:, self.ub:self.ub + 2]
@@ -424,6 +437,10 @@ class EKFWorkload:
     def small_outputs(self):
         return self.delta
 
+    def outputs(self):
+        """The filtered covariances (updated in place, step after step) and the state corrections of the last tick."""
+        return {"P": self.dev["P"], "delta": self.delta}
+
     def cpu_baseline(self, cores, budget_s=15.0):
         from oracle import loader as O
         h = self.host
@@ -629,6 +646,33 @@ def dense_sizes_table(sfb, device, cores):
     return rows
 
 
+DUMP_BYTES = 60_000_000  # array data of --dump-outputs: stays under 64 MB with the .npy headers
+
+
+def dump_outputs(outputs, directory):
+    """Writes each output as float64 <directory>/<name>.npy.  Every output has one row per item; when they would take more
+    than DUMP_BYTES, the 2-D ones keep a fixed, seeded sample of rows (sorted, the same for all of them, written as
+    sampled_rows.npy).  The 1-D ones stay whole while they take at most half of DUMP_BYTES, else they keep the same rows."""
+    os.makedirs(directory, exist_ok=True)
+    B = next(iter(outputs.values())).shape[0]
+    total = sum(8 * t.numel() for t in outputs.values())
+    rows, whole_1d = None, True
+    if total > DUMP_BYTES:
+        flat = sum(8 * t.numel() for t in outputs.values() if t.dim() == 1)
+        per_row = sum(8 * t[0].numel() for t in outputs.values() if t.dim() > 1)
+        whole_1d = flat <= DUMP_BYTES // 2
+        if whole_1d:
+            k = (DUMP_BYTES - flat) // (per_row + 8)  # (+ 8: the row's index in sampled_rows.npy)
+        else:
+            k = DUMP_BYTES // (per_row + flat // B + 8)
+        rows = np.sort(np.random.default_rng(0).choice(B, size=k, replace=False))
+        np.save(os.path.join(directory, "sampled_rows.npy"), rows.astype(np.float64))
+    for name, t in outputs.items():
+        if rows is not None and (t.dim() > 1 or not whole_1d):
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        np.save(os.path.join(directory, name + ".npy"), t.to(torch.float64).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -636,10 +680,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="mpc", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default: the BASELINE config)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pipelined", action="store_true", help="skip the multi-stream throughput measurement (mpc)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads reported next to the headline")
-    ap.add_argument("--no-closed-loop", action="store_true", help="skip the end-to-end / swarm-tick / single-agent figures (mpc)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check beyond the headline (single GPU): CPU baseline and parity with the oracle, "
+                         "multi-stream / swarm-order / phase / closed-loop figures (mpc), secondary workloads, dense size table")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity check")
+    ap.add_argument("--no-pipelined", action="store_true", help="with --full: skip the multi-stream throughput measurement (mpc)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary workloads reported next to the headline")
+    ap.add_argument("--no-closed-loop", action="store_true", help="with --full: skip the end-to-end / swarm-tick / single-agent figures (mpc)")
     ap.add_argument("--debug-knob", action="append", default=[], metavar="NAME=VALUE",
                     help="a debug knob of the library (sfb_debug_set, csrc/knobs.h) for this run: measurements and profiling only; "
                          "recorded in the line as `debug_knobs`")
@@ -741,6 +790,9 @@ def main():
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
 
+    if rank == 0 and args.dump_outputs:  # before anything of --full launches into the same buffers
+        dump_outputs(wl.outputs(), args.dump_outputs)
+
     if rank == 0:
         units = wl.units_per_step * world * args.steps
         value = units / elapsed
@@ -773,13 +825,14 @@ def main():
                 rec["roofline"]["factor_stream_GBps"] = eff / (kern_ms * 1e-3) / 1e9
         if hasattr(wl, "roofline_alt"):
             rec["roofline_alt"] = wl.roofline_alt(kern_ms)
-        if world == 1 and hasattr(wl, "pipelined") and not args.no_pipelined:
+        full = args.full and world == 1
+        if full and hasattr(wl, "pipelined") and not args.no_pipelined:
             rec["ordered_like_a_swarm_tick"] = wl.ordered_like_a_swarm_tick()
             rec["pipelined"] = wl.pipelined(max(4, 2 * args.steps))
             rec["phases_ms"] = wl.phases_ms()
             if args.batch is None and not args.no_closed_loop:
                 rec["closed_loop"] = wl.closed_loop()
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline:
             cores, cpuinfo = host_cpus()
             rec["cpu_baseline"], rec["parity_vs_oracle"] = wl.cpu_baseline(cores)
             # `cores` = threads the oracle was run with = CPUs this process may use (affinity mask, cgroup quota), which
@@ -788,7 +841,7 @@ def main():
             sc = rec["cpu_baseline"].get("single_core")
             if sc and sc.get("value"):
                 rec["cpu_baseline"]["speedup_over_single_core"] = rec["cpu_baseline"]["value"] / sc["value"]
-        if world == 1 and not args.no_secondary and not args.no_cpu_baseline and args.batch is None:
+        if full and not args.no_secondary and not args.no_cpu_baseline and args.batch is None:
             del wl  # free the headline workload's device memory first
             torch.cuda.empty_cache()
             rec["secondary"] = {w: secondary_line(sfb, w, device) for w in sorted(WORKLOADS) if w != args.workload}

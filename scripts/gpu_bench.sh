@@ -1,11 +1,13 @@
 #!/bin/bash
+# the full bench line (headline + CPU baseline, parity, closed loop, secondary workloads) and a digest of it; files under $1
 cd ${GRAFT_REPO_ROOT:-.}
-mkdir -p gpurun_out
-SECONDS=0; timeout 900 python bench.py 2> gpurun_out/bench_default.err | tail -1 > gpurun_out/bench_default.json; echo "bench.py wall $SECONDS s"
-tail -3 gpurun_out/bench_default.err
-python - <<'PY'
-import json
-r = json.load(open("gpurun_out/bench_default.json"))
+OUT=${1:-bench_out}
+mkdir -p $OUT
+SECONDS=0; timeout 900 python bench.py --full 2> $OUT/bench_default.err | tail -1 > $OUT/bench_default.json; echo "bench.py wall $SECONDS s"
+tail -3 $OUT/bench_default.err
+python - $OUT/bench_default.json <<'PY'
+import json, sys
+r = json.load(open(sys.argv[1]))
 def show(name, d):
     print(name, "value %.4g %s" % (d["value"], d["unit"]), "kernel_ms %.3f" % d["roofline"]["kernel_ms"], "frac %.3g" % d["roofline"]["frac"],
           "traffic", d["roofline"].get("traffic"), d["roofline"].get("traffic_source"), "alt", d.get("roofline_alt", {}).get("frac"))

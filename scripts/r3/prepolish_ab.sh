@@ -6,4 +6,4 @@ B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-pipelined --no-se
 for W in 0 64 128 192 256 384 512; do
   echo "SFB_SP_PREPOLISH=$W: $(SFB_SP_PREPOLISH=$W timeout 300 $B 2>/dev/null | tail -1 | python -c 'import sys,json; r=json.loads(sys.stdin.read()); p=r.get("parity_vs_oracle",{}); print("%.2f ms" % r["ms_per_step"])')"
 done
-echo "default with parity: $(timeout 600 python bench.py --steps 5 --warmup 2 --no-pipelined --no-secondary --workload mpc 2>/dev/null | tail -1 | python -c 'import sys,json; r=json.loads(sys.stdin.read()); p=r.get("parity_vs_oracle",{}); print("%.2f ms" % r["ms_per_step"], p.get("code_mismatches"), p.get("iter_mismatches"), p.get("max_abs_dx"))')"
+echo "default with parity: $(timeout 600 python bench.py --steps 5 --warmup 2 --no-pipelined --no-secondary --workload mpc --full 2>/dev/null | tail -1 | python -c 'import sys,json; r=json.loads(sys.stdin.read()); p=r.get("parity_vs_oracle",{}); print("%.2f ms" % r["ms_per_step"], p.get("code_mismatches"), p.get("iter_mismatches"), p.get("max_abs_dx"))')"

@@ -6,10 +6,10 @@ cd ${GRAFT_REPO_ROOT:-.}
 mkdir -p gpurun_out
 timeout 1200 python -m pytest tests/test_qp_sparse_gpu.py tests/test_mpc_gpu.py tests/test_bench_gpu.py -x -q -m gpu 2>&1 | tail -3
 cat gpurun_out/rccl_two_ranks_one_device.json 2>/dev/null | head -40
-timeout 600 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-secondary --workload mpc 2> gpurun_out/book_bench.err | tail -1 > gpurun_out/book_bench.json
-python3 - <<'PY'
-import json
-d = json.load(open("gpurun_out/book_bench.json"))
+LINE=$(timeout 600 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-secondary --workload mpc --full | tail -1)
+python3 - "$LINE" <<'PY'
+import json, sys
+d = json.loads(sys.argv[1])
 print("headline %.0f QP/s %.3f ms" % (d["value"], d["ms_per_step"]))
 print("pipelined", json.dumps(d.get("pipelined")))
 cl = d.get("closed_loop", {})

@@ -40,7 +40,10 @@ def main():
         dist.destroy_process_group()
     except Exception as e:  # noqa: BLE001 -- the backend's refusal is the measurement
         res["error"] = "%s: %s" % (type(e).__name__, str(e)[:600])
-    print("RCCL_RANKS " + json.dumps(res), flush=True)
+    # ONE write() for the whole line: the ranks share the pipe, and a line written in pieces (print() under unbuffered stdout
+    # writes the text and its newline separately) can have the other rank's line land inside it
+    sys.stdout.flush()
+    os.write(1, ("RCCL_RANKS " + json.dumps(res) + "\n").encode())
 
 
 if __name__ == "__main__":

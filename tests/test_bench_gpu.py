@@ -22,7 +22,7 @@ def _last_json(out):
 
 def test_single_gpu_line_has_roofline_and_cpu_baseline():
     out = subprocess.run([sys.executable, "bench.py", "--workload", "qp_dense", "--batch", "8192", "--steps", "2",
-                          "--warmup", "1"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                          "--warmup", "1", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json(out.stdout)
     assert KEYS <= set(d) and {"cpu_baseline", "parity_vs_oracle"} <= set(d)
@@ -31,6 +31,32 @@ def test_single_gpu_line_has_roofline_and_cpu_baseline():
     assert {"value", "unit", "cores", "kind", "sample"} <= set(d["cpu_baseline"])
     assert d["parity_vs_oracle"]["code_mismatches"] == 0 and d["parity_vs_oracle"]["iter_mismatches"] == 0
     assert d["parity_vs_oracle"]["max_abs_dx"] <= 1e-8
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline only; --dump-outputs writes what the last timed step returned, as
+    float64, and equals the oracle's solution of the same seeded QPs."""
+    import numpy as np
+    out = subprocess.run([sys.executable, "bench.py", "--workload", "qp_dense", "--batch", "4096", "--steps", "3",
+                          "--warmup", "1", "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = _last_json(out.stdout)
+    assert KEYS <= set(d) and d["steps"] == 3 and d["ms_per_step"] > 0
+    assert not {"cpu_baseline", "parity_vs_oracle", "secondary", "pipelined", "closed_loop"} & set(d)
+    got = {k: np.load(tmp_path / (k + ".npy")) for k in ("x", "y", "obj", "iter", "code")}
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(k + ".npy" for k in got)
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["x"].shape == (4096, 10) and got["y"].shape == (4096, 20) and got["iter"].shape == (4096,)
+    sys.path.insert(0, ROOT)
+    import smooth_feedback_amd as sfb
+    from oracle import loader as O
+    P, q, A, l, u = sfb.random_qp_batch(5, 4096, 20, 10, 1.0)  # rank 0's batch of the bench's dense workload
+    S = 256
+    ref = O.qp_dense_solve_batch(P[:S], q[:S], A[:S], l[:S], u[:S], nthreads=4,
+                                 params=O.default_params(eps_abs=1e-6, eps_rel=1e-6, polish=1, max_iter=10000, scaling=0))
+    assert np.array_equal(got["code"][:S], ref["code"]) and np.array_equal(got["iter"][:S], ref["iter"])
+    fin = np.isfinite(ref["x"]).all(axis=1)
+    assert np.abs(got["x"][:S] - ref["x"])[fin].max(initial=0.0) <= 1e-8
 
 
 @pytest.mark.parametrize("workload,batch,port", [("qp_dense", 4096, 29533), ("mpc", 96, 29541), ("ekf", 70000, 29549)])
@@ -70,9 +96,9 @@ def test_eight_ranks_mpc_code_path():
 
 
 def test_default_line_carries_the_secondary_workloads():
-    """The driver's command (no flags): headline = BASELINE configs[2], plus the other two configurations under
+    """The driver's command with --full: headline = BASELINE configs[2], plus the other two configurations under
     `secondary`, each with its own roofline, CPU baseline and parity figures; the dense one with the FP64-VALU view."""
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1"], cwd=ROOT, capture_output=True,
+    out = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--full"], cwd=ROOT, capture_output=True,
                          text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json(out.stdout)
