@@ -23,6 +23,8 @@ def main():
       if os.environ.get("BIG") == "1":                                                           # big kernel only: filter shapes, block-structured A
           n, m = int(rng.integers(1, 6)), int(rng.integers(64, 330))
           if rng.random() < 0.3: n, m = int(rng.integers(6, 60)), int(rng.integers(60, 200))
+          if rng.random() < 0.4:                                                                 # 385 <= n + m <= 1024: beyond the diagonal
+              kk = int(rng.integers(385, 1025)); n = int(rng.integers(1, 301)); m = kk - n           # cache, and the <16> instance above 512
       if os.environ.get("MID") == "1":                                                           # the on-chip block-sweep kernel: 32 < n + m <= 128, every shape
           kk = int(rng.integers(33, 129)); n = int(rng.integers(1, kk)); m = kk - n
           if rng.random() < 0.3: n, m = int(rng.integers(8, 50)), int(rng.integers(25, 79))

@@ -28,6 +28,7 @@ def test_randomised_parity_sweep(script, n):
     ("fuzz_sparse.py", 100, {"KNOBS": "SFB_SP_GRID=4,SFB_SP_LAT=0", "BMAX": "40"}),  # predicted order with the standard-form loop launch
     ("fuzz_sparse.py", 150, {"KNOBS": "SFB_PLAN_UNITS=0"}),                        # the supernodal engine of the numeric factorisation for every plan
     ("fuzz_sparse.py", 100, {"KNOBS": "SFB_PLAN_UNITS=0,SFB_SP_GRID=4", "BMAX": "40"}),
+    ("fuzz_dense.py", 40, {"BIG": "1"}),                                           # big dense kernel only, up to n + m = 1024
 ])
 def test_randomised_parity_sweep_of_the_other_launch_shapes(script, n, knobs):
     """The same sweeps with the debug knobs that select the non-default engines / launch shapes (the scripts hand KNOBS to
