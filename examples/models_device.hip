@@ -232,15 +232,17 @@ int sfbx_mpc_swarm_devlin_step_multi(int variant, int K, double tf, int64_t batc
  * closed loop.  Vehicle 0 starts at the identity like the example, the others off it by xi ~ U(-0.3, 0.3)^6 (mt19937_64(seed + b)).
  * Out per tick: positions xy [ticks][batch][2], u_mpc / u_asif [ticks][batch][2], the number of non-Optimal MPC / ASIF
  * solves, the smallest barrier value h(x) over the swarm, seconds [ticks][2] (MPC, ASIF). */
-int sfbx_vehicle_swarm_sim(int64_t batch, int K_mpc, int K_asif, int ticks, uint64_t seed, double * xy, double * u_mpc, double * u_asif,
-                           int32_t * mpc_bad, int32_t * asif_bad, double * hmin, double * seconds)
+static int vehicle_swarm_sim_impl(int64_t batch, int K_mpc, int K_asif, int ticks, uint64_t seed, double * xy, double * u_mpc, double * u_asif,
+                                  int32_t * mpc_bad, int32_t * asif_bad, double * hmin, double * seconds, const bool reduced_kkt)
 {
   try {
+    auto fprm        = sfbx::vehicle_asif_params(K_asif);
+    fprm.reduced_kkt = reduced_kkt;
     const sfbx::VehicleModel6 mdl{};
     auto mpc = sfbx::make_vehicle_mpc<sfbx::MPC6, sfbx::VehicleModel6>(K_mpc, 5.0);
     MPCSwarmDeviceLin<sfbx::MPC6, sfbx::VehicleModel6> ctrl(mpc, mdl, batch);
     ASIFSwarmDevice<X6, U2, sfbx::VehicleDyn6, sfbx::VehicleH, sfbx::VehicleBU> filt(sfbx::VehicleDyn6{}, sfbx::VehicleH{}, sfbx::VehicleBU{},
-                                                                                    (size_t)batch, sfbx::vehicle_asif_params(K_asif));
+                                                                                    (size_t)batch, fprm);
     std::vector<X6> x((size_t)batch);
     for (int64_t b = 1; b < batch; ++b) {
       std::mt19937_64 rng(seed + (uint64_t)b);
@@ -283,6 +285,17 @@ int sfbx_vehicle_swarm_sim(int64_t batch, int K_mpc, int K_asif, int ticks, uint
     return -2;
   }
 }
+int sfbx_vehicle_swarm_sim(int64_t batch, int K_mpc, int K_asif, int ticks, uint64_t seed, double * xy, double * u_mpc, double * u_asif,
+                           int32_t * mpc_bad, int32_t * asif_bad, double * hmin, double * seconds)
+{
+  return vehicle_swarm_sim_impl(batch, K_mpc, K_asif, ticks, seed, xy, u_mpc, u_asif, mpc_bad, asif_bad, hmin, seconds, false);
+}
+/* ... with the filter's QPs on the reduced-KKT route for tall problems (ASIFilterParams::reduced_kkt) */
+int sfbx_vehicle_swarm_sim_tall(int64_t batch, int K_mpc, int K_asif, int ticks, uint64_t seed, double * xy, double * u_mpc, double * u_asif,
+                                int32_t * mpc_bad, int32_t * asif_bad, double * hmin, double * seconds)
+{
+  return vehicle_swarm_sim_impl(batch, K_mpc, K_asif, ticks, seed, xy, u_mpc, u_asif, mpc_bad, asif_bad, hmin, seconds, true);
+}
 
 /* sfbx_mpc_swarm_device_step (models.h) with the linearisation on the GPU as well (MPCSwarmDeviceLin): same agents, same
  * closed loop.  Also out: the records of the LAST tick as the device wrote them ([batch][*record_doubles], room for the
@@ -310,13 +323,15 @@ int sfbx_mpc_swarm_devlin_step(int variant, int K, double tf, int64_t batch, uin
  * [batch][2]: `ticks` consecutive filter calls, the vehicles moved 25 ms along their filtered inputs in between.  Out for
  * the LAST tick: u [batch][2], codes, iters, the QPs (n = 3, m = K + 3), their primal / dual and the warm start used;
  * seconds[ticks]: wall time of every filter call. */
-int sfbx_asif_swarm_device_step(int64_t batch, int K, int ticks, const double * states, const double * udes, double * u_out,
-                                int32_t * codes, uint32_t * iters, double * P, double * q, double * A, double * l, double * u,
-                                double * x, double * y, double * wx, double * wy, double * seconds)
+static int asif_swarm_device_step_impl(int64_t batch, int K, int ticks, const double * states, const double * udes, double * u_out,
+                                       int32_t * codes, uint32_t * iters, double * P, double * q, double * A, double * l, double * u,
+                                       double * x, double * y, double * wx, double * wy, double * seconds, const bool reduced_kkt)
 {
   try {
+    auto fprm        = sfbx::vehicle_asif_params(K);
+    fprm.reduced_kkt = reduced_kkt;
     ASIFSwarmDevice<X6, U2, sfbx::VehicleDyn6, sfbx::VehicleH, sfbx::VehicleBU> swarm(sfbx::VehicleDyn6{}, sfbx::VehicleH{}, sfbx::VehicleBU{},
-                                                                                     (size_t)batch, sfbx::vehicle_asif_params(K));
+                                                                                     (size_t)batch, fprm);
     std::vector<X6> g((size_t)batch);
     std::vector<U2> ud((size_t)batch);
     for (int64_t b = 0; b < batch; ++b) {
@@ -348,6 +363,19 @@ int sfbx_asif_swarm_device_step(int64_t batch, int K, int ticks, const double * 
     std::fprintf(stderr, "sfbx_asif_swarm_device_step: %s\n", e.what());
     return 1;
   }
+}
+int sfbx_asif_swarm_device_step(int64_t batch, int K, int ticks, const double * states, const double * udes, double * u_out,
+                                int32_t * codes, uint32_t * iters, double * P, double * q, double * A, double * l, double * u,
+                                double * x, double * y, double * wx, double * wy, double * seconds)
+{
+  return asif_swarm_device_step_impl(batch, K, ticks, states, udes, u_out, codes, iters, P, q, A, l, u, x, y, wx, wy, seconds, false);
+}
+/* ... with the QPs on the reduced-KKT route for tall problems (ASIFilterParams::reduced_kkt) */
+int sfbx_asif_swarm_device_step_tall(int64_t batch, int K, int ticks, const double * states, const double * udes, double * u_out,
+                                     int32_t * codes, uint32_t * iters, double * P, double * q, double * A, double * l, double * u,
+                                     double * x, double * y, double * wx, double * wy, double * seconds)
+{
+  return asif_swarm_device_step_impl(batch, K, ticks, states, udes, u_out, codes, iters, P, q, A, l, u, x, y, wx, wy, seconds, true);
 }
 
 }  // extern "C"

@@ -180,15 +180,17 @@ def asif_swarm_states(batch, seed=0):
     return st, ud
 
 
-def asif_swarm_device_step(states, udes, K, ticks=1):
-    """ASIFSwarmDevice (assembly and solve on the GPU) from the states of asif_swarm_states; outputs like asif_swarm_step."""
+def asif_swarm_device_step(states, udes, K, ticks=1, reduced_kkt=False):
+    """ASIFSwarmDevice (assembly and solve on the GPU) from the states of asif_swarm_states; outputs like asif_swarm_step.
+    reduced_kkt: the filter's opt-in switch (ASIFilterParams::reduced_kkt), the QPs on the reduced-KKT route for tall problems."""
     batch = len(states)
     n, m = 3, K + 3
     out = dict(u=np.zeros((batch, 2)), code=np.zeros(batch, np.int32), iter=np.zeros(batch, np.uint32), P=np.zeros((batch, n * n)),
                q=np.zeros((batch, n)), A=np.zeros((batch, m * n)), l=np.zeros((batch, m)), ub=np.zeros((batch, m)),
                x=np.zeros((batch, n)), y=np.zeros((batch, m)), wx=np.zeros((batch, n)), wy=np.zeros((batch, m)), seconds=np.zeros(ticks))
     st = np.ascontiguousarray(states, dtype=np.float64); ud = np.ascontiguousarray(udes, dtype=np.float64)
-    rc = dev_lib().sfbx_asif_swarm_device_step(C.c_int64(batch), K, ticks, _p(st), _p(ud), _p(out["u"]), _p(out["code"]), _p(out["iter"]),
+    fn = dev_lib().sfbx_asif_swarm_device_step_tall if reduced_kkt else dev_lib().sfbx_asif_swarm_device_step
+    rc = fn(C.c_int64(batch), K, ticks, _p(st), _p(ud), _p(out["u"]), _p(out["code"]), _p(out["iter"]),
                                                _p(out["P"]), _p(out["q"]), _p(out["A"]), _p(out["l"]), _p(out["ub"]), _p(out["x"]),
                                                _p(out["y"]), _p(out["wx"]), _p(out["wy"]), _p(out["seconds"]))
     assert rc == 0, rc
@@ -270,11 +272,13 @@ def ekf_swarm_host(states, P0, y, tau=0.1, dt=0.0, rk4=False):
     return out
 
 
-def vehicle_swarm_sim(batch, ticks, K_mpc=30, K_asif=200, seed=0):
-    """examples/mpc_asif_vehicle.cpp's closed loop for a swarm, MPC and ASI filter on the GPU (models_device.hip)."""
+def vehicle_swarm_sim(batch, ticks, K_mpc=30, K_asif=200, seed=0, reduced_kkt=False):
+    """examples/mpc_asif_vehicle.cpp's closed loop for a swarm, MPC and ASI filter on the GPU (models_device.hip).
+    reduced_kkt: the filter's QPs on the reduced-KKT route for tall problems (ASIFilterParams::reduced_kkt)."""
     out = dict(xy=np.zeros((ticks, batch, 2)), u_mpc=np.zeros((ticks, batch, 2)), u_asif=np.zeros((ticks, batch, 2)),
                mpc_bad=np.zeros(ticks, np.int32), asif_bad=np.zeros(ticks, np.int32), hmin=np.zeros(ticks), seconds=np.zeros((ticks, 2)))
-    rc = dev_lib().sfbx_vehicle_swarm_sim(C.c_int64(batch), K_mpc, K_asif, ticks, C.c_uint64(seed), _p(out["xy"]), _p(out["u_mpc"]),
+    fn = dev_lib().sfbx_vehicle_swarm_sim_tall if reduced_kkt else dev_lib().sfbx_vehicle_swarm_sim
+    rc = fn(C.c_int64(batch), K_mpc, K_asif, ticks, C.c_uint64(seed), _p(out["xy"]), _p(out["u_mpc"]),
                                           _p(out["u_asif"]), _p(out["mpc_bad"]), _p(out["asif_bad"]), _p(out["hmin"]), _p(out["seconds"]))
     assert rc == 0, rc
     return out

@@ -246,6 +246,43 @@ sfb_status sfb_qp_dense_solve_batch_host_multi(const sfb_qp_params *prm, int64_t
                                                const double *u, const double *warm_x, const double *warm_y,
                                                double *x, double *y, double *obj, uint32_t *iter, int32_t *code);
 
+/*
+ * Tall dense QPs (few unknowns, many rows -- a safety filter has n = nu + 1 and m = K nh + nu + 1): the reduced-KKT route.
+ *
+ * Same problem, same layout, same arguments and outputs as sfb_qp_dense_solve_batch / _host / _host_multi, and the same
+ * algorithm (scaling, pre-check, rho classes, warm start, ADMM update, stopping checks, max_iter, max_time, polish,
+ * un-scaling, objective).  What is reduced: the linear solves.  Instead of the pivoted LDL' of the (n+m) x (n+m) KKT matrix
+ * [P + sigma I, A'; A, -diag(1/rho)], the m dual unknowns are eliminated first,
+ *     S x = rhs_x + A' diag(rho) rhs_z,   S = P + sigma I + A' diag(rho) A  (n x n),   nu = diag(rho) (A x - rhs_z),
+ * and S gets an unpivoted LDL' once per solve; polish solves (P + delta I + A_act' A_act / delta) the same way and keeps the
+ * reference's refinement rounds against the unperturbed system.  A factorisation costs O(m n^2) instead of O((n+m)^3), an
+ * iteration O(m n) instead of O((n+m)^2), and a problem with n = 3, m = 203 lives in the registers of one wavefront.
+ * Results agree with sfb_qp_dense_solve_batch TO ROUNDING, NOT bit for bit: sums over the rows of A are wave reductions
+ * and there is no pivoting, so iteration counts can differ where a stopping test is met within rounding.  This is an
+ * opt-in route: sfb_qp_dense_solve_batch never takes it.  S must be positive definite (sigma > 0 or P + A'A definite);
+ * a pivot that is not positive ends the solve with SFB_QP_UNKNOWN like a failed LDL' of the reference.
+ * Sizes: 1 <= n <= SFB_QP_DENSE_TALL_MAX_N, 1 <= m <= SFB_QP_DENSE_TALL_MAX_M (so n + m may exceed the 19 198 of the
+ * entry points above); anything else is SFB_ERR_UNSUPPORTED.
+ * Working memory: none while a problem's rows fit in registers (m <= 512 for n <= 4, m <= 256 for n <= 8) or in LDS
+ * ((3 + n) m doubles within 60 KB); beyond that 2 m doubles per problem are taken stream-ordered per call.
+ */
+#define SFB_QP_DENSE_TALL_MAX_N 16
+#define SFB_QP_DENSE_TALL_MAX_M 1048576
+sfb_status sfb_qp_dense_tall_solve_batch(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
+                                         const double *q, const double *A, const double *l, const double *u,
+                                         const double *warm_x, const double *warm_y, double *x, double *y,
+                                         double *obj, uint32_t *iter, int32_t *code, void *stream);
+/* ... with host pointers (synchronous, on the staging buffer sfb_qp_dense_solve_batch_host keeps) */
+sfb_status sfb_qp_dense_tall_solve_batch_host(const sfb_qp_params *prm, int64_t batch, int n, int m,
+                                              const double *P, const double *q, const double *A, const double *l,
+                                              const double *u, const double *warm_x, const double *warm_y,
+                                              double *x, double *y, double *obj, uint32_t *iter, int32_t *code);
+/* ... and sharded over the device list (sfb_set_devices); same arguments, same results. */
+sfb_status sfb_qp_dense_tall_solve_batch_host_multi(const sfb_qp_params *prm, int64_t batch, int n, int m,
+                                                    const double *P, const double *q, const double *A, const double *l,
+                                                    const double *u, const double *warm_x, const double *warm_y,
+                                                    double *x, double *y, double *obj, uint32_t *iter, int32_t *code);
+
 /* ------------------------------------------------------------------------------------------
  * Sparse QPs sharing ONE sparsity pattern (a swarm of MPC problems from the same transcription).
  *

@@ -285,6 +285,10 @@ struct ASIFilterParams {
   ManifoldBounds<U> ulim{};
   ASIFtoQPParams asif{};
   QPSolverParams qp{};
+  /// Opt-in (default off): solve the filter's QP -- n = nu + 1 unknowns, m = K nh + rows(ulim) + 1 rows -- through the
+  /// reduced-KKT route for tall problems (sfb.h, sfb_qp_dense_tall_solve_batch).  Same algorithm; results agree with the
+  /// default pivoted route to rounding, not bit for bit.  Needs nu + 1 <= SFB_QP_DENSE_TALL_MAX_N.
+  bool reduced_kkt{false};
 };
 
 namespace detail {
@@ -292,7 +296,7 @@ namespace detail {
 /// for n + m <= 64, the shared-pattern sparse kernel with a full pattern behind the same call for larger ones.
 class DenseQPBackend {
 public:
-  DenseQPBackend(int n, int m, const QPSolverParams & prm) : n_(n), m_(m), prm_(prm) {}
+  DenseQPBackend(int n, int m, const QPSolverParams & prm, bool reduced_kkt = false) : n_(n), m_(m), prm_(prm), tall_(reduced_kkt) {}
 
   /// B problems, batch-major dense column-major arrays as in sfb_qp_dense_solve_batch_host
   void solve_batch(int64_t B, const double * P, const double * q, const double * A, const double * l, const double * u,
@@ -300,12 +304,14 @@ public:
                    int32_t * code)
   {
     const sfb_qp_params c = prm_.to_c();
-    sfb_check(sfb_qp_dense_solve_batch_host(&c, B, n_, m_, P, q, A, l, u, wx, wy, x, y, obj, iter, code));
+    sfb_check((tall_ ? sfb_qp_dense_tall_solve_batch_host : sfb_qp_dense_solve_batch_host)(&c, B, n_, m_, P, q, A, l, u, wx, wy, x, y, obj,
+                                                                                         iter, code));
   }
 
 private:
   int n_, m_;
   QPSolverParams prm_;
+  bool tall_;  // ASIFilterParams::reduced_kkt
 };
 }  // namespace detail
 
@@ -316,7 +322,7 @@ public:
   explicit ASIFilter(Dyn f, ASIFilterParams<U> prm = {}) : f_(std::move(f)), prm_(std::move(prm))
   {
     asif_to_qp_allocate<G, U>(qp_, prm_.asif.K, prm_.ulim.rows, prm_.nh);  // :59-60
-    backend_ = std::make_unique<detail::DenseQPBackend>(qp_.n, qp_.m, prm_.qp);
+    backend_ = std::make_unique<detail::DenseQPBackend>(qp_.n, qp_.m, prm_.qp, prm_.reduced_kkt);
   }
 
   /// asif.hpp:82-102: {u, code}
@@ -361,7 +367,7 @@ public:
     asif_to_qp_allocate<G, U>(qp_, prm_.asif.K, prm_.ulim.rows, prm_.nh);
     n_ = qp_.n;
     m_ = qp_.m;
-    backend_ = std::make_unique<detail::DenseQPBackend>(n_, m_, prm_.qp);
+    backend_ = std::make_unique<detail::DenseQPBackend>(n_, m_, prm_.qp, prm_.reduced_kkt);
     P_.assign(B_ * n_ * n_, 0.0); q_.assign(B_ * n_, 0.0); A_.assign(B_ * m_ * n_, 0.0);
     l_.assign(B_ * m_, 0.0); u_.assign(B_ * m_, 0.0);
     x_.assign(B_ * n_, 0.0); y_.assign(B_ * m_, 0.0); wx_ = x_; wy_ = y_;

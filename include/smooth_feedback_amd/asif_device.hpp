@@ -88,7 +88,7 @@ public:
     }
     const sfb_qp_params c = prm_.qp.to_c();
     int64_t wsb = 0;
-    sfb_check(sfb_qp_dense_workspace_bytes(&c, B_, n_, m_, &wsb));
+    if (!prm_.reduced_kkt) sfb_check(sfb_qp_dense_workspace_bytes(&c, B_, n_, m_, &wsb));  // (the reduced route needs none at filter sizes)
     sfb_check(sfb_workspace_create(wsb, &ws_));
     hx_.resize(B * n_);
     hcode_.assign(B, 6);
@@ -114,8 +114,12 @@ public:
                        g_, udes_, f_, h_, bu_, n_, m_, P_, q_, A_, l_, u_);
     detail::hip_check(hipGetLastError(), "asif_assemble_kernel");
     const sfb_qp_params c = prm_.qp.to_c();
-    sfb_check(sfb_qp_dense_solve_batch_ws(&c, B_, n_, m_, P_, q_, A_, l_, u_, have_warm_ ? wx_ : nullptr, have_warm_ ? wy_ : nullptr,
-                                          x_, y_, nullptr, iter_, code_, ws_, nullptr));
+    if (prm_.reduced_kkt)  // opt-in: the reduced-KKT route for tall problems (ASIFilterParams::reduced_kkt)
+      sfb_check(sfb_qp_dense_tall_solve_batch(&c, B_, n_, m_, P_, q_, A_, l_, u_, have_warm_ ? wx_ : nullptr, have_warm_ ? wy_ : nullptr,
+                                              x_, y_, nullptr, iter_, code_, nullptr));
+    else
+      sfb_check(sfb_qp_dense_solve_batch_ws(&c, B_, n_, m_, P_, q_, A_, l_, u_, have_warm_ ? wx_ : nullptr, have_warm_ ? wy_ : nullptr,
+                                            x_, y_, nullptr, iter_, code_, ws_, nullptr));
     if (!have_warm_) detail::hip_check(hipMemsetAsync(wx_, 0, (size_t)B_ * (n_ + m_) * 8, nullptr), "hipMemsetAsync");  // wx, wy adjacent
     hipLaunchKernelGGL(detail::asif_store_kernel, dim3((unsigned)B_), dim3(256), 0, nullptr, B_, n_, m_, x_, y_, code_, wx_, wy_);
     detail::hip_check(hipGetLastError(), "asif_store_kernel");

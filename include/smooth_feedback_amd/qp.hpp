@@ -307,6 +307,19 @@ QPSolution<> solve_qp(const Pbm & pbm, const QPSolverParams & prm, const QPSolut
   return solver.solve(pbm, warmstart);
 }
 
+/// Batched solve of TALL dense problems (1 <= n <= 16, many rows) through the reduced-KKT route (sfb.h,
+/// sfb_qp_dense_tall_solve_batch_host): P [B][n*n], A [B][m*n] column-major, q [B][n], l, u [B][m] on the host.  Results
+/// agree with QPSolver<dense>::solve_batch to rounding, not bit for bit.  multi_device: sharded over sfb_set_devices.
+inline void solve_qp_tall_batch(const QPSolverParams & prm, int64_t B, int n, int m, const double * P, const double * q,
+                                const double * A, const double * l, const double * u, const double * warm_x,
+                                const double * warm_y, double * x, double * y, double * obj, uint32_t * iter, int32_t * code,
+                                bool multi_device = false)
+{
+  const sfb_qp_params c = prm.to_c();
+  sfb_check((multi_device ? sfb_qp_dense_tall_solve_batch_host_multi : sfb_qp_dense_tall_solve_batch_host)(
+    &c, B, n, m, P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code));
+}
+
 /// The parameter mapping of the reference's OSQP comparator (compat/osqp.hpp:54-80): what solve_qp_osqp sets on an
 /// OSQPSettings before osqp_setup.  OSQP itself is not part of this tree; field names are OSQP's.
 struct OsqpSettingsView {

@@ -7,7 +7,8 @@ from . import _capi  # noqa: F401  (fails loudly if libsfb.so is missing)
 from ._capi import debug_set, debug_set_from  # noqa: F401  (debug knobs of the library: tests, A/B measurements)
 from .qp import (QPBatchSolution, QPSolution, QPSolutionStatus, QPSolver, QPSolverParams,  # noqa: F401
                  QuadraticProgram, pack_colmajor, random_qp_batch, solve_qp, solve_qp_batch_device, solve_qp_batch_device_ws, Workspace,
-                 solve_qp_batch_host, QuadraticProgramSparse, SparseQPPlan, solve_qp_sparse)
+                 solve_qp_batch_host, QuadraticProgramSparse, SparseQPPlan, solve_qp_sparse,
+                 solve_qp_tall_batch_device, solve_qp_tall_batch_host)
 
 from .ekf import (ekf_predict_batch_device, ekf_predict_batch_host, ekf_predict_stepper_batch_device,  # noqa: F401
                   ekf_predict_update_batch_device, ekf_step_batch_host, ekf_update_batch_device)

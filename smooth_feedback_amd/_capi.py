@@ -74,6 +74,9 @@ def _load():
     L.sfb_qp_dense_solve_batch.argtypes = [C.POINTER(SfbQPParams), i64, i32, i32] + [dp] * 12 + [vp]
     L.sfb_qp_dense_solve_batch_host.argtypes = [C.POINTER(SfbQPParams), i64, i32, i32] + [dp] * 12
     L.sfb_qp_dense_solve_batch_host_multi.argtypes = L.sfb_qp_dense_solve_batch_host.argtypes
+    L.sfb_qp_dense_tall_solve_batch.argtypes = L.sfb_qp_dense_solve_batch.argtypes
+    L.sfb_qp_dense_tall_solve_batch_host.argtypes = L.sfb_qp_dense_solve_batch_host.argtypes
+    L.sfb_qp_dense_tall_solve_batch_host_multi.argtypes = L.sfb_qp_dense_solve_batch_host.argtypes
     L.sfb_qp_dense_solve_batch_host_trace.argtypes = [C.POINTER(SfbQPParams), i64, i32, i32] + [dp] * 12 + [dp, i32]
     L.sfb_qp_dense_solve_batch_trace.argtypes = [C.POINTER(SfbQPParams), i64, i32, i32] + [dp] * 12 + [dp, i32, vp]
     L.sfb_qp_dense_solve_batch_host_phases.argtypes = [C.POINTER(SfbQPParams), i64, i32, i32] + [dp] * 12 + [dp, i32, dp]

@@ -593,6 +593,53 @@ sfb_status sfb_qp_dense_solve_batch(const sfb_qp_params *prm, int64_t batch, int
   return dense_solve_impl(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code, nullptr, false, stream);
 }
 
+// ---- tall problems through the reduced n x n system (qp_dense_tall.hip) ----
+static sfb_status check_tall_size(int n, int m)
+{
+  if (n > SFB_QP_DENSE_TALL_MAX_N || m > SFB_QP_DENSE_TALL_MAX_M)
+    return fail(SFB_ERR_UNSUPPORTED, "the reduced-KKT route needs n <= SFB_QP_DENSE_TALL_MAX_N and m <= SFB_QP_DENSE_TALL_MAX_M");
+  return SFB_OK;
+}
+
+sfb_status sfb_qp_dense_tall_solve_batch(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
+                                         const double *q, const double *A, const double *l, const double *u,
+                                         const double *warm_x, const double *warm_y, double *x, double *y, double *obj,
+                                         uint32_t *iter, int32_t *code, void *stream)
+{
+  sfb_status st = check_qp_args(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, code);
+  if (st != SFB_OK) return st;
+  if ((st = check_tall_size(n, m)) != SFB_OK) return st;
+  if ((st = require_device()) != SFB_OK) return st;
+  if (batch == 0) return SFB_OK;
+  const hipStream_t hs = static_cast<hipStream_t>(stream);
+  const sfb::DenseKernelParams kp = make_kernel_params(prm, n, m);
+  const sfb::QpBatch g{P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code};
+  // rows that fit neither registers nor LDS keep sy and z in device memory: stream-ordered, like the big dense kernel's factor
+  const size_t bytes = sfb::qp_dense_tall_ws_bytes(n, m, batch);
+  char *buf          = nullptr;
+  bool async_alloc   = true;
+  hipError_t e       = hipSuccess;
+  if (bytes) {
+    e = hipMallocAsync(reinterpret_cast<void **>(&buf), bytes, hs);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      async_alloc = false;
+      e           = hipMalloc(reinterpret_cast<void **>(&buf), bytes);
+      if (e != hipSuccess) return hip_fail(e, "hipMalloc");
+    }
+  }
+  e = sfb::qp_dense_tall_launch(kp, batch, g, hs, buf);
+  if (!bytes) {
+  } else if (async_alloc) {
+    (void)hipFreeAsync(buf, hs);
+  } else {
+    (void)hipStreamSynchronize(hs);
+    (void)hipFree(buf);
+  }
+  if (e != hipSuccess) return hip_fail(e, "qp_dense_tall_kernel launch");
+  return SFB_OK;
+}
+
 sfb_status sfb_qp_dense_solve_batch_trace(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P, const double *q,
                                           const double *A, const double *l, const double *u, const double *warm_x, const double *warm_y,
                                           double *x, double *y, double *obj, uint32_t *iter, int32_t *code, double *trace,
@@ -706,21 +753,38 @@ void host_stage_give(int dev, HostStage s)
 
 extern "C" {
 
+static sfb_status dense_host_multi_impl(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P, const double *q,
+                                        const double *A, const double *l, const double *u, const double *warm_x, const double *warm_y,
+                                        double *x, double *y, double *obj, uint32_t *iter, int32_t *code, const bool tall)
+{
+  sfb_status st = check_qp_args(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, code);
+  if (st != SFB_OK) return st;
+  if (tall && (st = check_tall_size(n, m)) != SFB_OK) return st;
+  if (batch == 0) return require_device();
+  const size_t N = (size_t)n, M = (size_t)m;
+  const auto solve = tall ? sfb_qp_dense_tall_solve_batch_host : sfb_qp_dense_solve_batch_host;
+  return sfb::run_sharded(batch, [&](int, int64_t b0, int64_t cnt) {
+    const size_t o = (size_t)b0;
+    return solve(prm, cnt, n, m, P + o * N * N, q + o * N, A + o * M * N, l + o * M, u + o * M,
+                 warm_x ? warm_x + o * N : nullptr, warm_y ? warm_y + o * M : nullptr, x + o * N,
+                 y + o * M, obj ? obj + o : nullptr, iter ? iter + o : nullptr, code + o);
+  });
+}
+
 sfb_status sfb_qp_dense_solve_batch_host_multi(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
                                                const double *q, const double *A, const double *l, const double *u,
                                                const double *warm_x, const double *warm_y, double *x, double *y,
                                                double *obj, uint32_t *iter, int32_t *code)
 {
-  sfb_status st = check_qp_args(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, code);
-  if (st != SFB_OK) return st;
-  if (batch == 0) return require_device();
-  const size_t N = (size_t)n, M = (size_t)m;
-  return sfb::run_sharded(batch, [&](int, int64_t b0, int64_t cnt) {
-    const size_t o = (size_t)b0;
-    return sfb_qp_dense_solve_batch_host(prm, cnt, n, m, P + o * N * N, q + o * N, A + o * M * N, l + o * M, u + o * M,
-                                         warm_x ? warm_x + o * N : nullptr, warm_y ? warm_y + o * M : nullptr, x + o * N,
-                                         y + o * M, obj ? obj + o : nullptr, iter ? iter + o : nullptr, code + o);
-  });
+  return dense_host_multi_impl(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code, false);
+}
+
+sfb_status sfb_qp_dense_tall_solve_batch_host_multi(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
+                                                    const double *q, const double *A, const double *l, const double *u,
+                                                    const double *warm_x, const double *warm_y, double *x, double *y,
+                                                    double *obj, uint32_t *iter, int32_t *code)
+{
+  return dense_host_multi_impl(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code, true);
 }
 
 void sfb_host_staging_trim(void)
@@ -734,13 +798,15 @@ void sfb_host_staging_trim(void)
     if (kv.second.mem) (void)hipFree(kv.second.mem);
 }
 
-sfb_status sfb_qp_dense_solve_batch_host(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
-                                         const double *q, const double *A, const double *l, const double *u,
-                                         const double *warm_x, const double *warm_y, double *x, double *y,
-                                         double *obj, uint32_t *iter, int32_t *code)
+// the host-pointer solve of both dense routes (tall: the reduced-KKT kernel) on the kept staging buffer
+static sfb_status dense_host_impl(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
+                                  const double *q, const double *A, const double *l, const double *u,
+                                  const double *warm_x, const double *warm_y, double *x, double *y,
+                                  double *obj, uint32_t *iter, int32_t *code, const bool tall)
 {
   sfb_status st = check_qp_args(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, code);
   if (st != SFB_OK) return st;
+  if (tall && (st = check_tall_size(n, m)) != SFB_OK) return st;
   st = require_device();
   if (st != SFB_OK) return st;
   if (batch == 0) return SFB_OK;
@@ -807,7 +873,8 @@ sfb_status sfb_qp_dense_solve_batch_host(const sfb_qp_params *prm, int64_t batch
       if ((e = H2D(dwy, warm_y, B * M * 8)) != hipSuccess) break;
     }
     tv1 = clk::now();
-    st = sfb_qp_dense_solve_batch(prm, batch, n, m, dP, dq, dA, dl, du, dwx, dwy, dx, dy, dobj, dit, dcode, nullptr);
+    st = (tall ? sfb_qp_dense_tall_solve_batch : sfb_qp_dense_solve_batch)(prm, batch, n, m, dP, dq, dA, dl, du, dwx, dwy, dx, dy, dobj, dit,
+                                                                           dcode, nullptr);
     if (st != SFB_OK) break;
     if ((e = hipDeviceSynchronize()) != hipSuccess) break;
     tv2 = clk::now();
@@ -819,7 +886,7 @@ sfb_status sfb_qp_dense_solve_batch_host(const sfb_qp_params *prm, int64_t batch
   } while (false);
   if (e != hipSuccess) st = hip_fail(e, "sfb_qp_dense_solve_batch_host");
   const auto tv3 = clk::now();
-  if (st == SFB_OK && prm->verbose && batch == 1) {  // (inputs still on the device)
+  if (st == SFB_OK && prm->verbose && batch == 1 && !tall) {  // (inputs still on the device)
     uint32_t it1 = 0;
     const bool have_it = iter ? (it1 = iter[0], true) : hipMemcpy(&it1, dit, 4, hipMemcpyDeviceToHost) == hipSuccess;
     if (n + m <= sfb::kDenseMidMaxK) dense_native_table(prm, n, m, dP, dq, dA, dl, du, dwx, dwy, have_it ? &it1 : nullptr, code);  // the solve's own iterates
@@ -831,10 +898,26 @@ sfb_status sfb_qp_dense_solve_batch_host(const sfb_qp_params *prm, int64_t batch
       itv.resize(B);
       if (hipMemcpy(itv.data(), dit, B * 4, hipMemcpyDeviceToHost) != hipSuccess) itv.clear();
     }
-    sfb::verbose_report("dense QP batch", batch, n, m, ms(tv0, tv1), ms(tv1, tv2), ms(tv2, tv3), code,
+    sfb::verbose_report(tall ? "tall dense QP batch (reduced KKT)" : "dense QP batch", batch, n, m, ms(tv0, tv1), ms(tv1, tv2), ms(tv2, tv3), code,
                         iter ? iter : (itv.empty() ? nullptr : itv.data()));
   }
   return st;
+}
+
+sfb_status sfb_qp_dense_solve_batch_host(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
+                                         const double *q, const double *A, const double *l, const double *u,
+                                         const double *warm_x, const double *warm_y, double *x, double *y,
+                                         double *obj, uint32_t *iter, int32_t *code)
+{
+  return dense_host_impl(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code, false);
+}
+
+sfb_status sfb_qp_dense_tall_solve_batch_host(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
+                                              const double *q, const double *A, const double *l, const double *u,
+                                              const double *warm_x, const double *warm_y, double *x, double *y,
+                                              double *obj, uint32_t *iter, int32_t *code)
+{
+  return dense_host_impl(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code, true);
 }
 
 sfb_status sfb_qp_dense_solve_batch_host_trace(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P, const double *q,

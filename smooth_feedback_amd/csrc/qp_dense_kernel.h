@@ -57,6 +57,13 @@ hipError_t qp_dense_mid_launch(const DenseKernelParams &kp, int64_t batch, const
 hipError_t qp_dense_mid_trace_launch(const DenseKernelParams &kp, int64_t batch, const QpBatch &g, hipStream_t stream, double *trace, int trace_cap,
                                      double *phase_us = nullptr);
 
+// tall problems, 1 <= n <= 16 and any m: the reduced-KKT route (qp_dense_tall.hip), one QP per wavefront, the n x n system
+// S = P + sigma I + A' diag(rho) A instead of the (n+m)-square KKT matrix.  Agrees with the kernels above to rounding only.
+// workspace: qp_dense_tall_ws_bytes bytes of device memory (0 while the rows of a QP fit in registers or LDS)
+constexpr int kDenseTallMaxN = 16;
+size_t qp_dense_tall_ws_bytes(int n, int m, int64_t batch);
+hipError_t qp_dense_tall_launch(const DenseKernelParams &kp, int64_t batch, const QpBatch &g, hipStream_t stream, void *workspace);
+
 hipError_t qp_dense_launch(const DenseKernelParams &kp, int64_t batch, const double *P, const double *q,
                            const double *A, const double *l, const double *u, const double *wx, const double *wy,
                            double *x, double *y, double *obj, uint32_t *iter, int32_t *code, hipStream_t stream,

@@ -165,6 +165,53 @@ def solve_qp_batch_device(B, n, m, dP, dq, dA, dl, du, dx, dy, dobj, diter, dcod
         dobj or None, diter or None, dcode, stream or None))
 
 
+TALL_MAX_N, TALL_MAX_M = 16, 1 << 20  # SFB_QP_DENSE_TALL_MAX_N / _M (include/sfb.h)
+
+
+def solve_qp_tall_batch_host(P, q, A, l, u, prm: Optional[QPSolverParams] = None, warm_x=None, warm_y=None, multi_device=False):
+    """solve_qp_batch_host for TALL problems (1 <= n <= 16, many rows) through the reduced-KKT route
+    (sfb_qp_dense_tall_solve_batch_host, or _host_multi): the same algorithm on the n x n system
+    S = P + sigma I + A' diag(rho) A instead of the (n+m)-square KKT matrix.  Same layout and result type; results agree
+    with solve_qp_batch_host to rounding, not bit for bit."""
+    q = np.ascontiguousarray(q, dtype=np.float64)
+    l = np.ascontiguousarray(l, dtype=np.float64)
+    if q.ndim != 2 or l.ndim != 2:
+        raise ValueError("q and l must be (batch, n) / (batch, m)")
+    B, n = q.shape
+    m = l.shape[1]
+    if l.shape[0] != B:
+        raise ValueError("q and l must have the same batch size")
+    P = _f64(P, (B, n * n))
+    A = _f64(A, (B, m * n))
+    u = _f64(u, (B, m))
+    if (warm_x is None) != (warm_y is None):
+        raise ValueError("warm_x and warm_y must be given together")
+    if warm_x is not None:
+        warm_x = _f64(warm_x, (B, n))
+        warm_y = _f64(warm_y, (B, m))
+    x = np.empty((B, n))
+    y = np.empty((B, m))
+    obj = np.empty(B)
+    it = np.empty(B, dtype=np.uint32)
+    code = np.empty(B, dtype=np.int32)
+    cp = (prm or QPSolverParams()).to_c()
+    fn = _capi.lib.sfb_qp_dense_tall_solve_batch_host_multi if multi_device else _capi.lib.sfb_qp_dense_tall_solve_batch_host
+    _capi.check(fn(
+        C.byref(cp), B, n, m, _ptr(P), _ptr(q), _ptr(A), _ptr(l), _ptr(u), _ptr(warm_x), _ptr(warm_y),
+        _ptr(x), _ptr(y), _ptr(obj), _ptr(it), _ptr(code)))
+    return QPBatchSolution(code=code, iter=it, primal=x, dual=y, objective=obj)
+
+
+def solve_qp_tall_batch_device(B, n, m, dP, dq, dA, dl, du, dx, dy, dobj, diter, dcode, prm=None,
+                               dwarm_x=0, dwarm_y=0, stream=0):
+    """solve_qp_batch_device on the reduced-KKT route for tall problems (sfb_qp_dense_tall_solve_batch): asynchronous on
+    `stream`, DEVICE pointers as ints."""
+    cp = (prm or QPSolverParams()).to_c()
+    _capi.check(_capi.lib.sfb_qp_dense_tall_solve_batch(
+        C.byref(cp), B, n, m, dP, dq, dA, dl, du, dwarm_x or None, dwarm_y or None, dx, dy,
+        dobj or None, diter or None, dcode, stream or None))
+
+
 class Workspace:
     """sfb_workspace: device memory the caller creates once and hands to every call (no allocation per call).
     Workspace.for_dense(batch, n, m, prm) sizes it with sfb_qp_dense_workspace_bytes."""
