@@ -15,6 +15,7 @@
 #include <smooth_feedback_amd/mpc.hpp>
 #include <smooth/feedback/mpc.hpp>  // the reference's include path and namespace (sfbx_test_mpc_api)
 
+#include "lie_eval.h"
 #include "vehicle_model.h"
 
 using namespace smooth_feedback_amd;
@@ -1191,4 +1192,40 @@ int sfbx_test_ekf_predict_linear9(const double * A9, const double * F9, double *
   } catch (const std::exception &) {
     return 1;
   }
+}
+
+/* the QPs of sfbx_asif_swarm_step's first tick, assembled as ASIFSwarm assembles them (asif_to_qp_update with the per-agent
+ * callbacks) but not solved: no GPU */
+int sfbx_asif_swarm_assemble(int64_t batch, uint64_t seed, int K, double * P, double * q, double * A, double * l, double * u)
+{
+  const auto prm = vehicle_asif_params(K);
+  const VehicleDyn6 f{};
+  const VehicleH hb{};
+  const VehicleBU bub{};
+  QuadraticProgram<> qp;
+  for (int64_t b = 0; b < batch; ++b) {
+    const X6 g = perturbed(xdes6(0.025 * double(b % 400)), seed + (uint64_t)b);
+    std::mt19937_64 rng(seed + 7919u * (uint64_t)b);
+    std::uniform_real_distribution<double> d(-0.5, 0.5);
+    U2 ud;
+    ud.v = {d(rng), d(rng)};
+    asif_to_qp_allocate<X6, U2>(qp, prm.asif.K, prm.ulim.rows, prm.nh);
+    const ASIFProblem<X6, U2> pbm{prm.T, g, ud, prm.u_weight, prm.ulim};
+    asif_to_qp_update<X6, U2>(qp, pbm, prm.asif, f, detail::AgentFn<VehicleH, X6>{hb, (size_t)b}, detail::AgentFn<VehicleBU, X6>{bub, (size_t)b});
+    const size_t n = (size_t)qp.n, m = (size_t)qp.m;
+    copy_qp(qp, P + b * n * n, q + b * n, A + b * m * n, l + b * m, u + b * m);
+  }
+  return 0;
+}
+
+int sfbx_lie_eval_widths(int group, int op, int * win, int * wout) { return sfbx::lie_eval_widths(group, op, win, wout) ? 0 : -1; }
+
+int sfbx_lie_eval(int group, int op, int64_t count, const double * in, double * out)
+{
+  int win = 0, wout = 0;
+  if (count < 0 || !sfbx::lie_eval_widths(group, op, &win, &wout)) return -1;
+  sfbx::lie_dispatch_group(group, [&]<class G>() {
+    for (int64_t b = 0; b < count; ++b) sfbx::lie_eval_item<G>(op, in + b * win, out + b * wout);
+  });
+  return 0;
 }

@@ -111,6 +111,15 @@ int sfbx_asif_swarm_step(int64_t batch, uint64_t seed, int K, int ticks, double 
                          double *wy);
 /* the states (x, y, cos, sin, v0, v1, v2) [batch][7] and desired inputs [batch][2] sfbx_asif_swarm_step starts from */
 int sfbx_asif_swarm_states(int64_t batch, uint64_t seed, double *states, double *udes);
+/* the QPs [batch][...] of the FIRST tick of sfbx_asif_swarm_step (same agents, same assembly code path), not solved.
+ * Host only (no GPU). */
+int sfbx_asif_swarm_assemble(int64_t batch, uint64_t seed, int K, double *P, double *q, double *A, double *l, double *u);
+/* The operations of include/smooth_feedback_amd/lie.hpp on `count` items (examples/lie_eval.h: group and operation
+ * ids, element layouts): in [count][win], out [count][wout] with the widths of sfbx_lie_eval_widths.  Returns -1 when
+ * the group has no such operation.  Host code; sfbx_lie_eval_device (models_device.hip) runs the same item function as
+ * one GPU thread per item. */
+int sfbx_lie_eval_widths(int group, int op, int *win, int *wout);
+int sfbx_lie_eval(int group, int op, int64_t count, const double *in, double *out);
 /* vehicle EKFs, one host EKF<> object per filter: `steps` x (predict(Q, tau, dt) + update(y[step], R)); the host twin of
  * sfbx_ekf_swarm_device (models_device.hip) */
 int sfbx_ekf_swarm_host(int64_t batch, int steps, int rk4, double tau, double dt, const double *states, const double *P0,

@@ -13,6 +13,7 @@
 #include <smooth_feedback_amd/mpc_device.hpp>
 #include <smooth_feedback_amd/multi_device.hpp>
 
+#include "lie_eval.h"
 #include "vehicle_model.h"
 
 using namespace smooth_feedback_amd;
@@ -174,6 +175,16 @@ int ekf_swarm(int64_t batch, int steps, int fused, double tau, double dt, const 
     info[b] = inf[b];
   }
   return 0;
+}
+
+// one thread per item through sfbx::lie_eval_item, the function sfbx_lie_eval (models.cpp) runs on the host
+template<class G>
+__global__ void __launch_bounds__(64) lie_eval_kernel(const int op, const int64_t count, const int win, const int wout, const double * __restrict__ in,
+                                                      double * __restrict__ out)
+{
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= count) return;
+  sfbx::lie_eval_item<G>(op, in + b * win, out + b * wout);
 }
 }  // namespace
 
@@ -376,6 +387,35 @@ int sfbx_asif_swarm_device_step_tall(int64_t batch, int K, int ticks, const doub
                                      double * x, double * y, double * wx, double * wy, double * seconds)
 {
   return asif_swarm_device_step_impl(batch, K, ticks, states, udes, u_out, codes, iters, P, q, A, l, u, x, y, wx, wy, seconds, true);
+}
+
+/* sfbx_lie_eval (models.h) on the GPU: in [count][win] is copied to a plain device buffer, one thread per item runs the
+ * item function of examples/lie_eval.h (the lie.hpp operations with the device maths library), out [count][wout] comes back. */
+int sfbx_lie_eval_device(int group, int op, int64_t count, const double * in, double * out)
+{
+  int win = 0, wout = 0;
+  if (count < 0 || !sfbx::lie_eval_widths(group, op, &win, &wout)) return -1;
+  if (count == 0) return 0;
+  const size_t nin = (size_t)count * win * sizeof(double), nout = (size_t)count * wout * sizeof(double);
+  double *din = nullptr, *dout = nullptr;
+  if (hipMalloc(reinterpret_cast<void **>(&din), nin) != hipSuccess) return -3;
+  if (hipMalloc(reinterpret_cast<void **>(&dout), nout) != hipSuccess) { (void)hipFree(din); return -3; }
+  hipError_t e = hipMemcpy(din, in, nin, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    sfbx::lie_dispatch_group(group, [&]<class G>() {
+      hipLaunchKernelGGL((lie_eval_kernel<G>), dim3((unsigned)((count + 63) / 64)), dim3(64), 0, nullptr, op, count, win, wout, din, dout);
+    });
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, dout, nout, hipMemcpyDeviceToHost);
+  (void)hipFree(din);
+  (void)hipFree(dout);
+  if (e != hipSuccess) {
+    std::fprintf(stderr, "sfbx_lie_eval_device: %s\n", hipGetErrorString(e));
+    return -2;
+  }
+  return 0;
 }
 
 }  // extern "C"

@@ -282,3 +282,38 @@ def vehicle_swarm_sim(batch, ticks, K_mpc=30, K_asif=200, seed=0, reduced_kkt=Fa
                                           _p(out["u_asif"]), _p(out["mpc_bad"]), _p(out["asif_bad"]), _p(out["hmin"]), _p(out["seconds"]))
     assert rc == 0, rc
     return out
+
+
+def asif_swarm_assemble(batch, K, seed=0):
+    """The QPs of asif_swarm_step's first tick, assembled on the host and not solved (no GPU)."""
+    n, m = 3, K + 3
+    out = dict(P=np.zeros((batch, n * n)), q=np.zeros((batch, n)), A=np.zeros((batch, m * n)), l=np.zeros((batch, m)),
+               ub=np.zeros((batch, m)))
+    rc = lib().sfbx_asif_swarm_assemble(C.c_int64(batch), C.c_uint64(seed), K, _p(out["P"]), _p(out["q"]), _p(out["A"]), _p(out["l"]),
+                                        _p(out["ub"]))
+    assert rc == 0, rc
+    return out
+
+
+LIE_GROUPS = dict(R3=0, SE2=1, SO3=2, X6=3, X12=4)
+LIE_OPS = dict(exp=0, log=1, mul=2, ad=3, dr_expinv=4, rplus=5, rminus=6, rminus_rplus=7)
+
+
+def lie_eval_widths(group, op):
+    """doubles per item (in, out) of lie_eval, or None when the group has no such operation (examples/lie_eval.h)"""
+    win, wout = C.c_int(0), C.c_int(0)
+    if lib().sfbx_lie_eval_widths(LIE_GROUPS[group], LIE_OPS[op], C.byref(win), C.byref(wout)) != 0:
+        return None
+    return win.value, wout.value
+
+
+def lie_eval(group, op, inp, device=False):
+    """The lie.hpp operation `op` of `group` on every row of inp [count][win]: on the host, or (device=True) one GPU thread
+    per item running the same functions."""
+    win, wout = lie_eval_widths(group, op)
+    inp = np.ascontiguousarray(inp, dtype=np.float64).reshape(-1, win)
+    out = np.full((len(inp), wout), np.nan)
+    fn = dev_lib().sfbx_lie_eval_device if device else lib().sfbx_lie_eval
+    rc = fn(LIE_GROUPS[group], LIE_OPS[op], C.c_int64(len(inp)), _p(inp), _p(out))
+    assert rc == 0, rc
+    return out

@@ -3,8 +3,8 @@
 // (linearisation of f and h at the estimate, state propagation, g (+) delta) stays here on the host;
 // the covariance algebra runs on the GPU through sfb_ekf_*_batch (include/sfb.h).
 //
-// Derivatives: analytic if the callable offers jacobian(...), else forward differences with step
-// sqrt(eps) (the reference's default without the autodiff header, SURVEY.md section 8 notes).
+// Derivatives: always forward differences with step sqrt(eps) (the reference's default without the
+// autodiff header, SURVEY.md section 8 notes); a jacobian(...) member of the callable is not looked at.
 // Stepper (ekf.hpp:27-31, the Stp template argument): explicit Euler (the reference's default) or
 // runge_kutta4 (the one tests/test_ekf.cpp:113-115 instantiates); predict(f, Q, tau, dt) runs ceil(tau/dt)
 // substeps and re-linearises before each one, covariance first (ekf.hpp:93-102).  The state is stepped on

@@ -5,8 +5,8 @@
 // (reference README.md:17-18, mpc.hpp:498,505,518, ekf.hpp:137).  Only what the hot path's callers
 // need is restated: R^n, SE(2), SO(3) and Bundle<...> with exp/log, ad and dr_expinv (the inverse right
 // Jacobian used by MPCCE::jacobian, mpc.hpp:293-301).  Semantics as summarised in SURVEY.md section
-// 8 ("smooth semantics the host side must restate"); parity with the real library is pinned only
-// by group identities (tests), not by golden values.
+// 8 ("smooth semantics the host side must restate").  Every operation is pinned to 60-digit values computed from the
+// matrix groups (tests/golden/lie_reference.npz; tests/test_lie_host.py on the host, tests/test_lie_gpu.py in device code).
 #pragma once
 #include <array>
 #include <cmath>
@@ -98,6 +98,28 @@ struct Rn {
   SFB_LIE_HD static Mat<N, N> dr_expinv(const Tangent &) { return Mat<N, N>::Identity(); }
 };
 
+namespace detail {
+// (1 - cos th) / th from sin and cos of th, th != 0.  For cos th > 0 the difference 1 - cos th cancels (to eps / th^2
+// relative: 1e-6 at th = 1e-5); sin^2 / (1 + cos) is the same number without a difference.
+SFB_LIE_HD inline double one_minus_cos_over(double th, double sn, double cs)
+{
+  return (cs > 0.0) ? (sn / th) * sn / (1.0 + cs) : (1.0 - cs) / th;
+}
+// k(th) = 1/th^2 - (1 + cos th) / (2 th sin th), the coefficient of ad^2 in dr_expinv (SE2 and SO3: ad^3 = -th^2 ad)
+//       = sum_n |B_2n| th^(2n-2) / (2n)!  (Bernoulli numbers).
+// The closed form subtracts two numbers of size 1/th^2 (absolute error eps / th^2: 1e-8 just above a switch at th^2 = 1e-8),
+// so the series runs until its truncation, 1.3e-11 th^12, meets that error: th^2 < 0.16 (both 3e-16 there).  Towards pi
+// (1 + cos) / sin divides two vanishing numbers; sin / (1 - cos) is the same cotangent of th / 2 without them.
+SFB_LIE_HD inline double dr_expinv_coef(double th2)
+{
+  if (th2 < 0.16)
+    return 1.0 / 12.0 + th2 * (1.0 / 720.0 + th2 * (1.0 / 30240.0 + th2 * (1.0 / 1209600.0 + th2 * (1.0 / 47900160.0 + th2 * (691.0 / 1307674368000.0)))));
+  const double th = std::sqrt(th2), cs = std::cos(th), sn = std::sin(th);
+  const double cot_half = (cs >= 0.0) ? (1.0 + cs) / sn : sn / (1.0 - cs);
+  return 1.0 / th2 - cot_half / (2.0 * th);
+}
+}  // namespace detail
+
 // ---- SE(2): tangent order (v_x, v_y, omega) ----
 struct SE2 {
   static constexpr int Dof           = 3;
@@ -113,14 +135,15 @@ struct SE2 {
   {
     const double th = a[2], th2 = th * th;
     double A, B;  // A = sin(th)/th, B = (1-cos(th))/th
+    const double cs = std::cos(th), sn = std::sin(th);
     if (th2 < 1e-10) {
       A = 1.0 - th2 / 6.0;
       B = th / 2.0 - th * th2 / 24.0;
     } else {
-      A = std::sin(th) / th;
-      B = (1.0 - std::cos(th)) / th;
+      A = sn / th;
+      B = detail::one_minus_cos_over(th, sn, cs);
     }
-    return SE2{A * a[0] - B * a[1], B * a[0] + A * a[1], std::cos(th), std::sin(th)};
+    return SE2{A * a[0] - B * a[1], B * a[0] + A * a[1], cs, sn};
   }
   SFB_LIE_HD Tangent log() const
   {
@@ -131,7 +154,7 @@ struct SE2 {
       B = th / 2.0 - th * th2 / 24.0;
     } else {
       A = s / th;
-      B = (1.0 - c) / th;
+      B = detail::one_minus_cos_over(th, s, c);
     }
     const double den = A * A + B * B;
     return {(A * x + B * y) / den, (-B * x + A * y) / den, th};
@@ -154,8 +177,7 @@ struct SE2 {
   // inverse of the right Jacobian of exp:  I + ad/2 + (1/th^2 - (1+cos th)/(2 th sin th)) ad^2
   SFB_LIE_HD static Mat<3, 3> dr_expinv(const Tangent &a)
   {
-    const double th = a[2], th2 = th * th;
-    const double k  = (th2 < 1e-8) ? (1.0 / 12.0 + th2 / 720.0) : (1.0 / th2 - (1.0 + std::cos(th)) / (2.0 * th * std::sin(th)));
+    const double k = detail::dr_expinv_coef(a[2] * a[2]);
     const Mat<3, 3> A = ad(a);
     return Mat<3, 3>::Identity() + 0.5 * A + k * (A * A);
   }
@@ -218,8 +240,7 @@ struct SO3 {
   }
   SFB_LIE_HD static Mat<3, 3> dr_expinv(const Tangent &a)
   {
-    const double th2 = a[0] * a[0] + a[1] * a[1] + a[2] * a[2], th = std::sqrt(th2);
-    const double k   = (th2 < 1e-8) ? (1.0 / 12.0 + th2 / 720.0) : (1.0 / th2 - (1.0 + std::cos(th)) / (2.0 * th * std::sin(th)));
+    const double k = detail::dr_expinv_coef(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
     const Mat<3, 3> A = ad(a);
     return Mat<3, 3>::Identity() + 0.5 * A + k * (A * A);
   }

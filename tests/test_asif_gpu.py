@@ -96,3 +96,13 @@ def test_device_side_assembly_of_the_swarm(oracle, K, B):
     assert np.array_equal(dev3["code"], host3["code"])
     assert np.abs(dev3["u"] - host3["u"]).max() <= 1e-6
     assert (dev3["code"] == 0).mean() > 0.9
+
+
+@pytest.mark.parametrize("K,B", [(10, 48), (200, 24)])
+def test_swarm_solves_the_qps_the_host_test_checks(K, B):
+    """tests/test_asif_host.py pins the assembly through asif_swarm_assemble (no GPU); the swarm front hands exactly those
+    QPs to the solver"""
+    step = M.asif_swarm_step(B, K, ticks=1, seed=3)
+    asm = M.asif_swarm_assemble(B, K, seed=3)
+    for key in ("P", "q", "A", "l", "ub"):
+        assert np.array_equal(step[key], asm[key]), key

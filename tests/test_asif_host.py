@@ -88,3 +88,105 @@ def test_structure_asserted_by_the_reference_test():
     assert np.allclose(qp["l"][Nh * K:Nh * K + niq], -1.0 - udes)
     assert np.allclose(qp["u"][Nh * K:Nh * K + niq], 1.0 - udes)
     assert qp["l"][Nh * K + niq] == 0 and qp["u"][Nh * K + niq] == np.inf
+
+
+# ---- the vehicle filter (examples/vehicle_model.h): X6 = SE2 x R^3, K up to 200, closed-loop backup dynamics ----
+_E = np.zeros((3, 3, 3))            # hat of the basis of se(2), tangent order (vx, vy, omega)
+_E[0, 0, 2] = _E[1, 1, 2] = 1.0
+_E[2, 1, 0], _E[2, 0, 1] = 1.0, -1.0
+
+
+def _se2_expm(a):
+    """exp of hat(a) by its power series on the 3x3 homogeneous matrix (|a| < 1 here: 1 / 25! = 6e-26)"""
+    X = np.einsum("i,ijk->jk", a, _E)
+    out, term = np.eye(3), np.eye(3)
+    for n in range(1, 25):
+        term = term @ X / n
+        out = out + term
+    return out
+
+
+def _se2_ad(a):
+    """ad(a) e_i = vee([hat(a), hat(e_i)])"""
+    A = np.einsum("i,ijk->jk", a, _E)
+    cols = [A @ _E[i] - _E[i] @ A for i in range(3)]
+    return np.array([[c[0, 2] for c in cols], [c[1, 2] for c in cols], [c[1, 0] for c in cols]])
+
+
+def restate_vehicle(state, udes, K):
+    """asif_func.hpp:139-198 for the vehicle filter with ANALYTIC Jacobians and the SE2 arithmetic in matrix form:
+    state (x, y, cos, sin, v0, v1, v2); parameters of vehicle_asif_params(K); barrier VehicleH (0.7 away from (0, -2.3)),
+    backup controller VehicleBU (brake and turn), dynamics VehicleDyn6."""
+    T, alpha, dtmax, relax, W = 2.5, 5.0, 0.01, 100.0, (20.0, 1.0)
+    ul, uu = np.array([-0.2, -0.5]), np.array([0.5, 0.5])
+    nu, M = 2, K + 2 + 1
+    A = np.zeros((M, nu + 1)); l = np.zeros(M); u = np.zeros(M)
+
+    def f(v, uin):
+        return np.array([v[0], v[1], v[2], -0.2 * v[0] + uin[0], 0.0, -0.4 * v[2] + uin[1]])
+
+    def bu(v):
+        return np.array([0.2 * v[0], -0.5])
+    dfdx = np.zeros((6, 6))
+    dfdx[0, 3] = dfdx[1, 4] = dfdx[2, 5] = 1.0
+    dfdx[3, 3], dfdx[5, 5] = -0.2, -0.4
+    dfdu = np.zeros((6, 2))
+    dfdu[3, 0] = dfdu[5, 1] = 1.0
+    dbudx = np.zeros((2, 6))
+    dbudx[0, 3] = 0.2
+    dcl = dfdx + dfdu @ dbudx                                  # d/dx f(x, bu(x))
+
+    g = np.array([[state[2], -state[3], state[0]], [state[3], state[2], state[1]], [0.0, 0.0, 1.0]])
+    v = np.array(state[4:7], dtype=float)
+    f0 = f(v, udes)                                            # :155-156
+    tau = T / K
+    dt = min(dtmax, tau)
+    t, S = 0.0, np.eye(6)
+    for k in range(K):
+        d = g[:2, 2] - np.array([0.0, -2.3])
+        nrm = np.hypot(d[0], d[1])
+        dh_dx = np.zeros(6)
+        dh_dx[:2] = d @ g[:2, :2] / nrm                        # p (+) a = p + R (a0, a1)
+        dh_dx0 = dh_dx @ S
+        A[k, :nu] = dh_dx0 @ dfdu                              # :169
+        l[k] = -0.0 - alpha * (nrm - 0.7) - dh_dx0 @ f0        # :170 (h does not depend on t)
+        u[k] = np.inf
+        dt_act = min(dt, tau * (k + 1) - t)                    # :174
+        while t < tau * (k + 1):
+            fx = f(v, bu(v))
+            g, v = g @ _se2_expm(dt_act * fx[:3]), v + dt_act * fx[3:]     # the state first (:176) ...
+            fcl = f(v, bu(v))                                  # ... the sensitivity ODE sees the stepped state (:148-151)
+            Acl = dcl.copy()
+            Acl[:3, :3] -= _se2_ad(fcl[:3])
+            S = S + dt_act * (Acl @ S)
+            t += dt_act
+    A[:K, nu] = 1.0                                            # :183
+    A[K:K + 2, :nu] = np.eye(2)                                # :186-188, c = 0
+    l[K:K + 2], u[K:K + 2] = ul - udes, uu - udes
+    A[K + 2, nu] = 1.0                                         # :191-193
+    l[K + 2], u[K + 2] = 0.0, np.inf
+    return dict(P=np.diag([W[0], W[1], relax]), q=np.zeros(3), A=A, l=l, ub=u)
+
+
+@pytest.mark.parametrize("K,B", [(10, 48), (40, 32), (200, 24)])
+def test_vehicle_assembly_matches_numpy_restatement(K, B):
+    """The QPs the host front assembles for the swarm of asif_swarm_step (sfbx_asif_swarm_assemble: the same agents through
+    the same asif_to_qp_update + per-agent callbacks, without the GPU solve; tests/test_asif_gpu.py checks on the GPU that
+    asif_swarm_step solves exactly these) against the restatement, to the 1e-9 (1 + max|value|) that test_asif_gpu.py
+    allows between the host and device assemblies."""
+    st, ud = M.asif_swarm_states(B, seed=3)
+    got = M.asif_swarm_assemble(B, K, seed=3)
+    n, m = 3, K + 3
+    worst = {}
+    for b in range(B):
+        ref = restate_vehicle(st[b], ud[b], K)
+        mine = dict(P=got["P"][b].reshape(n, n).T, q=got["q"][b], A=got["A"][b].reshape(n, m).T, l=got["l"][b], ub=got["ub"][b])
+        for key in ("P", "q", "A", "l", "ub"):
+            a, r = mine[key], ref[key]
+            fin = np.isfinite(r)
+            assert np.array_equal(np.isfinite(a), fin) and np.array_equal(a[~fin], r[~fin]), (key, b)
+            err = np.abs(a[fin] - r[fin]).max(initial=0) / (1 + np.abs(r[fin]).max(initial=0))
+            worst[key] = max(worst.get(key, 0.0), err)
+    print("vehicle ASIF K=%d B=%d: worst |host - restatement| / (1 + max|value|): %s" % (K, B, worst))
+    assert all(e <= 1e-9 for e in worst.values()), worst
+    assert np.abs(got["A"].reshape(B, n, m)[:, :2, :K]).max() > 1e-3      # the barrier rows are not trivially zero
