@@ -1347,12 +1347,49 @@ __device__ __forceinline__ double sp_row_P(const SparsePlanDev &pl, const Item &
 // RBX: rows per lane whose products are formed together (their loads share the memory round trips): 4 is what the
 // register budget of three waves per SIMD leaves; the LAT form (one wave per SIMD pair of registers more, the loop's state in
 // LDS) takes all rows of a lane at once -- a check cost a lone wave 46 us = two iterations, most of it these round trips.
+// The two infeasibility tests need of their norms |A'dy|_inf and |P dx|_inf only the side of a threshold they lie on, and leave
+// a pass at the first group of rows that settles it (EARLY EXIT comments below).  The first group is one row per lane -- a probe
+// of one chain, which decides for an item that is still iterating -- the later ones have the width the form affords.
+// -DSFB_CHECK_FULL_PASSES: every pass to its end (A/B measurements; same results).
+#ifdef SFB_CHECK_FULL_PASSES
+constexpr bool kCheckExit = false;
+#else
+constexpr bool kCheckExit = true;
+#endif
+// -DSFB_PROF_CHECK (scripts/build_prof.sh, scripts/check_prof.py): how often the parts of a check run, in which group of 64
+// rows the first deciding row of a pass lies, and the cycles of the parts, summed over all checks of a process per form of
+// the kernel (0: standard, 1: LAT) and read back through sfb_debug_check_prof.  Off in production.
+#ifdef SFB_PROF_CHECK
+enum { kCkChecks, kCkOptimal, kCkDualRes, kCkOrdered, kCkPass2, kCkPinf, kCkPass3, kCkQdx, kCkRows, kCkDinf, kCkCycOpt, kCkCycCert, kCkCycPass2,
+       kCkCycPass3, kCkCycTail, kCkHist2 = 16, kCkHist3 = 32, kCkSlots = 48 };  // (histograms: 15 groups of 64 rows, slot 15 = no row decides)
+__device__ unsigned long long sfb_check_prof[2][kCkSlots];
+constexpr int kStdWavesPerSimd = 2;  // (the counters take the standard form's last registers: it runs two waves per SIMD, not three, in this build)
+#define SFB_CK_ADD(slot, v) { if (lane == 0) atomicAdd(&sfb_check_prof[RBX > 4][slot], (unsigned long long)(v)); }
+// (the profiling state is kept small and wave-uniform -- a 32-bit clock, one flag per pass: the kernel has no register to spare, and a
+// spill inside a sweep fails the build, check_sweep_spills.py)
+#define SFB_CK_LAP(slot) { const unsigned now_ = (unsigned)__builtin_amdgcn_s_memtime(); SFB_CK_ADD(slot, now_ - ck_pc) ck_pc = now_; }
+// the group of 64 rows [j0, j0 + 64) holds a deciding row: counted for the first such group of a pass
+#define SFB_CK_ROW(found, hit, base, j0) { if (!found && wave_ballot(hit)) { found = true; SFB_CK_ADD(base + min((j0) / kWave, 14), 1) } }
+#define SFB_CK_HIST(base, found) { if (!found) SFB_CK_ADD(base + 15, 1) }
+#else
+constexpr int kStdWavesPerSimd = 3;
+#define SFB_CK_ADD(slot, v)
+#define SFB_CK_LAP(slot)
+#define SFB_CK_ROW(found, hit, base, j0)
+#define SFB_CK_HIST(base, found)
+#endif
+
 template<int RBX = 4>
 __device__ inline int sp_check_stopping(const SparsePlanDev &pl, const Item &it, const Ws &w,
                                         const DenseKernelParams &kp, double *t, const int lane, float *score = nullptr)
 {
   const int n = uni(pl.n), m = uni(pl.m);
   const double inf = INFINITY;
+#ifdef SFB_PROF_CHECK
+  unsigned ck_pc = (unsigned)__builtin_amdgcn_s_memtime();
+  bool ck_first2 = false, ck_first3 = false;
+#endif
+  SFB_CK_ADD(kCkChecks, 1)
   const int chunk  = (uni(pl.k) + 1) / 2;  // pairs of doubles that fit the work vector
   // x and y of the check as the caller left them in the work vector (t[0, n) and t[n, n + m): LDS gathers instead of global ones,
   // the same values); the later parts use t as scratch
@@ -1375,6 +1412,7 @@ __device__ inline int sp_check_stopping(const SparsePlanDev &pl, const Item &it,
     const double Ax_norm = wave_max(a), r_norm = wave_max(r), z_norm = wave_max(z);
     if (score != nullptr && lane == 0) *score = (float)(r_norm / (kp.eps_abs + kp.eps_rel * fmax(Ax_norm, z_norm)));
     if (r_norm <= kp.eps_abs + kp.eps_rel * fmax(Ax_norm, z_norm)) {
+      SFB_CK_ADD(kCkDualRes, 1)
       double pn = 0.0, qn = 0.0, an = 0.0, rn = 0.0;
       if constexpr (RBX <= 4) {  // (three waves per SIMD: one row at a time, 8 entries in flight)
       for (int j = lane; j < n; j += kWave) {
@@ -1400,10 +1438,15 @@ __device__ inline int sp_check_stopping(const SparsePlanDev &pl, const Item &it,
         }
       }
       const double dual_scale = fmax(fmax(wave_max(pn), wave_max(qn)), wave_max(an)), rn_norm = wave_max(rn);
-      if (rn_norm <= kp.eps_abs + kp.eps_rel * dual_scale) return SFB_QP_OPTIMAL;
+      if (rn_norm <= kp.eps_abs + kp.eps_rel * dual_scale) {
+        SFB_CK_ADD(kCkOptimal, 1)
+        SFB_CK_LAP(kCkCycOpt)
+        return SFB_QP_OPTIMAL;
+      }
       if (score != nullptr && lane == 0) *score = (float)(rn_norm / (kp.eps_abs + kp.eps_rel * dual_scale));
     }
   }
+  SFB_CK_LAP(kCkCycOpt)
   {  // PRIMAL INFEASIBILITY: max(|A'dy|, certificate sum) < thr.  The cheap certificate sum is formed first and
      // A'dy only when the sum leaves the verdict open (same result, NaN included).
     constexpr int UBV     = RBX > 4 ? 6 : 1;  // rows of the short vectors fetched together (round 6; the standard form has no register to spare)
@@ -1454,6 +1497,7 @@ __device__ inline int sp_check_stopping(const SparsePlanDev &pl, const Item &it,
     double acc = 0.0;
     bool brk   = false;
     if (side == 2) {
+    SFB_CK_ADD(kCkOrdered, 1)
     // Certificate sum, sequential over the rows with an early exit to +inf (:607-621).  Equivalent form: the
     // result is +inf iff SOME row has an unbounded side with dy beyond the threshold; otherwise it is the
     // ordered sum of u_i max(0,dy_i) then l_i min(0,dy_i) over the rows, where a skipped term adds +0.0 (exact:
@@ -1487,23 +1531,59 @@ __device__ inline int sp_check_stopping(const SparsePlanDev &pl, const Item &it,
     }
     if (wave_ballot(brk)) acc = inf;
     }
+    SFB_CK_LAP(kCkCycCert)
     if (side == 1 || (side == 2 && !(acc >= thr))) {
+      SFB_CK_ADD(kCkPass2, 1)
       for (int e = lane; e < m; e += kWave) t[e] = w.dyus[e];  // dy into the work vector: the gathers of A'dy stay on chip
       wave_sync();
+      // EARLY EXIT.  |A'dy|_inf is used below for ONE thing: whether mxv < thr.  an is a running fmax of fabs(row) that starts at
+      // +0.0: it never decreases, a NaN row leaves it as it is (fmax returns its other operand), and so does a row beyond n
+      // (|0|).  Once a group of rows holds one with fabs(row) >= thr -- the exact comparison with the exact thr, false for a NaN
+      // row and for a NaN thr -- that lane's an is >= thr, and so are the wave maximum of the an as they stand and the maximum
+      // the full pass would have formed.  With either of them mxv < thr is false in both forms of mxv: side 1, mxv = Aty_norm
+      // >= thr; side 2, where acc >= thr does not hold: Aty_norm < acc needs acc > Aty_norm >= thr, so it is false (also for
+      // a NaN acc) and mxv = Aty_norm again.  The item is not primal infeasible whatever the other rows are; the rest of the
+      // pass is skipped, and the expressions behind the loop, fed with the partial maximum, conclude just that.  While no
+      // row decides every row is formed, as before.  (The wave_sync behind the pass is passed either way: it keeps dy in t
+      // until every lane is done with it.)
       double an = 0.0;
-      if constexpr (RBX <= 4) {
-        for (int j = lane; j < n; j += kWave) an = fmax(an, fabs(sp_row_At(pl, it, j, t)));
-      } else
-      for (int j0 = lane; j0 < n; j0 += kWave * RBX) {
-        double Atdy[RBX];
-        sp_rows_At<RBX, 2>(Atdy, pl, it, j0, t);
-#pragma unroll
-        for (int rr = 0; rr < RBX; ++rr) an = fmax(an, fabs(Atdy[rr]));
+      bool open;  // (wave-uniform) no row >= thr so far
+      {           // the probe: rows 0 .. 63, one per lane, a single chain
+        const double r = fabs(lane < n ? sp_row_At(pl, it, lane, t) : 0.0);
+        an             = fmax(an, r);
+        SFB_CK_ROW(ck_first2, r >= thr, kCkHist2, 0)
+        open = !(kCheckExit && wave_ballot(r >= thr));
       }
+      if constexpr (RBX <= 4) {
+        for (int jb = kWave; open && jb < n; jb += kWave) {
+          const int j    = jb + lane;
+          const double r = fabs(j < n ? sp_row_At(pl, it, j, t) : 0.0);
+          an             = fmax(an, r);
+          SFB_CK_ROW(ck_first2, r >= thr, kCkHist2, jb)
+          open = !(kCheckExit && wave_ballot(r >= thr));
+        }
+      } else
+      for (int jb = kWave; open && jb < n; jb += kWave * RBX) {
+        double Atdy[RBX];
+        sp_rows_At<RBX, 2>(Atdy, pl, it, jb + lane, t);
+        bool hit = false;
+#pragma unroll
+        for (int rr = 0; rr < RBX; ++rr) {
+          an  = fmax(an, fabs(Atdy[rr]));
+          hit = hit || fabs(Atdy[rr]) >= thr;
+          SFB_CK_ROW(ck_first2, fabs(Atdy[rr]) >= thr, kCkHist2, jb + rr * kWave)
+        }
+        open = !(kCheckExit && wave_ballot(hit));
+      }
+      SFB_CK_HIST(kCkHist2, ck_first2)
       const double Aty_norm = wave_max(an);
       wave_sync();
       const double mxv      = (side == 1 || !(Aty_norm < acc)) ? Aty_norm : acc;  // (side 1: acc < thr is known, see above)
-      if (mxv < thr) return SFB_QP_PRIMAL_INFEASIBLE;
+      SFB_CK_LAP(kCkCycPass2)
+      if (mxv < thr) {
+        SFB_CK_ADD(kCkPinf, 1)
+        return SFB_QP_PRIMAL_INFEASIBLE;
+      }
     }
   }
   {  // DUAL INFEASIBILITY: |P dx| <= thr, q'dx <= thr and the row conditions on A dx, each evaluated only while
@@ -1524,15 +1604,39 @@ __device__ inline int sp_check_stopping(const SparsePlanDev &pl, const Item &it,
     const double dx_norm = wave_max(dmx);
     const double thr     = kp.eps_dinf * dx_norm;
     wave_sync();
-    double pn            = 0.0;
-    for (int j0 = lane; j0 < n; j0 += kWave * 8) {
-      double Pdx[8];
-      sp_rows_P<8, 1>(Pdx, pl, it, j0, t);
-#pragma unroll
-      for (int rr = 0; rr < 8; ++rr) pn = fmax(pn, fabs(Pdx[rr]));
+    SFB_CK_LAP(kCkCycTail)
+    SFB_CK_ADD(kCkPass3, 1)
+    // EARLY EXIT, as in the primal test: pn is a running fmax of fabs(row) from +0.0 (monotone; NaN rows and the |0| of rows
+    // beyond n leave it alone) and |P dx|_inf is used for one thing, !(Pdx_n <= thr).  A row with fabs(row) > thr -- false for a
+    // NaN row, false for a NaN thr -- makes its lane's pn > thr, hence the wave maximum as it stands and the full one: Pdx_n <= thr
+    // is false, and so the negated form holds, the test the full pass would have failed in the same way.  The check returns
+    // -1 from the statement behind the loop.  (With a NaN thr no row decides, every row is formed, and !(Pdx_n <= NaN) returns
+    // -1 as before.)  The caller's wave_sync follows, as it does behind the existing return.
+    double pn = 0.0;
+    bool open;  // (wave-uniform) no row > thr so far
+    {           // the probe: rows 0 .. 63, one per lane
+      const double r = fabs(lane < n ? sp_row_P(pl, it, lane, t) : 0.0);
+      pn             = fmax(pn, r);
+      SFB_CK_ROW(ck_first3, r > thr, kCkHist3, 0)
+      open = !(kCheckExit && wave_ballot(r > thr));
     }
+    for (int jb = kWave; open && jb < n; jb += kWave * 8) {
+      double Pdx[8];
+      sp_rows_P<8, 1>(Pdx, pl, it, jb + lane, t);
+      bool hit = false;
+#pragma unroll
+      for (int rr = 0; rr < 8; ++rr) {
+        pn  = fmax(pn, fabs(Pdx[rr]));
+        hit = hit || fabs(Pdx[rr]) > thr;
+        SFB_CK_ROW(ck_first3, fabs(Pdx[rr]) > thr, kCkHist3, jb + rr * kWave)
+      }
+      open = !(kCheckExit && wave_ballot(hit));
+    }
+    SFB_CK_HIST(kCkHist3, ck_first3)
     const double Pdx_n = wave_max(pn);
+    SFB_CK_LAP(kCkCycPass3)
     if (!(Pdx_n <= thr)) return -1;
+    SFB_CK_ADD(kCkQdx, 1)
     wave_sync();  // (every lane is done with dx in t: the chain below stages its operands there)
     double qdx = 0.0;  // q' dx, sequential fma chain (:633) fed from LDS
     for (int c0 = 0; c0 < n; c0 += chunk) {
@@ -1556,7 +1660,11 @@ __device__ inline int sp_check_stopping(const SparsePlanDev &pl, const Item &it,
       }
       wave_sync();
     }
-    if (!(qdx <= thr)) return -1;
+    if (!(qdx <= thr)) {
+      SFB_CK_LAP(kCkCycTail)
+      return -1;
+    }
+    SFB_CK_ADD(kCkRows, 1)
     bool rowok = true;
     for (int i = lane; i < m; i += kWave) {
       const double Adx = sp_row_A(pl, it, i, w.dxus), ui = it.u[i], li = it.l[i];
@@ -1564,7 +1672,11 @@ __device__ inline int sp_check_stopping(const SparsePlanDev &pl, const Item &it,
       else if (li == -inf) rowok = rowok && (Adx <= thr);
       else rowok = rowok && (fabs(Adx) < thr);
     }
-    if (!wave_ballot(!rowok)) return SFB_QP_DUAL_INFEASIBLE;
+    SFB_CK_LAP(kCkCycTail)
+    if (!wave_ballot(!rowok)) {
+      SFB_CK_ADD(kCkDinf, 1)
+      return SFB_QP_DUAL_INFEASIBLE;
+    }
   }
   return -1;
 }
@@ -2777,7 +2889,7 @@ constexpr int kDqStarted = 88;  // != 0: the loop launch's waves are on the chip
 
 // POLISHER: the instance the polishers run (dq_mode 2); the standard instance has no register to spare for their loop.
 template<bool LAT, bool TRACE = false, bool POLISHER = false>
-__global__ void __launch_bounds__(64, LAT ? 1 : ((TRACE || POLISHER) ? 2 : 3)) qp_sparse_kernel(const SparsePlanDev *__restrict__ plp, const DenseKernelParams kp,
+__global__ void __launch_bounds__(64, LAT ? 1 : ((TRACE || POLISHER) ? 2 : kStdWavesPerSimd)) qp_sparse_kernel(const SparsePlanDev *__restrict__ plp, const DenseKernelParams kp,
                                                        const double *__restrict__ gPx, const double *__restrict__ gq,
                                                        const double *__restrict__ gAx, const double *__restrict__ gl,
                                                        const double *__restrict__ gu, const double *__restrict__ gwx,
@@ -3487,3 +3599,15 @@ hipError_t qp_sparse_launch(const SparsePlanDev &pl, const DenseKernelParams &kp
 }
 
 }  // namespace sfb
+
+#ifdef SFB_PROF_CHECK
+// the counters of the profiling build (sp_check_stopping): out[2][48], form by form, optionally reset
+extern "C" int sfb_debug_check_prof(unsigned long long *out, int reset)
+{
+  static const unsigned long long zero[2][sfb::kCkSlots] = {};
+  if (hipDeviceSynchronize() != hipSuccess) return 1;
+  if (out != nullptr && hipMemcpyFromSymbol(out, HIP_SYMBOL(sfb::sfb_check_prof), sizeof(zero)) != hipSuccess) return 1;
+  if (reset && hipMemcpyToSymbol(HIP_SYMBOL(sfb::sfb_check_prof), zero, sizeof(zero)) != hipSuccess) return 1;
+  return 0;
+}
+#endif
