@@ -2,8 +2,8 @@
 // to a high-precision reference (tests/golden/lie_reference.npz): the same item function runs on the host
 // (sfbx_lie_eval, models.cpp) and as one GPU thread per item (sfbx_lie_eval_device, models_device.hip).
 //
-// Elements as doubles: R3 (v0, v1, v2); SE2 (x, y, cos, sin); SO3 (w, x, y, z); a Bundle is its parts one after the other
-// (X6 = 7 doubles, X12 = 14).  Tangents in the order of lie.hpp; matrices column-major.
+// Elements as doubles: R3 (v0, v1, v2); SE2 (x, y, cos, sin); SO3 (w, x, y, z); SE3 (px, py, pz, w, x, y, z); a Bundle is its
+// parts one after the other (X6 = 7 doubles, X12 = 14, X12B = Bundle<SE3, Rn<6>> = 13).  Tangents in the order of lie.hpp; matrices column-major.
 #pragma once
 #include <cstdint>
 #include <utility>
@@ -13,7 +13,7 @@
 namespace sfbx {
 using namespace smooth_feedback_amd;
 
-enum LieGroupId { LIE_R3 = 0, LIE_SE2 = 1, LIE_SO3 = 2, LIE_X6 = 3, LIE_X12 = 4 };
+enum LieGroupId { LIE_R3 = 0, LIE_SE2 = 1, LIE_SO3 = 2, LIE_X6 = 3, LIE_X12 = 4, LIE_SE3 = 5, LIE_X12B = 6 };
 // in -> out per item (E doubles per element, T per tangent):
 enum LieOp {
   LIE_EXP          = 0,  // tangent -> element                         (SE2, SO3)
@@ -53,6 +53,15 @@ struct LieIO<SO3> {
   static constexpr int E = 4;
   SFB_LIE_HD static SO3 load(const double * p) { return SO3{p[0], p[1], p[2], p[3]}; }
   SFB_LIE_HD static void store(const SO3 & g, double * p) { p[0] = g.w; p[1] = g.x; p[2] = g.y; p[3] = g.z; }
+};
+template<>
+struct LieIO<SE3> {
+  static constexpr int E = 7;
+  SFB_LIE_HD static SE3 load(const double * p) { return SE3{{p[0], p[1], p[2]}, SO3{p[3], p[4], p[5], p[6]}}; }
+  SFB_LIE_HD static void store(const SE3 & g, double * p)
+  {
+    p[0] = g.p[0]; p[1] = g.p[1]; p[2] = g.p[2]; p[3] = g.q.w; p[4] = g.q.x; p[5] = g.q.y; p[6] = g.q.z;
+  }
 };
 template<class... Gs>
 struct LieIO<Bundle<Gs...>> {
@@ -150,6 +159,8 @@ inline bool lie_dispatch_group(int group, Fn && fn)
   case LIE_SO3: fn.template operator()<SO3>(); return true;
   case LIE_X6: fn.template operator()<Bundle<SE2, Rn<3>>>(); return true;
   case LIE_X12: fn.template operator()<Bundle<SE2, Rn<3>, SE2, Rn<3>>>(); return true;
+  case LIE_SE3: fn.template operator()<SE3>(); return true;
+  case LIE_X12B: fn.template operator()<Bundle<SE3, Rn<6>>>(); return true;
   default: return false;
   }
 }

@@ -16,6 +16,7 @@
 #include <smooth/feedback/mpc.hpp>  // the reference's include path and namespace (sfbx_test_mpc_api)
 
 #include "lie_eval.h"
+#include "rigid_body_model.h"
 #include "vehicle_model.h"
 
 using namespace smooth_feedback_amd;
@@ -38,9 +39,16 @@ X6 xdes6(double t) { return sfbx::VehicleModel6{}.xdes(t); }
 X12 xdes12(double t) { return sfbx::VehicleModel12{}.xdes(t); }
 MPC6 make6(int K, double tf) { return sfbx::make_vehicle_mpc<MPC6, sfbx::VehicleModel6>(K, tf); }
 MPC12 make12(int K, double tf) { return sfbx::make_vehicle_mpc<MPC12, sfbx::VehicleModel12>(K, tf); }
+// ---- the rigid body on SE3 x R^6 (rigid_body_model.h), variant 13 ----
+using sfbx::MPC12B;
+using sfbx::U6;
+using sfbx::X12B;
+X12B xdes12b(double t) { return sfbx::RigidBodyModel{}.xdes(t); }
+MPC12B make12b(int K, double tf) { return sfbx::make_rigid_body_mpc(K, tf); }
 
 Vec<6> mpc_dyn(MPC6 &, const X6 & x, const U2 & u) { return VehicleDyn6{}(x, u); }
 Vec<12> mpc_dyn(MPC12 &, const X12 & x, const U2 & u) { return VehicleDyn12{}(x, u); }
+Vec<12> mpc_dyn(MPC12B &, const X12B & x, const U6 & u) { return sfbx::RigidBodyDyn{}(x, u); }
 
 template<class X>
 X perturbed(const X & x0, uint64_t seed)
@@ -85,7 +93,7 @@ std::vector<double> g_tick_seconds;  // wall time of every swarm.step() of the l
 
 bool g_swarm_multi_device = false;  // sfbx_mpc_swarm_step_multi: shard the swarm's solves over the device list
 
-template<class M, class XF, class X, class Swarm = MPCSwarm<M>>
+template<class M, class XF, class X, class Swarm = MPCSwarm<M>, class U = U2>
 int swarm_step(M & mpc, XF xdes, int64_t batch, uint64_t seed, int ticks, double * u0, int32_t * codes, uint32_t * iters)
 {
   Swarm swarm(mpc, batch);
@@ -96,7 +104,7 @@ int swarm_step(M & mpc, XF xdes, int64_t batch, uint64_t seed, int ticks, double
     t[b]  = 0.025 * double(b % 400);
     xs[b] = perturbed(xdes(t[b]), seed + (uint64_t)b);
   }
-  std::vector<U2> us;
+  std::vector<U> us;
   std::vector<QPSolutionStatus> cs;
   g_tick_seconds.assign(ticks, 0.0);
   for (int k = 0; k < ticks; ++k) {
@@ -112,7 +120,7 @@ int swarm_step(M & mpc, XF xdes, int64_t batch, uint64_t seed, int ticks, double
     }
   }
   for (int64_t b = 0; b < batch; ++b) {
-    u0[2 * b] = us[b].v[0]; u0[2 * b + 1] = us[b].v[1];
+    for (int i = 0; i < U::Dof; ++i) u0[U::Dof * b + i] = us[b].v[i];
     codes[b] = (int32_t)cs[b];
     iters[b] = swarm.iterations()[b];
   }
@@ -143,10 +151,11 @@ int sfbx_mpc_dims(int variant, int K, int * n, int * m, int * nnzP, int * nnzA, 
 {
   auto fill = [&](const auto & mpc, int nx) {
     *n = mpc.qp().n; *m = mpc.qp().m; *nnzP = (int)mpc.qp().P_val.size(); *nnzA = (int)mpc.qp().A_val.size();
-    *Nx = nx; *Nu = 2; *N = mpc.N();
+    *Nx = nx; *Nu = std::decay_t<decltype(mpc)>::Nu; *N = mpc.N();
   };
   if (variant == 6) { auto mpc = make6(K, 5.0); fill(mpc, 6); return 0; }
   if (variant == 12) { auto mpc = make12(K, 5.0); fill(mpc, 12); return 0; }
+  if (variant == 13) { auto mpc = make12b(K, 5.0); fill(mpc, 12); return 0; }
   return -1;
 }
 
@@ -154,6 +163,7 @@ int sfbx_mpc_pattern(int variant, int K, double tf, int32_t * Pp, int32_t * Pi, 
 {
   if (variant == 6) { auto mpc = make6(K, tf); return fill_pattern(mpc, Pp, Pi, Pval, Ap, Aj); }
   if (variant == 12) { auto mpc = make12(K, tf); return fill_pattern(mpc, Pp, Pi, Pval, Ap, Aj); }
+  if (variant == 13) { auto mpc = make12b(K, tf); return fill_pattern(mpc, Pp, Pi, Pval, Ap, Aj); }
   return -1;
 }
 
@@ -167,6 +177,7 @@ int sfbx_mpc_stage(int variant, int K, int32_t * stage)
   };
   if (variant == 6) { auto mpc = make6(K, 5.0); return fill(mpc); }
   if (variant == 12) { auto mpc = make12(K, 5.0); return fill(mpc); }
+  if (variant == 13) { auto mpc = make12b(K, 5.0); return fill(mpc); }
   return -1;
 }
 
@@ -175,6 +186,7 @@ int sfbx_mpc_assemble_batch(int variant, int K, double tf, int64_t batch, uint64
 {
   if (variant == 6) { auto mpc = make6(K, tf); return assemble_batch(mpc, xdes6, batch, seed, Aval, l, u, threads); }
   if (variant == 12) { auto mpc = make12(K, tf); return assemble_batch(mpc, xdes12, batch, seed, Aval, l, u, threads); }
+  if (variant == 13) { auto mpc = make12b(K, tf); return assemble_batch(mpc, xdes12b, batch, seed, Aval, l, u, threads); }
   return -1;
 }
 
@@ -194,6 +206,7 @@ int sfbx_mpc_layout(int variant, int K, double tf, int32_t * dims, double * alph
   };
   if (variant == 6) { auto mpc = make6(K, tf); return fill(mpc); }
   if (variant == 12) { auto mpc = make12(K, tf); return fill(mpc); }
+  if (variant == 13) { auto mpc = make12b(K, tf); return fill(mpc); }
   return -1;
 }
 
@@ -201,6 +214,7 @@ int sfbx_mpc_records(int variant, int K, double tf, int64_t batch, uint64_t seed
 {
   if (variant == 6) { auto mpc = make6(K, tf); return records_batch(mpc, xdes6, batch, seed, rec, threads); }
   if (variant == 12) { auto mpc = make12(K, tf); return records_batch(mpc, xdes12, batch, seed, rec, threads); }
+  if (variant == 13) { auto mpc = make12b(K, tf); return records_batch(mpc, xdes12b, batch, seed, rec, threads); }
   return -1;
 }
 
@@ -216,6 +230,7 @@ int sfbx_mpc_swarm_device_step(int variant, int K, double tf, int64_t batch, uin
   try {
     if (variant == 6) { auto mpc = make6(K, tf); return swarm_step<MPC6, decltype(&xdes6), X6, MPCSwarmDevice<MPC6>>(mpc, xdes6, batch, seed, ticks, u0, codes, iters); }
     if (variant == 12) { auto mpc = make12(K, tf); return swarm_step<MPC12, decltype(&xdes12), X12, MPCSwarmDevice<MPC12>>(mpc, xdes12, batch, seed, ticks, u0, codes, iters); }
+    if (variant == 13) { auto mpc = make12b(K, tf); return swarm_step<MPC12B, decltype(&xdes12b), X12B, MPCSwarmDevice<MPC12B>, U6>(mpc, xdes12b, batch, seed, ticks, u0, codes, iters); }
   } catch (const std::exception &) {
     return -2;
   }
@@ -228,6 +243,7 @@ int sfbx_mpc_swarm_step(int variant, int K, double tf, int64_t batch, uint64_t s
   try {
     if (variant == 6) { auto mpc = make6(K, tf); return swarm_step<MPC6, decltype(&xdes6), X6>(mpc, xdes6, batch, seed, ticks, u0, codes, iters); }
     if (variant == 12) { auto mpc = make12(K, tf); return swarm_step<MPC12, decltype(&xdes12), X12>(mpc, xdes12, batch, seed, ticks, u0, codes, iters); }
+    if (variant == 13) { auto mpc = make12b(K, tf); return swarm_step<MPC12B, decltype(&xdes12b), X12B, MPCSwarm<MPC12B>, U6>(mpc, xdes12b, batch, seed, ticks, u0, codes, iters); }
   } catch (const std::exception &) {
     return -2;
   }
@@ -1077,6 +1093,64 @@ int sfbx_ekf_swarm_host(int64_t batch, int steps, int rk4, double tau, double dt
     return 0;
   } catch (const std::exception &) {
     return -2;
+  }
+}
+
+/* the pose filter of rigid_body_model.h (G = SE3, position measured), one host EKF<SE3> object per filter: the host twin of
+ * sfbx_pose_ekf_swarm_device (models_device.hip).  states [batch][7] = (px, py, pz, w, x, y, z), P0 [batch][36], y [steps][batch][3] */
+int sfbx_pose_ekf_swarm_host(int64_t batch, int steps, int rk4, double tau, double dt, const double * states, const double * P0,
+                             const double * y, double * states_out, double * P_out)
+{
+  try {
+    const auto Q = sfbx::pose_ekf_Q();
+    const auto R = sfbx::pose_ekf_R();
+    auto run = [&](auto & ekf, int64_t b) {
+      Mat<6, 6> P;
+      std::copy(P0 + 36 * b, P0 + 36 * (b + 1), P.a.begin());
+      ekf.reset(sfbx::pose_state(states + 7 * b), P);
+      for (int k = 0; k < steps; ++k) {
+        ekf.predict(sfbx::PoseEkfDyn{}, Q, tau, dt > 0 ? std::optional<double>(dt) : std::nullopt);
+        const double * yk = y + ((size_t)k * batch + b) * 3;
+        ekf.template update<3>(sfbx::PoseEkfMeas{}, Vec<3>{yk[0], yk[1], yk[2]}, R);
+      }
+      sfbx::pose_state_out(ekf.estimate(), states_out + 7 * b);
+      const auto Pn = ekf.covariance();
+      std::copy(Pn.a.begin(), Pn.a.end(), P_out + 36 * b);
+    };
+    for (int64_t b = 0; b < batch; ++b) {
+      if (rk4) { EKF<SE3, EKFStepper::RK4> e; run(e, b); }
+      else { EKF<SE3> e; run(e, b); }
+    }
+    return 0;
+  } catch (const std::exception &) {
+    return -2;
+  }
+}
+
+/* an ASI filter on the rigid body (ASIFilter<Bundle<SE3,R6>, R6>; rigid_body_model.h: stay above z = 0.2, backup = damp the
+ * twist) for agent b of the filter tests.  Out: the filtered input u [6], the solver's code and the smallest slack of the QP's
+ * rows at the solution.  Needs a GPU. */
+int sfbx_test_asif_rigid_body(int64_t b, double * u_out, int32_t * code, double * slack)
+{
+  try {
+    sfbx::RigidBodyDyn f;
+    ASIFilter<X12B, U6, sfbx::RigidBodyDyn> asif(f, sfbx::rigid_body_asif_params(20));
+    const auto [ua, c] = asif(sfbx::rigid_body_asif_state(b), sfbx::rigid_body_asif_udes(), sfbx::RigidBodyH{}, sfbx::RigidBodyBU{});
+    for (int i = 0; i < 6; ++i) u_out[i] = ua.v[i];
+    *code = (int32_t)c;
+    const auto & qp = asif.qp();
+    const auto & sol = asif.last_solution();
+    double s = 1e300;
+    for (int r = 0; r < qp.m; ++r) {
+      double ax = 0.0;
+      for (int j = 0; j < qp.n; ++j) ax += qp.A[(size_t)r + (size_t)j * qp.m] * sol.primal[j];
+      s = std::min({s, ax - qp.l[r], qp.u[r] - ax});
+    }
+    *slack = s;
+    return 0;
+  } catch (const std::exception & e) {
+    std::fprintf(stderr, "sfbx_test_asif_rigid_body: %s\n", e.what());
+    return 1;
   }
 }
 

@@ -10,7 +10,8 @@ extern "C" {
 
 /* variant 6 : X = Bundle<SE2,R3>, U = R2   -- the vehicle of examples/mpc_asif_vehicle.cpp:42-79
  * variant 12: X = Bundle<SE2,R3,SE2,R3>, U = R2 -- two such vehicles driven by one input pair
- *             (synthetic: matches BASELINE.json's "nx=12, nu=2" problem size n = m = 740 at K = 50) */
+ *             (synthetic: matches BASELINE.json's "nx=12, nu=2" problem size n = m = 740 at K = 50)
+ * variant 13: X = Bundle<SE3,R6>, U = R6  -- a 3-D rigid body, pose and body twist (rigid_body_model.h); u0 is [batch][6] */
 int sfbx_mpc_dims(int variant, int K, int *n, int *m, int *nnzP, int *nnzA, int *Nx, int *Nu, int *N);
 /* pattern (+ P values, identical for all agents).  Arrays sized by sfbx_mpc_dims. */
 int sfbx_mpc_pattern(int variant, int K, double tf, int32_t *Pp, int32_t *Pi, double *Pval, int32_t *Ap, int32_t *Aj);
@@ -124,6 +125,11 @@ int sfbx_lie_eval(int group, int op, int64_t count, const double *in, double *ou
  * sfbx_ekf_swarm_device (models_device.hip) */
 int sfbx_ekf_swarm_host(int64_t batch, int steps, int rk4, double tau, double dt, const double *states, const double *P0,
                         const double *y, double *states_out, double *P_out);
+/* the pose filter on SE3 of rigid_body_model.h, one host EKF<SE3> object per filter; states [batch][7] = (px, py, pz, w, x, y, z) */
+int sfbx_pose_ekf_swarm_host(int64_t batch, int steps, int rk4, double tau, double dt, const double *states, const double *P0,
+                             const double *y, double *states_out, double *P_out);
+/* ASIFilter<Bundle<SE3,R6>, R6> on the rigid body, agent b of the filter tests: filtered input u [6], solver code, smallest constraint slack at the solution */
+int sfbx_test_asif_rigid_body(int64_t b, double *u_out, int32_t *code, double *slack);
 /* mesh: nodes (N+1), weights (N+1), Dus ((K+1)*K col-major) for `n` intervals of K points */
 int sfbx_mesh(int n_ivals, int K, double *nodes, double *weights, double *Dus);
 

@@ -14,6 +14,7 @@
 #include <smooth_feedback_amd/multi_device.hpp>
 
 #include "lie_eval.h"
+#include "rigid_body_model.h"
 #include "vehicle_model.h"
 
 using namespace smooth_feedback_amd;
@@ -32,19 +33,28 @@ X perturbed(const X & x0, uint64_t seed)
   return rplus(x0, xi);
 }
 
+// the host MPC object of a model: the vehicles, or the rigid body on SE3 x R^6 (rigid_body_model.h, variant 13)
+template<class MPCT, class Model>
+MPCT make_mpc(int K, double tf)
+{
+  if constexpr (std::is_same_v<Model, sfbx::RigidBodyModel>) return sfbx::make_rigid_body_mpc(K, tf);
+  else return sfbx::make_vehicle_mpc<MPCT, Model>(K, tf);
+}
+
 // `ticks` closed-loop ticks of the swarm of sfbx_mpc_swarm_step through any swarm type with MPCSwarmDeviceLin's step()
 template<class Model, class Swarm>
 void devlin_loop(Swarm & swarm, const Model & mdl, int64_t batch, uint64_t seed, int ticks, double * u0, int32_t * codes, uint32_t * iters,
                  double * seconds)
 {
   using X = decltype(std::declval<const Model &>().xdes(0.0));
+  using U = decltype(std::declval<const Model &>().udes(0.0));
   std::vector<double> t((size_t)batch);
   std::vector<X> xs((size_t)batch);
   for (int64_t b = 0; b < batch; ++b) {
     t[b]  = 0.025 * double(b % 400);
     xs[b] = perturbed(mdl.xdes(t[b]), seed + (uint64_t)b);
   }
-  std::vector<sfbx::U2> us;
+  std::vector<U> us;
   std::vector<QPSolutionStatus> cs;
   for (int k = 0; k < ticks; ++k) {
     if (k > 0)
@@ -59,7 +69,7 @@ void devlin_loop(Swarm & swarm, const Model & mdl, int64_t batch, uint64_t seed,
     if (seconds) seconds[k] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   }
   for (int64_t b = 0; b < batch; ++b) {
-    u0[2 * b] = us[b].v[0]; u0[2 * b + 1] = us[b].v[1];
+    for (int i = 0; i < U::Dof; ++i) u0[U::Dof * b + i] = us[b].v[i];
     codes[b] = (int32_t)cs[b];
     iters[b] = swarm.iterations()[b];
   }
@@ -70,7 +80,7 @@ int devlin_step(int K, double tf, int64_t batch, uint64_t seed, int ticks, int p
                 double * records, int64_t * record_doubles, int32_t * packed, double * seconds)
 {
   const Model mdl{};
-  auto mpc = sfbx::make_vehicle_mpc<MPCT, Model>(K, tf);
+  auto mpc = make_mpc<MPCT, Model>(K, tf);
   MPCSwarmDeviceLin<MPCT, Model> swarm(mpc, mdl, batch, 0.0, probe_empty != 0);
   devlin_loop(swarm, mdl, batch, seed, ticks, u0, codes, iters, seconds);
   if (record_doubles) *record_doubles = swarm.record_doubles();
@@ -84,7 +94,7 @@ int devlin_step_multi(int K, double tf, int64_t batch, uint64_t seed, int ticks,
                       int32_t * codes, uint32_t * iters, double * seconds)
 {
   const Model mdl{};
-  auto mpc = sfbx::make_vehicle_mpc<MPCT, Model>(K, tf);
+  auto mpc = make_mpc<MPCT, Model>(K, tf);
   MPCSwarmMultiDeviceLin<MPCT, Model> swarm(mpc, mdl, batch, std::vector<int>(devices, devices + ndev));
   swarm.shards().thread_per_shard(thread_per_shard != 0);
   devlin_loop(swarm, mdl, batch, seed, ticks, u0, codes, iters, seconds);
@@ -177,6 +187,52 @@ int ekf_swarm(int64_t batch, int steps, int fused, double tau, double dt, const 
   return 0;
 }
 
+// the pose filter of rigid_body_model.h (G = SE3) through EKFSwarmDevice: the rounds of ekf_swarm, fused as there
+template<EKFStepper Stp>
+int pose_ekf_swarm(int64_t batch, int steps, int fused, double tau, double dt, const double * states, const double * P0, const double * y,
+                   double * states_out, double * P_out, int32_t * info)
+{
+  EKFSwarmDevice<SE3, sfbx::PoseEkfDyn, sfbx::PoseEkfMeas, 3, Stp> swarm(sfbx::PoseEkfDyn{}, sfbx::PoseEkfMeas{}, batch);
+  std::vector<SE3> g((size_t)batch);
+  std::vector<Mat<6, 6>> P((size_t)batch);
+  for (int64_t b = 0; b < batch; ++b) {
+    g[b] = sfbx::pose_state(states + 7 * b);
+    std::copy(P0 + 36 * b, P0 + 36 * (b + 1), P[b].a.begin());
+  }
+  swarm.reset(g, P);
+  swarm.one_launch(fused != 2);
+  double * dy = nullptr;
+  if (fused == 3) {
+    if (hipMalloc(reinterpret_cast<void **>(&dy), (size_t)steps * batch * 24) != hipSuccess) return -3;
+    (void)hipMemcpy(dy, y, (size_t)steps * batch * 24, hipMemcpyHostToDevice);
+  }
+  const auto Q = sfbx::pose_ekf_Q();
+  const auto R = sfbx::pose_ekf_R();
+  std::vector<Vec<3>> ys((size_t)batch);
+  for (int k = 0; k < steps; ++k) {
+    for (int64_t b = 0; b < batch; ++b) ys[b] = {y[((size_t)k * batch + b) * 3], y[((size_t)k * batch + b) * 3 + 1], y[((size_t)k * batch + b) * 3 + 2]};
+    if (fused == 3) {
+      (void)hipMemcpy(swarm.device_measurements(), dy + (size_t)k * batch * 3, (size_t)batch * 24, hipMemcpyDeviceToDevice);
+      swarm.step_resident(Q, tau, R);
+    } else if (fused) {
+      swarm.step(Q, tau, ys, R);
+    } else {
+      swarm.predict(Q, tau, dt > 0 ? std::optional<double>(dt) : std::nullopt);
+      swarm.update(ys, R);
+    }
+  }
+  if (dy) (void)hipFree(dy);
+  g = swarm.estimates();
+  P = swarm.covariances();
+  const auto inf = swarm.update_info();
+  for (int64_t b = 0; b < batch; ++b) {
+    sfbx::pose_state_out(g[b], states_out + 7 * b);
+    std::copy(P[b].a.begin(), P[b].a.end(), P_out + 36 * b);
+    info[b] = inf[b];
+  }
+  return 0;
+}
+
 // one thread per item through sfbx::lie_eval_item, the function sfbx_lie_eval (models.cpp) runs on the host
 template<class G>
 __global__ void __launch_bounds__(64) lie_eval_kernel(const int op, const int64_t count, const int win, const int wout, const double * __restrict__ in,
@@ -206,6 +262,20 @@ int sfbx_ekf_swarm_device(int64_t batch, int steps, int rk4, int fused, double t
   }
 }
 
+/* sfbx_ekf_swarm_device for the pose filter on SE3 (rigid_body_model.h: PoseEkfDyn / PoseEkfMeas): states [batch][7] =
+ * (px, py, pz, w, x, y, z), P0 [batch][36], y [steps][batch][3].  sfbx_pose_ekf_swarm_host (models.cpp) is its host twin. */
+int sfbx_pose_ekf_swarm_device(int64_t batch, int steps, int rk4, int fused, double tau, double dt, const double * states, const double * P0,
+                               const double * y, double * states_out, double * P_out, int32_t * info)
+{
+  try {
+    return rk4 ? pose_ekf_swarm<EKFStepper::RK4>(batch, steps, fused, tau, dt, states, P0, y, states_out, P_out, info)
+               : pose_ekf_swarm<EKFStepper::Euler>(batch, steps, fused, tau, dt, states, P0, y, states_out, P_out, info);
+  } catch (const std::exception & e) {
+    std::fprintf(stderr, "sfbx_pose_ekf_swarm_device: %s\n", e.what());
+    return -2;
+  }
+}
+
 /* sfbx_ekf_swarm_device through EKFSwarmMultiDevice (multi_device.hpp): the filters sharded over `devices` (an ordinal may repeat),
  * one resident swarm per shard.  thread_per_shard != 0: a host thread per shard even on one device (test hook). */
 int sfbx_ekf_swarm_device_multi(int64_t batch, int steps, int rk4, int fused, double tau, double dt, const int * devices, int ndev,
@@ -231,6 +301,8 @@ int sfbx_mpc_swarm_devlin_step_multi(int variant, int K, double tf, int64_t batc
       return devlin_step_multi<sfbx::MPC6, sfbx::VehicleModel6>(K, tf, batch, seed, ticks, devices, ndev, thread_per_shard, u0, codes, iters, seconds);
     if (variant == 12)
       return devlin_step_multi<sfbx::MPC12, sfbx::VehicleModel12>(K, tf, batch, seed, ticks, devices, ndev, thread_per_shard, u0, codes, iters, seconds);
+    if (variant == 13)
+      return devlin_step_multi<sfbx::MPC12B, sfbx::RigidBodyModel>(K, tf, batch, seed, ticks, devices, ndev, thread_per_shard, u0, codes, iters, seconds);
   } catch (const std::exception & e) {
     std::fprintf(stderr, "sfbx_mpc_swarm_devlin_step_multi: %s\n", e.what());
     return -2;
@@ -323,6 +395,9 @@ int sfbx_mpc_swarm_devlin_step(int variant, int K, double tf, int64_t batch, uin
     if (variant == 12)
       return devlin_step<sfbx::MPC12, sfbx::VehicleModel12>(K, tf, batch, seed, ticks, probe_empty, u0, codes, iters, records,
                                                             record_doubles, packed, seconds);
+    if (variant == 13)
+      return devlin_step<sfbx::MPC12B, sfbx::RigidBodyModel>(K, tf, batch, seed, ticks, probe_empty, u0, codes, iters, records,
+                                                             record_doubles, packed, seconds);
   } catch (const std::exception & e) {
     std::fprintf(stderr, "sfbx_mpc_swarm_devlin_step: %s\n", e.what());
     return -2;
@@ -387,6 +462,27 @@ int sfbx_asif_swarm_device_step_tall(int64_t batch, int K, int ticks, const doub
                                      double * x, double * y, double * wx, double * wy, double * seconds)
 {
   return asif_swarm_device_step_impl(batch, K, ticks, states, udes, u_out, codes, iters, P, q, A, l, u, x, y, wx, wy, seconds, true);
+}
+
+/* ASIFSwarmDevice on the rigid body (rigid_body_model.h): the agents of sfbx_test_asif_rigid_body (models.cpp), one filter call.
+ * Out: u [batch][6], codes. */
+int sfbx_asif_rigid_body_swarm_device(int64_t batch, double * u_out, int32_t * codes)
+{
+  try {
+    ASIFSwarmDevice<sfbx::X12B, sfbx::U6, sfbx::RigidBodyDyn, sfbx::RigidBodyH, sfbx::RigidBodyBU> swarm(
+      sfbx::RigidBodyDyn{}, sfbx::RigidBodyH{}, sfbx::RigidBodyBU{}, (size_t)batch, sfbx::rigid_body_asif_params(20));
+    std::vector<sfbx::X12B> g((size_t)batch);
+    std::vector<sfbx::U6> ud((size_t)batch, sfbx::rigid_body_asif_udes());
+    for (int64_t b = 0; b < batch; ++b) g[b] = sfbx::rigid_body_asif_state(b);
+    const auto out = swarm(g, ud);
+    for (int64_t b = 0; b < batch; ++b)
+      for (int i = 0; i < 6; ++i) u_out[6 * b + i] = out[b].v[i];
+    std::copy(swarm.codes().begin(), swarm.codes().end(), codes);
+    return 0;
+  } catch (const std::exception & e) {
+    std::fprintf(stderr, "sfbx_asif_rigid_body_swarm_device: %s\n", e.what());
+    return 1;
+  }
 }
 
 /* sfbx_lie_eval (models.h) on the GPU: in [count][win] is copied to a plain device buffer, one thread per item runs the

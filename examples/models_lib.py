@@ -119,7 +119,7 @@ def mpc_records(variant, K, batch, seed=0, tf=5.0, threads=8):
 
 def mpc_swarm_step(variant, K, batch, ticks, seed=1, tf=5.0, device=False):
     """`ticks` closed-loop ticks through MPCSwarm (host assembly) or MPCSwarmDevice; outputs of the last tick."""
-    u0 = np.zeros((batch, 2)); codes = np.zeros(batch, np.int32); iters = np.zeros(batch, np.uint32)
+    u0 = np.zeros((batch, mpc_dims(variant, K)["Nu"])); codes = np.zeros(batch, np.int32); iters = np.zeros(batch, np.uint32)
     fn = lib().sfbx_mpc_swarm_device_step if device else lib().sfbx_mpc_swarm_step
     rc = fn(variant, K, C.c_double(tf), C.c_int64(batch), C.c_uint64(seed), ticks, _p(u0), _p(codes), _p(iters))
     assert rc == 0, rc
@@ -129,7 +129,7 @@ def mpc_swarm_step(variant, K, batch, ticks, seed=1, tf=5.0, device=False):
 def mpc_swarm_step_multi(variant, K, batch, ticks, devices, seed=1, tf=5.0):
     """mpc_swarm_step with every batched solve sharded over `devices` from this one process (MPCSwarm +
     QPSolver::shard_over_devices + sfb_set_devices)."""
-    u0 = np.zeros((batch, 2)); codes = np.zeros(batch, np.int32); iters = np.zeros(batch, np.uint32)
+    u0 = np.zeros((batch, mpc_dims(variant, K)["Nu"])); codes = np.zeros(batch, np.int32); iters = np.zeros(batch, np.uint32)
     dev = (C.c_int * len(devices))(*devices)
     rc = lib().sfbx_mpc_swarm_step_multi(variant, K, C.c_double(tf), C.c_int64(batch), C.c_uint64(seed), ticks, dev, len(devices),
                                          _p(u0), _p(codes), _p(iters))
@@ -203,7 +203,7 @@ def mpc_swarm_devlin_step(variant, K, batch, ticks, seed=1, tf=5.0, probe_empty=
     dims = mpc_dims(variant, K)
     Nx, Nu, N = dims["Nx"], dims["Nu"], dims["N"]
     full = N * (2 * Nx + Nx * Nx + Nx * Nu + 2 + 2 * Nx + 2 * Nu) + Nx + Nx * Nx
-    out = dict(u0=np.zeros((batch, 2)), code=np.zeros(batch, np.int32), iter=np.zeros(batch, np.uint32), seconds=np.zeros(ticks))
+    out = dict(u0=np.zeros((batch, Nu)), code=np.zeros(batch, np.int32), iter=np.zeros(batch, np.uint32), seconds=np.zeros(ticks))
     rec = np.zeros((batch, full)) if want_records else None
     rd = C.c_int64(0); packed = C.c_int32(0)
     rc = dev_lib().sfbx_mpc_swarm_devlin_step(variant, K, C.c_double(tf), C.c_int64(batch), C.c_uint64(seed), ticks, int(probe_empty),
@@ -220,7 +220,8 @@ def mpc_swarm_devlin_step(variant, K, batch, ticks, seed=1, tf=5.0, probe_empty=
 def mpc_swarm_devlin_step_multi(variant, K, batch, ticks, devices, seed=1, tf=5.0, thread_per_shard=False):
     """MPCSwarmMultiDeviceLin (multi_device.hpp): mpc_swarm_devlin_step with the agents sharded over `devices` from this one
     process, one resident swarm per shard."""
-    out = dict(u0=np.zeros((batch, 2)), code=np.zeros(batch, np.int32), iter=np.zeros(batch, np.uint32), seconds=np.zeros(ticks))
+    out = dict(u0=np.zeros((batch, mpc_dims(variant, K)["Nu"])), code=np.zeros(batch, np.int32), iter=np.zeros(batch, np.uint32),
+               seconds=np.zeros(ticks))
     dev = (C.c_int * len(devices))(*devices)
     rc = dev_lib().sfbx_mpc_swarm_devlin_step_multi(variant, K, C.c_double(tf), C.c_int64(batch), C.c_uint64(seed), ticks, dev, len(devices),
                                                     int(thread_per_shard), _p(out["u0"]), _p(out["code"]), _p(out["iter"]), _p(out["seconds"]))
@@ -272,6 +273,44 @@ def ekf_swarm_host(states, P0, y, tau=0.1, dt=0.0, rk4=False):
     return out
 
 
+def pose_ekf_swarm_device(states, P0, y, tau=0.1, dt=0.0, rk4=False, fused=False):
+    """EKFSwarmDevice on the pose filter of rigid_body_model.h (G = SE3): states [batch][7] = (px, py, pz, w, x, y, z)"""
+    batch, steps = len(states), len(y)
+    out = dict(states=np.zeros((batch, 7)), P=np.zeros((batch, 36)), info=np.zeros(batch, np.int32))
+    st = np.ascontiguousarray(states, dtype=np.float64); P0 = np.ascontiguousarray(P0, dtype=np.float64); y = np.ascontiguousarray(y, dtype=np.float64)
+    rc = dev_lib().sfbx_pose_ekf_swarm_device(C.c_int64(batch), steps, int(rk4), int(fused), C.c_double(tau), C.c_double(dt), _p(st), _p(P0),
+                                              _p(y), _p(out["states"]), _p(out["P"]), _p(out["info"]))
+    assert rc == 0, rc
+    return out
+
+
+def pose_ekf_swarm_host(states, P0, y, tau=0.1, dt=0.0, rk4=False):
+    """the same through one host EKF<SE3> object per filter"""
+    batch, steps = len(states), len(y)
+    out = dict(states=np.zeros((batch, 7)), P=np.zeros((batch, 36)))
+    st = np.ascontiguousarray(states, dtype=np.float64); P0 = np.ascontiguousarray(P0, dtype=np.float64); y = np.ascontiguousarray(y, dtype=np.float64)
+    rc = lib().sfbx_pose_ekf_swarm_host(C.c_int64(batch), steps, int(rk4), C.c_double(tau), C.c_double(dt), _p(st), _p(P0), _p(y),
+                                        _p(out["states"]), _p(out["P"]))
+    assert rc == 0, rc
+    return out
+
+
+def asif_rigid_body(b=0):
+    """ASIFilter<Bundle<SE3, R6>, R6> on the rigid body, agent b (needs a GPU): filtered input, solver code, smallest row slack"""
+    u = np.zeros(6); code = C.c_int32(-1); slack = C.c_double(0.0)
+    rc = lib().sfbx_test_asif_rigid_body(C.c_int64(b), _p(u), C.byref(code), C.byref(slack))
+    assert rc == 0, rc
+    return u, code.value, slack.value
+
+
+def asif_rigid_body_swarm_device(batch):
+    """ASIFSwarmDevice on the same agents: u [batch][6], codes"""
+    u = np.zeros((batch, 6)); codes = np.zeros(batch, np.int32)
+    rc = dev_lib().sfbx_asif_rigid_body_swarm_device(C.c_int64(batch), _p(u), _p(codes))
+    assert rc == 0, rc
+    return u, codes
+
+
 def vehicle_swarm_sim(batch, ticks, K_mpc=30, K_asif=200, seed=0, reduced_kkt=False):
     """examples/mpc_asif_vehicle.cpp's closed loop for a swarm, MPC and ASI filter on the GPU (models_device.hip).
     reduced_kkt: the filter's QPs on the reduced-KKT route for tall problems (ASIFilterParams::reduced_kkt)."""
@@ -295,7 +334,7 @@ def asif_swarm_assemble(batch, K, seed=0):
     return out
 
 
-LIE_GROUPS = dict(R3=0, SE2=1, SO3=2, X6=3, X12=4)
+LIE_GROUPS = dict(R3=0, SE2=1, SO3=2, X6=3, X12=4, SE3=5, X12B=6)
 LIE_OPS = dict(exp=0, log=1, mul=2, ad=3, dr_expinv=4, rplus=5, rminus=6, rminus_rplus=7)
 
 

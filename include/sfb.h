@@ -450,7 +450,7 @@ sfb_status sfb_sparse_qp_solve_batch_host_multi(sfb_sparse_qp_plan *plan, const 
  * Jacobians [dfdx | dfdu | dcdx | dcdu] are read from that ONE record and the per-agent record shrinks to
  *   [ f | dxdes | c | e | J ].
  * ---------------------------------------------------------------------------------------- */
-typedef enum { SFB_LIE_RN = 0, SFB_LIE_SE2 = 1, SFB_LIE_SO3 = 2 } sfb_lie_kind;
+typedef enum { SFB_LIE_RN = 0, SFB_LIE_SE2 = 1, SFB_LIE_SO3 = 2, SFB_LIE_SE3 = 3 } sfb_lie_kind;
 
 typedef struct sfb_mpc_layout {
   int32_t nx, nu, ncr;      /* dof of state and input, running-constraint rows per node */
@@ -460,7 +460,7 @@ typedef struct sfb_mpc_layout {
   const double *D;          /* [(kmesh+1)*kmesh] differentiation matrix, D[j*kmesh + i] = Dus(j, i) (:243,:268) */
   int32_t nparts;           /* components of the state bundle, in order; 0 = commutative state (no ad term) */
   const int32_t *part_kind; /* [nparts] sfb_lie_kind */
-  const int32_t *part_dof;  /* [nparts] sums to nx (SE2 and SO3: 3) */
+  const int32_t *part_dof;  /* [nparts] sums to nx (SE2 and SO3: 3, SE3: 6) */
   const double *crl, *cru;  /* [ncr] bounds of the running constraint (OCP::crl / cru as set by the MPC constructor) */
   const uint8_t *jac_keep;  /* nullable.  Packed per-agent Jacobians: one flag per entry of the blocks
                                [dfdx nx*nx | dfdu nx*nu | dcdx ncr*nx | dcdu ncr*nu | J nx*nx], row-major (d, c);

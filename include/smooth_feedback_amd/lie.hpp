@@ -3,10 +3,11 @@
 // The reference gets this from pettni/smooth (absent here): right-invariant conventions
 //   rplus(g, a) = g * exp(a),  rminus(a, b) = log(b^-1 * a),  body velocities d^r x_t = f
 // (reference README.md:17-18, mpc.hpp:498,505,518, ekf.hpp:137).  Only what the hot path's callers
-// need is restated: R^n, SE(2), SO(3) and Bundle<...> with exp/log, ad and dr_expinv (the inverse right
+// need is restated: R^n, SE(2), SO(3), SE(3) and Bundle<...> with exp/log, ad and dr_expinv (the inverse right
 // Jacobian used by MPCCE::jacobian, mpc.hpp:293-301).  Semantics as summarised in SURVEY.md section
 // 8 ("smooth semantics the host side must restate").  Every operation is pinned to 60-digit values computed from the
-// matrix groups (tests/golden/lie_reference.npz; tests/test_lie_host.py on the host, tests/test_lie_gpu.py in device code).
+// matrix groups (tests/golden/lie_reference.npz; tests/test_lie_host.py on the host, tests/test_lie_gpu.py in device code;
+// SE(3): tests/golden/lie_se3_reference.npz, tests/test_lie_se3_host.py, tests/test_lie_se3_gpu.py).
 #pragma once
 #include <array>
 #include <cmath>
@@ -246,6 +247,147 @@ struct SO3 {
   }
 };
 
+namespace detail {
+// (th - sin th) / th^3, the coefficient of hat(w)^2 in the translation of SE3::exp
+//       = 1/6 - th^2/120 + th^4/5040 - ...
+// The closed form loses eps th / (th^3 / 6) = 6 eps / th^2 relative to the difference; the series through th^12 leaves
+// 6 th^14 / 17! = 1.7e-14 th^14 relative: they meet at th^2 = 0.67 (1e-15 relative, on a term that weighs th^2 / 6 in the
+// translation).  The switch sits a little below, where the series is the better of the two.
+SFB_LIE_HD inline double th_minus_sin_over_th3(double th2)
+{
+  if (th2 < 0.5)
+    return 1.0 / 6.0 - th2 * (1.0 / 120.0 - th2 * (1.0 / 5040.0 - th2 * (1.0 / 362880.0 - th2 * (1.0 / 39916800.0 - th2 * (1.0 / 6227020800.0 - th2 / 1307674368000.0)))));
+  const double th = std::sqrt(th2);
+  return (th - std::sin(th)) / (th2 * th);
+}
+// (1 - cos th) / th^2 = (sin(th/2) / (th/2))^2 / 2: the half angle has no difference to cancel, the series only bridges 0/0
+// (th^2 < 1e-8: truncation th^4 / 1920 = 5e-20).
+SFB_LIE_HD inline double one_minus_cos_over_th2(double th2)
+{
+  if (th2 < 1e-8) return 0.5 - th2 / 24.0;
+  const double h = 0.5 * std::sqrt(th2), s = std::sin(h) / h;
+  return 0.5 * s * s;
+}
+// k(th) of dr_expinv_coef for SE(3).  There k multiplies W V + V W, of size 2 th |v| in a block of size |v| / 2, where SE2
+// and SO3 only have W^2 (size th^2): the closed form's absolute error of 3 eps / th^2 is 8e-16 of that block just above
+// dr_expinv_coef's switch.  So the series runs further here: thirteen terms leave 9e-23 t^13 (t = th^2), which meets
+// 3 eps / t at t = 2.3 (4e-18 against 1.4e-16); the switch sits at 2.25.
+SFB_LIE_HD inline double dr_expinv_coef_wide(double t)
+{
+  if (t < 2.25)
+    return 1.0 / 12.0 + t * (1.0 / 720.0 + t * (1.0 / 30240.0 + t * (1.0 / 1209600.0 + t * (1.0 / 47900160.0 + t * (691.0 / 1307674368000.0
+         + t * (1.0 / 74724249600.0 + t * (3617.0 / 10670622842880000.0 + t * (8.586062056277845e-15 + t * (2.174868698558062e-16
+         + t * (5.5090028283602295e-18 + t * (1.3954464685812522e-19 + t * 3.534707039629467e-21)))))))))));
+  return dr_expinv_coef(t);
+}
+// k'(t) = d dr_expinv_coef / d(th^2), t = th^2: the coefficient that couples v and w in SE3::dr_expinv
+//       = -1/t^2 + (1 + c^2) / (8 t) + c / (4 t th),  c = cot(th / 2)
+//       = sum_n (n - 1) |B_2n| t^(n-2) / (2n)!.
+// The closed form subtracts numbers of size 1/t^2 from each other (absolute error 3 eps / t^2); the series through t^11
+// leaves 1.2e-21 t^12.  They meet at t = 2.1 (7e-18 against 8e-17: next to a value of 1.7e-3 that is 5e-14 relative, but the
+// coefficient multiplies 2 (w.v) hat(w)^2, of size 2 t^1.5 |v|, in a block of size |v| / 2: 1e-15 of the block at most).
+SFB_LIE_HD inline double dr_expinv_dcoef(double t)
+{
+  if (t < 2.0)
+    return 1.0 / 720.0 + t * (1.0 / 15120.0 + t * (1.0 / 403200.0 + t * (1.0 / 11975040.0 + t * (691.0 / 261534873600.0 + t * (1.0 / 12454041600.0
+         + t * (3617.0 / 1524374691840000.0 + t * (6.868849645022276e-14 + t * (1.9573818287022555e-15 + t * (5.5090028283602297e-17
+         + t * (1.5349911154393775e-18 + t * 4.241648447555361e-20))))))))));
+  const double th = std::sqrt(t), cs = std::cos(th), sn = std::sin(th);
+  const double c = (cs >= 0.0) ? (1.0 + cs) / sn : sn / (1.0 - cs);  // cot(th / 2), as in dr_expinv_coef
+  return -1.0 / (t * t) + (1.0 + c * c) / (8.0 * t) + c / (4.0 * t * th);
+}
+SFB_LIE_HD inline Vec<3> cross(const Vec<3> &a, const Vec<3> &b)
+{
+  return {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+}
+}  // namespace detail
+
+// ---- SE(3): translation p and unit quaternion q (as SO3); tangent (v_0, v_1, v_2, w_0, w_1, w_2), body velocities ----
+struct SE3 {
+  static constexpr int Dof           = 6;
+  static constexpr bool IsCommutative = false;
+  using Tangent                      = Vec<6>;
+  Vec<3> p{};
+  SO3 q{};
+
+  SFB_LIE_HD static SE3 Identity() { return SE3{}; }
+  // R(q) a = a + w t + u x t with t = 2 u x a, u the vector part
+  SFB_LIE_HD static Vec<3> rotate(const SO3 &q, const Vec<3> &a)
+  {
+    const Vec<3> u{q.x, q.y, q.z};
+    Vec<3> t = detail::cross(u, a);
+    for (auto &c : t) c *= 2.0;
+    const Vec<3> ut = detail::cross(u, t);
+    return {a[0] + q.w * t[0] + ut[0], a[1] + q.w * t[1] + ut[1], a[2] + q.w * t[2] + ut[2]};
+  }
+
+  // p = (I + B hat(w) + C hat(w)^2) v,  B = (1 - cos th) / th^2,  C = (th - sin th) / th^3
+  SFB_LIE_HD static SE3 exp(const Tangent &a)
+  {
+    const Vec<3> v{a[0], a[1], a[2]}, w{a[3], a[4], a[5]};
+    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+    const double B = detail::one_minus_cos_over_th2(th2), C = detail::th_minus_sin_over_th3(th2);
+    const Vec<3> wv = detail::cross(w, v), wwv = detail::cross(w, wv);
+    return SE3{{v[0] + B * wv[0] + C * wwv[0], v[1] + B * wv[1] + C * wwv[1], v[2] + B * wv[2] + C * wwv[2]}, SO3::exp(w)};
+  }
+  // v = (I - hat(w) / 2 + k hat(w)^2) p with the k of dr_expinv: the inverse of the matrix in exp
+  SFB_LIE_HD Tangent log() const
+  {
+    const Vec<3> w = q.log();
+    const double k = detail::dr_expinv_coef_wide(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+    const Vec<3> wp = detail::cross(w, p), wwp = detail::cross(w, wp);
+    return {p[0] - 0.5 * wp[0] + k * wwp[0], p[1] - 0.5 * wp[1] + k * wwp[1], p[2] - 0.5 * wp[2] + k * wwp[2], w[0], w[1], w[2]};
+  }
+  SFB_LIE_HD SE3 inverse() const
+  {
+    const SO3 qi = q.inverse();
+    const Vec<3> r = rotate(qi, p);
+    return SE3{{-r[0], -r[1], -r[2]}, qi};
+  }
+  SFB_LIE_HD friend SE3 operator*(const SE3 &g, const SE3 &h)
+  {
+    const Vec<3> r = rotate(g.q, h.p);
+    return SE3{{g.p[0] + r[0], g.p[1] + r[1], g.p[2] + r[2]}, g.q * h.q};
+  }
+  SFB_LIE_HD friend SE3 rplus(const SE3 &g, const Tangent &a) { return g * exp(a); }
+  SFB_LIE_HD friend Tangent rminus(const SE3 &a, const SE3 &b) { return (b.inverse() * a).log(); }
+
+  // [[hat(w), hat(v)], [0, hat(w)]]
+  SFB_LIE_HD static Mat<6, 6> ad(const Tangent &a)
+  {
+    Mat<6, 6> m{};
+    for (int b = 0; b < 2; ++b) {  // hat(w) on the diagonal blocks
+      const int o = 3 * b;
+      m(o + 0, o + 1) = -a[5]; m(o + 0, o + 2) = a[4];
+      m(o + 1, o + 0) = a[5];  m(o + 1, o + 2) = -a[3];
+      m(o + 2, o + 0) = -a[4]; m(o + 2, o + 1) = a[3];
+    }
+    m(0, 4) = -a[2]; m(0, 5) = a[1];
+    m(1, 3) = a[2];  m(1, 5) = -a[0];
+    m(2, 3) = -a[1]; m(2, 4) = a[0];
+    return m;
+  }
+  // inverse of the right Jacobian of exp, sum_n B_n^+ ad^n / n!, in block form: ad is block upper triangular with equal
+  // diagonal blocks, so a function of it is [[J, Q], [0, J]] with J = SO3::dr_expinv(w) = I + W/2 + k W^2 and Q the
+  // derivative of J in the direction v:  Q = V/2 + k (W V + V W) + 2 (w.v) k'(th^2) W^2   (W = hat(w), V = hat(v))
+  SFB_LIE_HD static Mat<6, 6> dr_expinv(const Tangent &a)
+  {
+    const Vec<3> v{a[0], a[1], a[2]}, w{a[3], a[4], a[5]};
+    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+    const double k = detail::dr_expinv_coef_wide(th2), dk2 = 2.0 * (w[0] * v[0] + w[1] * v[1] + w[2] * v[2]) * detail::dr_expinv_dcoef(th2);
+    const Mat<3, 3> W = SO3::ad(w), V = SO3::ad(v), W2 = W * W, WV = W * V;
+    Mat<6, 6> m{};
+    for (int c = 0; c < 3; ++c)
+      for (int r = 0; r < 3; ++r) {
+        const double J = (r == c ? 1.0 : 0.0) + 0.5 * W(r, c) + k * W2(r, c);
+        m(r, c) = J;
+        m(3 + r, 3 + c) = J;
+        m(r, 3 + c) = 0.5 * V(r, c) + k * (WV(r, c) + WV(c, r)) + dk2 * W2(r, c);  // V W = (W V)' for two skew matrices
+      }
+    return m;
+  }
+};
+
 // ---- Bundle<G...>: direct product, tangent = concatenation (first part first) ----
 template<class... Gs>
 struct Bundle {
@@ -334,6 +476,10 @@ struct LieParts<SE2> {
 template<>
 struct LieParts<SO3> {
   static void append(std::vector<int32_t> &kind, std::vector<int32_t> &dof) { kind.push_back(2); dof.push_back(3); }
+};
+template<>
+struct LieParts<SE3> {
+  static void append(std::vector<int32_t> &kind, std::vector<int32_t> &dof) { kind.push_back(3); dof.push_back(6); }
 };
 template<class... Gs>
 struct LieParts<Bundle<Gs...>> {

@@ -78,8 +78,9 @@ sfb_status check_layout(const sfb_mpc_layout *L)
   int dof = 0;
   for (int g = 0; g < L->nparts; ++g) {
     const int k = L->part_kind[g], d = L->part_dof[g];
-    if (k != SFB_LIE_RN && k != SFB_LIE_SE2 && k != SFB_LIE_SO3) return sfb::fail(SFB_ERR_INVALID_ARG, "layout: unknown part kind");
-    if (d < 1 || ((k == SFB_LIE_SE2 || k == SFB_LIE_SO3) && d != 3)) return sfb::fail(SFB_ERR_INVALID_ARG, "layout: bad part dof");
+    if (k != SFB_LIE_RN && k != SFB_LIE_SE2 && k != SFB_LIE_SO3 && k != SFB_LIE_SE3) return sfb::fail(SFB_ERR_INVALID_ARG, "layout: unknown part kind");
+    if (d < 1 || ((k == SFB_LIE_SE2 || k == SFB_LIE_SO3) && d != 3) || (k == SFB_LIE_SE3 && d != 6))
+      return sfb::fail(SFB_ERR_INVALID_ARG, "layout: bad part dof");
     dof += d;
   }
   if (L->nparts > 0 && dof != L->nx) return sfb::fail(SFB_ERR_INVALID_ARG, "layout: part dofs do not sum to nx");
@@ -130,7 +131,8 @@ void set_packing(sfb::MpcAsmParams &p, bool shared, const uint8_t *keep)
   p.rec_doubles = o;
 }
 
-// ad(a) of the bundle as a sign/index table (lie.hpp: SE2::ad, SO3::ad = hat)
+// ad(a) of the bundle as a sign/index table (lie.hpp: SE2::ad, SO3::ad = hat, SE3::ad = [[hat(w), hat(v)], [0, hat(w)]]):
+// every entry is plus or minus ONE tangent component, coded as sign * (index + 1) <= kMpcMaxNx = 24 in an int8_t
 void fill_params(const sfb_mpc_layout *L, bool shared, sfb::MpcAsmParams &p)
 {
   std::memset(&p, 0, sizeof(p));
@@ -161,6 +163,15 @@ void fill_params(const sfb_mpc_layout *L, bool shared, sfb::MpcAsmParams &p)
       set(0, 1, 2, -1); set(0, 2, 1, +1);
       set(1, 0, 2, +1); set(1, 2, 0, -1);
       if (k == SFB_LIE_SO3) { set(2, 0, 1, -1); set(2, 1, 0, +1); }
+    } else if (k == SFB_LIE_SE3) {
+      p.has_ad = 1;
+      // hat(x)(r, c) = sign * x[src] for (r, c, src, sign) below; blocks (0,0) and (3,3) take w = a[3..5], block (0,3) v = a[0..2]
+      static const int hat[6][4] = {{0, 1, 2, -1}, {0, 2, 1, +1}, {1, 0, 2, +1}, {1, 2, 0, -1}, {2, 0, 1, -1}, {2, 1, 0, +1}};
+      for (const auto &h : hat) {
+        set(h[0], h[1], 3 + h[2], h[3]);
+        set(3 + h[0], 3 + h[1], 3 + h[2], h[3]);
+        set(h[0], 3 + h[1], h[2], h[3]);
+      }
     }
     off += L->part_dof[g];
   }

@@ -9,7 +9,7 @@ import numpy as np
 from . import _capi
 from .qp import QPSolverParams, SparseQPPlan, _f64, _ptr
 
-LIE_RN, LIE_SE2, LIE_SO3 = 0, 1, 2
+LIE_RN, LIE_SE2, LIE_SO3, LIE_SE3 = 0, 1, 2, 3
 
 
 class MPCLayout:
