@@ -14,6 +14,7 @@
 #include <smooth_feedback_amd/ekf.hpp>
 #include <smooth_feedback_amd/mpc.hpp>
 #include <smooth/feedback/mpc.hpp>  // the reference's include path and namespace (sfbx_test_mpc_api)
+#include <smooth/feedback/pid.hpp>  // likewise (sfbx_test_pid_api, sfbx_pid_host)
 
 #include "lie_eval.h"
 #include "rigid_body_model.h"
@@ -1302,4 +1303,160 @@ int sfbx_lie_eval(int group, int op, int64_t count, const double * in, double * 
     for (int64_t b = 0; b < count; ++b) sfbx::lie_eval_item<G>(op, in + b * win, out + b * wout);
   });
   return 0;
+}
+
+// ---- PID ----
+namespace {
+
+// caller code against <smooth/feedback/pid.hpp>: the reference's names and namespace
+int test_pid_api(double * out)
+{
+  using namespace std::chrono_literals;
+  namespace sf = smooth::feedback;
+  using Sec    = std::chrono::duration<double>;
+  using PidT   = sf::PID<Sec, sf::SE2>;
+  const auto sq = [](const sf::SE2::Tangent & u) { return u[0] * u[0] + u[1] * u[1] + u[2] * u[2]; };
+  const sf::SE2::Tangent zero{};
+  {
+    PidT pid;  // PIDParams{} by default
+    pid.set_kp(1);
+    pid.set_kd(1);
+    pid.set_ki(1);
+    pid.set_kp(sf::SE2::Tangent{1, 1, 1});
+    pid.set_kd(sf::SE2::Tangent{1, 1, 1});
+    pid.set_ki(sf::SE2::Tangent{1, 1, 1});
+    out[0] = sq(pid(Sec(5s), sf::SE2::Identity(), zero));  // at the target, nothing integrated: <= 1e-10
+    (void)pid(Sec(6s), sf::SE2::FromAngle(0.7, 0.4, -1.1), zero);
+    (void)pid(Sec(7s), sf::SE2::FromAngle(-1.9, 2.0, 0.3), zero);
+    out[1] = sq(pid(Sec(8s), sf::SE2::Identity(), zero));  // the integral of the two excursions acts: >= 1e-10
+    pid.reset_integral();
+    out[2] = sq(pid(Sec(9s), sf::SE2::Identity(), zero));  // <= 1e-10 again
+  }
+  // a function trajectory, kp = 2, kd = 3: u = a_des + 3 (v_des - v) + 2 (g_des (-) g)
+  double worst = 0.0;
+  std::mt19937_64 rng(11);
+  std::uniform_real_distribution<double> d(-1.0, 1.0);
+  for (int rep = 0; rep < 5; ++rep) {
+    PidT pid(sf::PIDParams{.windup_limit = 2.0});
+    pid.set_kp(2);
+    pid.set_kd(3);
+    const sf::SE2 g0 = sf::SE2::FromAngle(3 * d(rng), d(rng), d(rng));
+    const sf::SE2::Tangent w{d(rng), d(rng), d(rng)}, acc{d(rng), d(rng), d(rng)};
+    const std::function<PidT::TrajectoryReturnT(Sec)> xdes = [=](Sec t) -> PidT::TrajectoryReturnT {
+      const double s = t.count() - 0.5;
+      return {rplus(g0, sf::SE2::Tangent{s * w[0], s * w[1], s * w[2]}), w, acc};
+    };
+    if (rep % 2) pid.set_xdes(xdes);  // both value categories
+    else pid.set_xdes(std::function<PidT::TrajectoryReturnT(Sec)>(xdes));
+    const sf::SE2 g = sf::SE2::FromAngle(3 * d(rng), d(rng), d(rng));
+    const sf::SE2::Tangent v{d(rng), d(rng), d(rng)};
+    const auto u = pid(Sec(1s), g, v);
+    const auto [g_des, v_des, a_des] = xdes(Sec(1s));
+    const auto e = rminus(g_des, g);
+    double num = 0, den = 0;
+    for (int i = 0; i < 3; ++i) {
+      const double expect = a_des[i] + 3 * (v_des[i] - v[i]) + 2 * e[i];
+      num += (u[i] - expect) * (u[i] - expect);
+      den += expect * expect;
+    }
+    worst = std::max(worst, std::sqrt(num / den));  // isApprox: relative, 1e-12
+  }
+  out[3] = worst;
+  return (out[0] <= 1e-10 && out[1] >= 1e-10 && out[2] <= 1e-10 && worst <= 1e-12) ? 0 : 1;
+}
+
+template<class G>
+void pid_host(int64_t batch, int ncalls, const double * times, const double * x, const double * v, const double * gd, const double * vd,
+              const double * ad, const double * kp, const double * kd, const double * ki, double windup, double * u_out, double * ie_out)
+{
+  using PidT      = smooth::feedback::PID<double, G>;
+  using Flat      = PIDFlat<G>;
+  constexpr int E = Flat::E, D = G::Dof;
+  const auto tangent = [](const double * p) {
+    typename G::Tangent t{};
+    for (int i = 0; i < D; ++i) t[i] = p[i];
+    return t;
+  };
+  for (int64_t b = 0; b < batch; ++b) {
+    PidT pid(PIDParams{windup});
+    pid.set_kp(tangent(kp + b * D));
+    pid.set_kd(tangent(kd + b * D));
+    pid.set_ki(tangent(ki + b * D));
+    int call = 0;
+    pid.set_xdes([&](double) -> typename PidT::TrajectoryReturnT {
+      const int64_t r = b * ncalls + call;
+      return {Flat::load(gd + r * E), tangent(vd + r * D), tangent(ad + r * D)};
+    });
+    for (call = 0; call < ncalls; ++call) {
+      const int64_t r = b * ncalls + call;
+      const auto u    = pid(times[call], Flat::load(x + r * E), tangent(v + r * D));
+      for (int i = 0; i < D; ++i) {
+        u_out[r * D + i]  = u[i];
+        ie_out[r * D + i] = pid.integral()[i];
+      }
+    }
+  }
+}
+
+// pid_rollout (pid.hpp) on the CPU: the per-lane function of the rollout kernels, one agent after the other
+template<class G>
+void pid_rollout_host(int64_t batch, double t0, double dt, int64_t steps, double * x, double * v, const double * g0, const double * w,
+                      const double * kp, const double * kd, const double * ki, double windup, const double * u_max, double * ie, double * t_last,
+                      double * u_last, double * cost)
+{
+  using Flat      = PIDFlat<G>;
+  constexpr int E = Flat::E, D = G::Dof;
+  const auto tangent = [](const double * p) {
+    typename G::Tangent t{};
+    for (int i = 0; i < D; ++i) t[i] = p[i];
+    return t;
+  };
+  for (int64_t b = 0; b < batch; ++b) {
+    G xb     = Flat::load(x + b * E);
+    auto vb  = tangent(v + b * D), ieb = tangent(ie + b * D);
+    typename G::Tangent ul{};
+    cost[b] = pid_rollout<G>(PIDConstantTwist<G>{Flat::load(g0 + b * E), tangent(w + b * D)}, t0, dt, steps, xb, vb, tangent(kp + b * D),
+                             tangent(kd + b * D), tangent(ki + b * D), windup, u_max != nullptr, u_max ? tangent(u_max) : typename G::Tangent{},
+                             t_last[b], ieb, ul);
+    Flat::store(xb, x + b * E);
+    for (int i = 0; i < D; ++i) {
+      v[b * D + i]      = vb[i];
+      ie[b * D + i]     = ieb[i];
+      u_last[b * D + i] = ul[i];
+    }
+  }
+}
+
+template<class Fn>
+int pid_dispatch(int group, Fn && run)
+{
+  switch (group) {
+  case 0: run.template operator()<Rn<2>>(); return 0;
+  case 1: run.template operator()<SE2>(); return 0;
+  case 2: run.template operator()<SO3>(); return 0;
+  case 3: run.template operator()<SE3>(); return 0;
+  case 4: run.template operator()<Bundle<SE3, Rn<3>>>(); return 0;
+  case 5: run.template operator()<Bundle<SE2, Rn<1>>>(); return 0;
+  default: return -1;
+  }
+}
+
+}  // namespace
+
+int sfbx_test_pid_api(double * out) { return test_pid_api(out); }
+
+int sfbx_pid_rollout_host(int group, int64_t batch, double t0, double dt, int64_t steps, double * x, double * v, const double * g0,
+                          const double * w, const double * kp, const double * kd, const double * ki, double windup, const double * u_max,
+                          double * ie, double * t_last, double * u_last, double * cost)
+{
+  if (batch < 0 || steps < 0) return -1;
+  return pid_dispatch(group, [&]<class G>() { pid_rollout_host<G>(batch, t0, dt, steps, x, v, g0, w, kp, kd, ki, windup, u_max, ie, t_last, u_last, cost); });
+}
+
+int sfbx_pid_host(int group, int64_t batch, int ncalls, const double * times, const double * x, const double * v, const double * gd,
+                  const double * vd, const double * ad, const double * kp, const double * kd, const double * ki, double windup, double * u_out,
+                  double * ie_out)
+{
+  if (batch < 0 || ncalls < 0) return -1;
+  return pid_dispatch(group, [&]<class G>() { pid_host<G>(batch, ncalls, times, x, v, gd, vd, ad, kp, kd, ki, windup, u_out, ie_out); });
 }

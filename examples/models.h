@@ -130,6 +130,23 @@ int sfbx_pose_ekf_swarm_host(int64_t batch, int steps, int rk4, double tau, doub
                              const double *y, double *states_out, double *P_out);
 /* ASIFilter<Bundle<SE3,R6>, R6> on the rigid body, agent b of the filter tests: filtered input u [6], solver code, smallest constraint slack at the solution */
 int sfbx_test_asif_rigid_body(int64_t b, double *u_out, int32_t *code, double *slack);
+/* PID<T, G> through <smooth/feedback/pid.hpp> (host only): the call sequence of the reference's first PID test -- setters
+ * in both forms, calls at and away from the target, reset_integral() -- then a function trajectory with kp = 2, kd = 3.
+ * out [4]: |u|^2 at the target before / after integrating / after the reset, worst relative error of the trajectory check.
+ * Returns 0 when all four are as expected. */
+int sfbx_test_pid_api(double *out);
+/* A batch pushed through one host PID<double, G> per agent: group 0 Rn<2>, 1 SE2, 2 SO3, 3 SE3, 4 Bundle<SE3, Rn<3>>,
+ * 5 Bundle<SE2, Rn<1>>.  Every controller is called at times[0 .. ncalls) with the state x, v [batch][ncalls][...] and the
+ * desired triple gd, vd, ad [batch][ncalls][...] of that call (element layout of sfb_pid_*); gains [batch][dof].
+ * Out: u and the integral state after each call, [batch][ncalls][dof]. */
+int sfbx_pid_host(int group, int64_t batch, int ncalls, const double *times, const double *x, const double *v, const double *gd,
+                  const double *vd, const double *ad, const double *kp, const double *kd, const double *ki, double windup,
+                  double *u_out, double *ie_out);
+/* pid_rollout of pid.hpp -- the per-lane function of sfb_pid_rollout_batch and PIDSwarmDevice -- on the CPU, whole group at once
+ * (no part-by-part split): arguments as sfb_pid_rollout_batch_host with per-agent gains and trajectories, groups as above. */
+int sfbx_pid_rollout_host(int group, int64_t batch, double t0, double dt, int64_t steps, double *x, double *v, const double *g0,
+                          const double *w, const double *kp, const double *kd, const double *ki, double windup, const double *u_max,
+                          double *ie, double *t_last, double *u_last, double *cost);
 /* mesh: nodes (N+1), weights (N+1), Dus ((K+1)*K col-major) for `n` intervals of K points */
 int sfbx_mesh(int n_ivals, int K, double *nodes, double *weights, double *Dus);
 

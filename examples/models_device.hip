@@ -12,6 +12,7 @@
 #include <smooth_feedback_amd/ekf_device.hpp>
 #include <smooth_feedback_amd/mpc_device.hpp>
 #include <smooth_feedback_amd/multi_device.hpp>
+#include <smooth_feedback_amd/pid_device.hpp>
 
 #include "lie_eval.h"
 #include "rigid_body_model.h"
@@ -512,6 +513,106 @@ int sfbx_lie_eval_device(int group, int op, int64_t count, const double * in, do
     return -2;
   }
   return 0;
+}
+
+}  // extern "C"
+
+namespace {
+// The trajectory functor of sfbx_pid_swarm_device: per agent a start pose g0 and a twist direction w (device arrays).
+// kind 0: constant twist, what PIDConstantTwist (the family of sfb_pid_rollout_batch) returns; kind 1: the twist keeps its
+// direction and changes its size, s(t) = 1 + 0.3 t:  g_des = rplus(g0, S(t) w), v_des = s(t) w, a_des = s'(t) w with
+// S(t) = t + 0.15 t^2 -- dynamically consistent (pid.hpp:170-176), since twists of one direction commute.
+struct PidSwarmTraj {
+  const SE3 * g0;
+  const double * w;  // [agents][6]
+  const int32_t * kind;
+  __host__ __device__ PIDDesired<SE3> operator()(int64_t agent, double t) const
+  {
+    SE3::Tangent wa{};
+    for (int i = 0; i < 6; ++i) wa[i] = w[agent * 6 + i];
+    if (kind[agent] == 0) return PIDConstantTwist<SE3>{g0[agent], wa}(t);
+    const double s = 1.0 + 0.3 * t, S = t + 0.15 * t * t;
+    PIDDesired<SE3> d;
+    SE3::Tangent Sw{};
+    for (int i = 0; i < 6; ++i) {
+      Sw[i]  = S * wa[i];
+      d.v[i] = s * wa[i];
+      d.a[i] = 0.3 * wa[i];
+    }
+    d.g = rplus(g0[agent], Sw);
+    return d;
+  }
+};
+}  // namespace
+
+extern "C" {
+
+/* PIDSwarmDevice<SE3, functor> (pid_device.hpp): agents with states x [batch][7], v [batch][6], controllers' state ie
+ * [batch][6] and t_last [batch], gains [batch][6], trajectory g0 [batch][7], w [batch][6], kind [batch] (0: constant twist,
+ * 1: a twist of changing size).  steps > 0: rollout(t0, dt, steps); steps == 0: one step(t0).  u_max [6] nullable.
+ * Out: x, v, ie, u [batch][...], cost [batch] (rollout only). */
+int sfbx_pid_swarm_device(int64_t batch, double t0, double dt, int64_t steps, const double * x, const double * v, const double * ie,
+                          const double * t_last, const double * kp, const double * kd, const double * ki, const double * g0, const double * w,
+                          const int32_t * kind, double windup, const double * u_max, double * x_out, double * v_out, double * ie_out,
+                          double * u_out, double * cost_out)
+{
+  if (batch < 1 || steps < 0) return -1;
+  SE3 * dg0 = nullptr;
+  double * dw = nullptr;
+  int32_t * dkind = nullptr;
+  int rc = 0;
+  try {
+    const size_t B = (size_t)batch;
+    using T6       = SE3::Tangent;
+    const auto tangents = [&](const double * p) {
+      std::vector<T6> out(B);
+      for (size_t b = 0; b < B; ++b)
+        for (int i = 0; i < 6; ++i) out[b][i] = p[6 * b + i];
+      return out;
+    };
+    const auto poses = [&](const double * p) {
+      std::vector<SE3> out(B);
+      for (size_t b = 0; b < B; ++b) out[b] = PIDFlat<SE3>::load(p + 7 * b);
+      return out;
+    };
+    const std::vector<SE3> hg0 = poses(g0);
+    detail::pid_hip_check(hipMalloc(reinterpret_cast<void **>(&dg0), B * sizeof(SE3)), "hipMalloc");
+    detail::pid_hip_check(hipMalloc(reinterpret_cast<void **>(&dw), B * 6 * sizeof(double)), "hipMalloc");
+    detail::pid_hip_check(hipMalloc(reinterpret_cast<void **>(&dkind), B * sizeof(int32_t)), "hipMalloc");
+    detail::pid_hip_check(hipMemcpy(dg0, hg0.data(), B * sizeof(SE3), hipMemcpyHostToDevice), "hipMemcpy");
+    detail::pid_hip_check(hipMemcpy(dw, w, B * 6 * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
+    detail::pid_hip_check(hipMemcpy(dkind, kind, B * sizeof(int32_t), hipMemcpyHostToDevice), "hipMemcpy");
+    PIDSwarmDevice<SE3, PidSwarmTraj> swarm(PidSwarmTraj{dg0, dw, dkind}, batch, PIDParams{windup});
+    swarm.set_state(poses(x), tangents(v));
+    swarm.set_gains(tangents(kp), tangents(kd), tangents(ki));
+    swarm.set_integral(tangents(ie), std::vector<double>(t_last, t_last + B));
+    if (u_max) {
+      T6 um{};
+      for (int i = 0; i < 6; ++i) um[i] = u_max[i];
+      swarm.set_u_max(um);
+    }
+    if (steps > 0) swarm.rollout(t0, dt, steps);
+    else swarm.step(t0);
+    const auto xs = swarm.states();
+    const auto vs = swarm.velocities(), is = swarm.integrals(), us = swarm.inputs();
+    const auto cs = swarm.costs();
+    for (size_t b = 0; b < B; ++b) {
+      PIDFlat<SE3>::store(xs[b], x_out + 7 * b);
+      for (int i = 0; i < 6; ++i) {
+        v_out[6 * b + i]  = vs[b][i];
+        ie_out[6 * b + i] = is[b][i];
+        u_out[6 * b + i]  = us[b][i];
+      }
+      cost_out[b] = steps > 0 ? cs[b] : 0.0;
+    }
+  } catch (const std::exception & e) {
+    std::fprintf(stderr, "sfbx_pid_swarm_device: %s\n", e.what());
+    rc = -2;
+  }
+  (void)hipFree(dg0);
+  (void)hipFree(dw);
+  (void)hipFree(dkind);
+  return rc;
 }
 
 }  // extern "C"

@@ -356,3 +356,55 @@ def lie_eval(group, op, inp, device=False):
     rc = fn(LIE_GROUPS[group], LIE_OPS[op], C.c_int64(len(inp)), _p(inp), _p(out))
     assert rc == 0, rc
     return out
+
+
+PID_GROUPS = dict(R2=0, SE2=1, SO3=2, SE3=3, SE3R3=4, SE2R1=5)
+PID_PARTS = dict(R2=[("RN", 2)], SE2=[("SE2", 3)], SO3=[("SO3", 3)], SE3=[("SE3", 6)], SE3R3=[("SE3", 6), ("RN", 3)], SE2R1=[("SE2", 3), ("RN", 1)])
+
+
+def test_pid_api():
+    """PID<T, G> under the reference's include path (models.h): (ok, [|u|^2 at the target x 3, trajectory check])"""
+    out = np.zeros(4)
+    rc = lib().sfbx_test_pid_api(_p(out))
+    return rc == 0, out
+
+
+def pid_host(group, times, x, v, gd, vd, ad, kp, kd, ki, windup=np.inf):
+    """one host PID<double, G> per agent, called at `times`: x, gd [B][ncalls][elem]; v, vd, ad [B][ncalls][dof]; gains
+    [B][dof].  Returns u and the integral state after each call, [B][ncalls][dof]."""
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (x, v, gd, vd, ad, kp, kd, ki)]
+    B, n = arrs[0].shape[0], len(times)
+    D = arrs[5].shape[1]
+    assert all(a.shape[:2] == (B, n) for a in arrs[:5]) and all(a.shape == (B, D) for a in arrs[5:])
+    u = np.zeros((B, n, D)); ie = np.zeros((B, n, D))
+    rc = lib().sfbx_pid_host(PID_GROUPS[group], C.c_int64(B), n, _p(times), *[_p(a) for a in arrs], C.c_double(windup), _p(u), _p(ie))
+    assert rc == 0, rc
+    return u, ie
+
+
+def pid_rollout_host(group, t0, dt, steps, x, v, g0, w, kp, kd, ki, ie, t_last, windup=np.inf, u_max=None):
+    """pid_rollout (pid.hpp) on the CPU for every agent; arrays as smooth_feedback_amd.pid_rollout_batch_host, same dict back"""
+    x, v, ie, t_last = [np.array(a, dtype=np.float64, order="C") for a in (x, v, ie, t_last)]
+    g0, w, kp, kd, ki = [np.ascontiguousarray(a, dtype=np.float64) for a in (g0, w, kp, kd, ki)]
+    um = None if u_max is None else np.ascontiguousarray(u_max, dtype=np.float64)
+    B = len(x)
+    u = np.zeros_like(v); cost = np.zeros(B)
+    rc = lib().sfbx_pid_rollout_host(PID_GROUPS[group], C.c_int64(B), C.c_double(t0), C.c_double(dt), C.c_int64(steps), _p(x), _p(v), _p(g0), _p(w),
+                                     _p(kp), _p(kd), _p(ki), C.c_double(windup), None if um is None else _p(um), _p(ie), _p(t_last), _p(u), _p(cost))
+    assert rc == 0, rc
+    return dict(x=x, v=v, i_err=ie, t_last=t_last, u_last=u, cost=cost)
+
+
+def pid_swarm_device(t0, dt, steps, x, v, ie, t_last, kp, kd, ki, g0, w, kind, windup=np.inf, u_max=None):
+    """PIDSwarmDevice<SE3, functor> (pid_device.hpp, models_device.hip): rollout(t0, dt, steps), or one step(t0) for steps == 0,
+    of agents tracking rplus(g0, t w) (kind 0) or a twist of changing size along w (kind 1).  Returns dict x, v, ie, u, cost."""
+    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (x, v, ie, t_last, kp, kd, ki, g0, w)]
+    B = len(arrs[0])
+    kind = np.ascontiguousarray(kind, dtype=np.int32)
+    um = None if u_max is None else np.ascontiguousarray(u_max, dtype=np.float64)
+    out = dict(x=np.zeros((B, 7)), v=np.zeros((B, 6)), ie=np.zeros((B, 6)), u=np.zeros((B, 6)), cost=np.zeros(B))
+    rc = dev_lib().sfbx_pid_swarm_device(C.c_int64(B), C.c_double(t0), C.c_double(dt), C.c_int64(steps), *[_p(a) for a in arrs], _p(kind),
+                                         C.c_double(windup), None if um is None else _p(um), *[_p(out[k]) for k in ("x", "v", "ie", "u", "cost")])
+    assert rc == 0, rc
+    return out

@@ -588,6 +588,58 @@ sfb_status sfb_ekf_step_batch_host(int64_t batch, int dof, int ny, const double 
                                    const double *dt, int dt_shared, const double *H, const double *R,
                                    int r_shared, const double *r, double *P, double *delta, int32_t *info);
 
+/* ------------------------------------------------------------------------------------------
+ * Batched Lie-group PID: smooth::feedback::PID<T, G>::operator() (pid.hpp:74-87) for `batch` independent controllers,
+ * and the closed loop on the system the controller is designed for (d^r x = v, dv/dt = u; pid.hpp:29-35) in one launch.
+ *
+ * The group is described at run time like the state of sfb_mpc_layout: parts in order, each an sfb_lie_kind with its
+ * dof (SFB_LIE_RN: any dof >= 1; SE2 and SO3: 3; SE3: 6), at most SFB_PID_MAX_PARTS parts.  Element storage per part:
+ *   RN  N values | SE2 (x, y, cos, sin) | SO3 (w, x, y, z) | SE3 (px, py, pz, w, x, y, z)
+ * a bundle is the concatenation of its parts, tangents are concatenated in the same order (SE2 (vx, vy, omega), SE3
+ * (v, omega)).  elem = sfb_pid_elem_doubles(group), dof = sfb_pid_dof(group) (both -1 for a bad descriptor).
+ * All arrays are [batch][...] contiguous doubles.  des_shared != 0: g_des, v_des (and a_des) hold ONE item used by every
+ * agent; gains_shared != 0: the same for kp, kd, ki.  t_last [batch]: NaN = unset (first call).  windup_limit >= 0,
+ * +inf = no clamp.  One agent per GPU lane; a bundle is run part by part (law, clamp and step are componentwise in the
+ * tangent and rplus / rminus of a bundle act per part).  Device pointers, asynchronous on `stream`; the descriptor is
+ * host memory.  SFB_ERR_INVALID_ARG for a bad descriptor, steps < 0, a non-finite dt, a negative or NaN windup_limit or
+ * a NULL array with batch > 0, then SFB_ERR_NO_DEVICE without a device: both before any device work.
+ * ---------------------------------------------------------------------------------------- */
+#define SFB_PID_MAX_PARTS 8
+typedef struct sfb_pid_group {
+  int32_t nparts;           /* 1 .. SFB_PID_MAX_PARTS */
+  const int32_t *part_kind; /* [nparts] sfb_lie_kind */
+  const int32_t *part_dof;  /* [nparts] */
+} sfb_pid_group;
+int64_t sfb_pid_elem_doubles(const sfb_pid_group *group);
+int64_t sfb_pid_dof(const sfb_pid_group *group);
+/* One controller call at time t for every agent.  In: x [elem], v [dof], g_des [elem], v_des, a_des [dof], kp, kd, ki
+ * [dof].  In/out: i_err [dof], t_last [1].  Out: u [dof]. */
+sfb_status sfb_pid_step_batch(const sfb_pid_group *group, int64_t batch, double t, const double *x, const double *v,
+                              const double *g_des, const double *v_des, const double *a_des, int des_shared,
+                              const double *kp, const double *kd, const double *ki, int gains_shared,
+                              double windup_limit, double *i_err, double *t_last, double *u, void *stream);
+/* `steps` closed-loop ticks of length dt from t0 in ONE launch.  Every agent tracks the constant-twist reference
+ * g_des(t) = rplus(g_des0, t v_des) with velocity v_des and acceleration 0 (recomputed from t each tick).  Tick k at
+ * t_k = t0 + k dt: the law, u <- clamp(u, -u_max, u_max) (u_max [dof] shared by all agents, NULL: no clamp), then
+ * x <- rplus(x, dt v + dt^2/2 u), v <- v + dt u (classical RK4 with u held, in closed form).  In/out: x, v, i_err,
+ * t_last.  Out: u_last [dof] (the last tick's input) and cost [1] = sum_k dt |g_des(t_k) (-) x_k|^2 in tick order.
+ * steps == 0 writes nothing. */
+sfb_status sfb_pid_rollout_batch(const sfb_pid_group *group, int64_t batch, double t0, double dt, int64_t steps,
+                                 double *x, double *v, const double *g_des0, const double *v_des, int des_shared,
+                                 const double *kp, const double *kd, const double *ki, int gains_shared,
+                                 double windup_limit, const double *u_max, double *i_err, double *t_last,
+                                 double *u_last, double *cost, void *stream);
+/* Host-pointer variants (stage through device memory, synchronous). */
+sfb_status sfb_pid_step_batch_host(const sfb_pid_group *group, int64_t batch, double t, const double *x,
+                                   const double *v, const double *g_des, const double *v_des, const double *a_des,
+                                   int des_shared, const double *kp, const double *kd, const double *ki,
+                                   int gains_shared, double windup_limit, double *i_err, double *t_last, double *u);
+sfb_status sfb_pid_rollout_batch_host(const sfb_pid_group *group, int64_t batch, double t0, double dt, int64_t steps,
+                                      double *x, double *v, const double *g_des0, const double *v_des, int des_shared,
+                                      const double *kp, const double *kd, const double *ki, int gains_shared,
+                                      double windup_limit, const double *u_max, double *i_err, double *t_last,
+                                      double *u_last, double *cost);
+
 /*
  * Synthetic workload of the reference benchmark: random_qp(m, n, density, rng)
  * (benchmarks/bench_types.hpp:19-41) drawn `batch` times from ONE std::default_random_engine

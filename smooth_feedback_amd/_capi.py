@@ -52,6 +52,12 @@ class SfbMPCLayout(C.Structure):
     ]
 
 
+class SfbPIDGroup(C.Structure):
+    """sfb_pid_group (include/sfb.h)."""
+
+    _fields_ = [("nparts", C.c_int32), ("part_kind", C.c_void_p), ("part_dof", C.c_void_p)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -115,6 +121,15 @@ def _load():
     L.sfb_ekf_update_batch.argtypes = [i64, i32, i32, dp, dp, i32, dp, dp, dp, dp, vp]
     L.sfb_ekf_predict_update_batch.argtypes = [i64, i32, i32, dp, dp, i32, dp, i32, dp, dp, i32, dp, dp, dp, dp, vp]
     L.sfb_ekf_step_batch_host.argtypes = [i64, i32, i32, dp, dp, i32, dp, i32, dp, dp, i32, dp, dp, dp, dp]
+    grp, dbl = C.POINTER(SfbPIDGroup), C.c_double
+    L.sfb_pid_elem_doubles.argtypes = [grp]
+    L.sfb_pid_elem_doubles.restype = i64
+    L.sfb_pid_dof.argtypes = [grp]
+    L.sfb_pid_dof.restype = i64
+    L.sfb_pid_step_batch_host.argtypes = [grp, i64, dbl] + [dp] * 5 + [i32] + [dp] * 3 + [i32, dbl] + [dp] * 3
+    L.sfb_pid_step_batch.argtypes = L.sfb_pid_step_batch_host.argtypes + [vp]
+    L.sfb_pid_rollout_batch_host.argtypes = [grp, i64, dbl, dbl, i64] + [dp] * 4 + [i32] + [dp] * 3 + [i32, dbl] + [dp] * 5
+    L.sfb_pid_rollout_batch.argtypes = L.sfb_pid_rollout_batch_host.argtypes + [vp]
     lay = C.POINTER(SfbMPCLayout)
     L.sfb_mpc_record_doubles.argtypes = [lay, i32]
     L.sfb_mpc_record_doubles.restype = i64
