@@ -11,6 +11,7 @@
 #include <vector>
 
 #include <smooth_feedback_amd/asif.hpp>
+#include <smooth_feedback_amd/detail/device_arena.hpp>
 #include <smooth_feedback_amd/ekf.hpp>
 #include <smooth_feedback_amd/mpc.hpp>
 #include <smooth/feedback/mpc.hpp>  // the reference's include path and namespace (sfbx_test_mpc_api)
@@ -1459,4 +1460,40 @@ int sfbx_pid_host(int group, int64_t batch, int ncalls, const double * times, co
 {
   if (batch < 0 || ncalls < 0) return -1;
   return pid_dispatch(group, [&]<class G>() { pid_host<G>(batch, ncalls, times, x, v, gd, vd, ad, kp, kd, ki, windup, u_out, ie_out); });
+}
+
+int sfbx_arena_selftest(void)
+{
+  using smooth_feedback_amd::detail::DeviceArena;
+  struct Seven { double v[7]; };
+  double *d5, *d0, *d1;
+  Seven *g3;
+  uint32_t *it5;
+  int32_t *code3;
+  char *c3;
+  DeviceArena a;
+  a.add(&d5, 5); a.add(&g3, 3); a.add(&d0, 0); a.add(&it5, 5); a.add(&code3, 3); a.add(&c3, 3); a.add(&d1, 1);
+  const size_t want = 5 * 8 + 3 * 56 + 5 * 4 + 3 * 4 + 3 + 5 /* padding in front of d1 */ + 8;
+  if (!a.ok() || a.size() != 7 || a.bytes() != want) return 1;
+  alignas(16) static char mem[256];
+  if (want > sizeof mem || !a.bind(mem)) return 2;
+  if ((char *)(d1 + 1) != mem + a.bytes()) return 3;  // the total is the end of the last array
+  const char * p[]   = {(char *)d5, (char *)g3, (char *)it5, (char *)code3, c3, (char *)d1};
+  const size_t len[] = {40, 168, 20, 12, 3, 8}, al[] = {alignof(double), alignof(Seven), alignof(uint32_t), alignof(int32_t), 1, alignof(double)};
+  if (p[0] != mem) return 4;
+  for (int i = 0; i < 6; ++i) {
+    if ((uintptr_t)p[i] % al[i] != 0) return 5;                 // aligned to its type
+    if (i + 1 < 6 && p[i] + len[i] > p[i + 1]) return 6;        // disjoint, in declaration order
+  }
+  if ((char *)d0 != (char *)it5 || (uintptr_t)d0 % alignof(double) != 0) return 7;  // zero count: a valid address, no bytes
+  // past the capacity: reported, nothing recorded, nothing bound
+  DeviceArena b;
+  double * q[DeviceArena::kCapacity + 2];
+  for (auto & x : q) x = (double *)mem;
+  for (int i = 0; i < DeviceArena::kCapacity; ++i) b.add(&q[i], 1);
+  if (!b.ok() || b.size() != DeviceArena::kCapacity) return 8;
+  const size_t full = b.bytes();
+  if (b.add(&q[DeviceArena::kCapacity], 1) != -1 || b.ok() || b.size() != DeviceArena::kCapacity || b.bytes() != full) return 9;
+  if (b.bind(mem) || q[DeviceArena::kCapacity] != nullptr || q[DeviceArena::kCapacity + 1] != (double *)mem) return 10;
+  return 0;
 }

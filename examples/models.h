@@ -84,6 +84,8 @@ int sfbx_mpc_swarm_device_step(int variant, int K, double tf, int64_t batch, uin
 int sfbx_last_tick_seconds(double *out, int n);
 /* group identities for the tests: returns max abs error over a set of checks */
 double sfbx_lie_selftest(void);
+/* the carver of the staging buffers (detail/device_arena.hpp), no GPU: 0, or the number of the first check that fails */
+int sfbx_arena_selftest(void);
 /* EKF<G> front (include/smooth_feedback_amd/ekf.hpp) against the reference's own checks: PredictTimeCut
  * (tests/test_ekf.cpp:155-180), UpdateLinear (:50-103, R^3 / Ny 3) and an SE2 predict+update smoke.
  * Returns 0 and writes max errors: err[0] time-cut, err[1] linear update state, err[2] linear update cov. Needs a GPU. */

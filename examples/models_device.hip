@@ -557,9 +557,9 @@ int sfbx_pid_swarm_device(int64_t batch, double t0, double dt, int64_t steps, co
                           double * u_out, double * cost_out)
 {
   if (batch < 1 || steps < 0) return -1;
-  SE3 * dg0 = nullptr;
-  double * dw = nullptr;
-  int32_t * dkind = nullptr;
+  SE3 * dg0;
+  double * dw;
+  int32_t * dkind;
   int rc = 0;
   try {
     const size_t B = (size_t)batch;
@@ -576,12 +576,12 @@ int sfbx_pid_swarm_device(int64_t batch, double t0, double dt, int64_t steps, co
       return out;
     };
     const std::vector<SE3> hg0 = poses(g0);
-    detail::pid_hip_check(hipMalloc(reinterpret_cast<void **>(&dg0), B * sizeof(SE3)), "hipMalloc");
-    detail::pid_hip_check(hipMalloc(reinterpret_cast<void **>(&dw), B * 6 * sizeof(double)), "hipMalloc");
-    detail::pid_hip_check(hipMalloc(reinterpret_cast<void **>(&dkind), B * sizeof(int32_t)), "hipMalloc");
-    detail::pid_hip_check(hipMemcpy(dg0, hg0.data(), B * sizeof(SE3), hipMemcpyHostToDevice), "hipMemcpy");
-    detail::pid_hip_check(hipMemcpy(dw, w, B * 6 * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
-    detail::pid_hip_check(hipMemcpy(dkind, kind, B * sizeof(int32_t), hipMemcpyHostToDevice), "hipMemcpy");
+    detail::DeviceArena a;
+    a.add(&dg0, B); a.add(&dw, B * 6); a.add(&dkind, B);
+    const detail::DeviceBlock traj(a, "pid_device");
+    detail::hip_check(detail::upload(dg0, hg0.data(), B), "pid_device", "hipMemcpy");
+    detail::hip_check(detail::upload(dw, w, B * 6), "pid_device", "hipMemcpy");
+    detail::hip_check(detail::upload(dkind, kind, B), "pid_device", "hipMemcpy");
     PIDSwarmDevice<SE3, PidSwarmTraj> swarm(PidSwarmTraj{dg0, dw, dkind}, batch, PIDParams{windup});
     swarm.set_state(poses(x), tangents(v));
     swarm.set_gains(tangents(kp), tangents(kd), tangents(ki));
@@ -609,9 +609,6 @@ int sfbx_pid_swarm_device(int64_t batch, double t0, double dt, int64_t steps, co
     std::fprintf(stderr, "sfbx_pid_swarm_device: %s\n", e.what());
     rc = -2;
   }
-  (void)hipFree(dg0);
-  (void)hipFree(dw);
-  (void)hipFree(dkind);
   return rc;
 }
 

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "asif.hpp"
+#include "detail/device_arena.hpp"
 
 namespace smooth_feedback_amd {
 
@@ -54,10 +55,6 @@ __global__ void __launch_bounds__(256) asif_store_kernel(const int64_t B, const 
   for (int e = threadIdx.x; e < m; e += 256) wy[b * m + e] = y[b * m + e];
 }
 
-inline void hip_check(hipError_t e, const char * what)
-{
-  if (e != hipSuccess) throw std::runtime_error(std::string("asif_device: ") + what + ": " + hipGetErrorString(e));
-}
 }  // namespace detail
 
 /// ASIFSwarm (asif.hpp) with device-side assembly.  h(agent, t, x) -> Vec<nh>, bu(agent, t, x) -> U.
@@ -69,22 +66,17 @@ public:
   {
     n_ = U::Dof + 1;
     m_ = int(prm_.asif.K * prm_.nh + (std::size_t)prm_.ulim.rows + 1);
-    const size_t B = (size_t)B_, qpd = (size_t)n_ * n_ + n_ + (size_t)m_ * n_ + 2 * (size_t)m_, sol = 2 * ((size_t)n_ + m_);
-    const size_t ul = (size_t)prm_.ulim.rows * (U::Dof + 2);
-    detail::hip_check(hipMalloc(reinterpret_cast<void **>(&mem_), (B * (qpd + sol) + ul) * sizeof(double) + B * (sizeof(G) + sizeof(U) + 8)),
-                      "hipMalloc");
-    double * d = mem_;
-    P_ = d; d += B * n_ * n_;  q_ = d; d += B * n_;  A_ = d; d += B * m_ * n_;  l_ = d; d += B * m_;  u_ = d; d += B * m_;
-    x_ = d; d += B * n_;  y_ = d; d += B * m_;  wx_ = d; d += B * n_;  wy_ = d; d += B * m_;
-    ulA_ = d; d += (size_t)prm_.ulim.rows * U::Dof;  ull_ = d; d += prm_.ulim.rows;  ulu_ = d; d += prm_.ulim.rows;
-    g_     = reinterpret_cast<G *>(d);
-    udes_  = reinterpret_cast<U *>(g_ + B);
-    iter_  = reinterpret_cast<uint32_t *>(udes_ + B);
-    code_  = reinterpret_cast<int32_t *>(iter_ + B);
+    const size_t B = (size_t)B_, n = (size_t)n_, m = (size_t)m_, rows = (size_t)prm_.ulim.rows;
+    detail::DeviceArena a;
+    a.add(&P_, B * n * n); a.add(&q_, B * n); a.add(&A_, B * m * n); a.add(&l_, B * m); a.add(&u_, B * m);
+    a.add(&x_, B * n); a.add(&y_, B * m); a.add(&wx_, B * n); a.add(&wy_, B * m);
+    a.add(&ulA_, rows * U::Dof); a.add(&ull_, rows); a.add(&ulu_, rows);
+    a.add(&g_, B); a.add(&udes_, B); a.add(&iter_, B); a.add(&code_, B);
+    mem_ = detail::DeviceBlock(a, "asif_device");
     if (prm_.ulim.rows > 0) {
-      detail::hip_check(hipMemcpy(ulA_, prm_.ulim.A.data(), prm_.ulim.A.size() * 8, hipMemcpyHostToDevice), "hipMemcpy");
-      detail::hip_check(hipMemcpy(ull_, prm_.ulim.l.data(), prm_.ulim.l.size() * 8, hipMemcpyHostToDevice), "hipMemcpy");
-      detail::hip_check(hipMemcpy(ulu_, prm_.ulim.u.data(), prm_.ulim.u.size() * 8, hipMemcpyHostToDevice), "hipMemcpy");
+      check(detail::upload(ulA_, prm_.ulim.A.data(), prm_.ulim.A.size()), "hipMemcpy");
+      check(detail::upload(ull_, prm_.ulim.l.data(), prm_.ulim.l.size()), "hipMemcpy");
+      check(detail::upload(ulu_, prm_.ulim.u.data(), prm_.ulim.u.size()), "hipMemcpy");
     }
     const sfb_qp_params c = prm_.qp.to_c();
     int64_t wsb = 0;
@@ -96,23 +88,19 @@ public:
   }
   ASIFSwarmDevice(const ASIFSwarmDevice &)             = delete;
   ASIFSwarmDevice & operator=(const ASIFSwarmDevice &) = delete;
-  ~ASIFSwarmDevice()
-  {
-    sfb_workspace_destroy(ws_);
-    if (mem_) (void)hipFree(mem_);
-  }
+  ~ASIFSwarmDevice() { sfb_workspace_destroy(ws_); }
 
   /// one tick: the filtered inputs of all agents
   std::vector<U> operator()(const std::vector<G> & g, const std::vector<U> & u_des)
   {
     if ((int64_t)g.size() != B_ || (int64_t)u_des.size() != B_) throw std::invalid_argument("ASIFSwarmDevice: one state and input per agent");
-    detail::hip_check(hipMemcpy(g_, g.data(), (size_t)B_ * sizeof(G), hipMemcpyHostToDevice), "hipMemcpy(states)");
-    detail::hip_check(hipMemcpy(udes_, u_des.data(), (size_t)B_ * sizeof(U), hipMemcpyHostToDevice), "hipMemcpy(inputs)");
+    check(detail::upload(g_, g.data(), (size_t)B_), "hipMemcpy(states)");
+    check(detail::upload(udes_, u_des.data(), (size_t)B_), "hipMemcpy(inputs)");
     ASIFProblemView<G, U> proto{prm_.T, G::Identity(), U::Identity(), prm_.u_weight, prm_.ulim.rows, ulA_, ull_, ulu_, prm_.ulim.c,
                                 int(prm_.asif.K), prm_.asif.alpha, prm_.asif.dt, prm_.asif.relax_cost};
-    hipLaunchKernelGGL((detail::asif_assemble_kernel<G, U, Dyn, H, BU>), dim3((unsigned)((B_ + 63) / 64)), dim3(64), 0, nullptr, B_, proto,
+    hipLaunchKernelGGL((detail::asif_assemble_kernel<G, U, Dyn, H, BU>), detail::lane_grid(B_), dim3(64), 0, nullptr, B_, proto,
                        g_, udes_, f_, h_, bu_, n_, m_, P_, q_, A_, l_, u_);
-    detail::hip_check(hipGetLastError(), "asif_assemble_kernel");
+    check(hipGetLastError(), "asif_assemble_kernel");
     const sfb_qp_params c = prm_.qp.to_c();
     if (prm_.reduced_kkt)  // opt-in: the reduced-KKT route for tall problems (ASIFilterParams::reduced_kkt)
       sfb_check(sfb_qp_dense_tall_solve_batch(&c, B_, n_, m_, P_, q_, A_, l_, u_, have_warm_ ? wx_ : nullptr, have_warm_ ? wy_ : nullptr,
@@ -120,12 +108,12 @@ public:
     else
       sfb_check(sfb_qp_dense_solve_batch_ws(&c, B_, n_, m_, P_, q_, A_, l_, u_, have_warm_ ? wx_ : nullptr, have_warm_ ? wy_ : nullptr,
                                             x_, y_, nullptr, iter_, code_, ws_, nullptr));
-    if (!have_warm_) detail::hip_check(hipMemsetAsync(wx_, 0, (size_t)B_ * (n_ + m_) * 8, nullptr), "hipMemsetAsync");  // wx, wy adjacent
+    if (!have_warm_) check(hipMemsetAsync(wx_, 0, (size_t)B_ * (n_ + m_) * 8, nullptr), "hipMemsetAsync");  // wx, wy adjacent
     hipLaunchKernelGGL(detail::asif_store_kernel, dim3((unsigned)B_), dim3(256), 0, nullptr, B_, n_, m_, x_, y_, code_, wx_, wy_);
-    detail::hip_check(hipGetLastError(), "asif_store_kernel");
-    detail::hip_check(hipMemcpy(hx_.data(), x_, (size_t)B_ * n_ * 8, hipMemcpyDeviceToHost), "hipMemcpy(x)");
-    detail::hip_check(hipMemcpy(hcode_.data(), code_, (size_t)B_ * 4, hipMemcpyDeviceToHost), "hipMemcpy(code)");
-    detail::hip_check(hipMemcpy(hiter_.data(), iter_, (size_t)B_ * 4, hipMemcpyDeviceToHost), "hipMemcpy(iter)");
+    check(hipGetLastError(), "asif_store_kernel");
+    check(detail::download(hx_.data(), x_, (size_t)B_ * n_), "hipMemcpy(x)");
+    check(detail::download(hcode_.data(), code_, (size_t)B_), "hipMemcpy(code)");
+    check(detail::download(hiter_.data(), iter_, (size_t)B_), "hipMemcpy(iter)");
     have_warm_ = true;  // agents that never were Optimal keep the zero start (== no warm start)
     std::vector<U> out((size_t)B_);
     for (int64_t b = 0; b < B_; ++b) {
@@ -144,7 +132,7 @@ public:
   void copy_problem(double * P, double * q, double * A, double * l, double * u, double * x, double * y) const
   {
     const size_t B = (size_t)B_;
-    auto dl = [&](double * dst, const double * src, size_t cnt) { detail::hip_check(hipMemcpy(dst, src, cnt * 8, hipMemcpyDeviceToHost), "hipMemcpy"); };
+    auto dl = [](double * dst, const double * src, size_t cnt) { check(detail::download(dst, src, cnt), "hipMemcpy"); };
     dl(P, P_, B * n_ * n_); dl(q, q_, B * n_); dl(A, A_, B * m_ * n_); dl(l, l_, B * m_); dl(u, u_, B * m_); dl(x, x_, B * n_); dl(y, y_, B * m_);
   }
   /// the warm start the NEXT call will use (zeros before the first call)
@@ -155,18 +143,21 @@ public:
       std::fill(wy, wy + (size_t)B_ * m_, 0.0);
       return;
     }
-    detail::hip_check(hipMemcpy(wx, wx_, (size_t)B_ * n_ * 8, hipMemcpyDeviceToHost), "hipMemcpy");
-    detail::hip_check(hipMemcpy(wy, wy_, (size_t)B_ * m_ * 8, hipMemcpyDeviceToHost), "hipMemcpy");
+    check(detail::download(wx, wx_, (size_t)B_ * n_), "hipMemcpy");
+    check(detail::download(wy, wy_, (size_t)B_ * m_), "hipMemcpy");
   }
 
 private:
+  static void check(hipError_t e, const char * what) { detail::hip_check(e, "asif_device", what); }
+
   Dyn f_;
   H h_;
   BU bu_;
   int64_t B_;
   ASIFilterParams<U> prm_;
   int n_ = 0, m_ = 0;
-  double *mem_ = nullptr, *P_ = nullptr, *q_ = nullptr, *A_ = nullptr, *l_ = nullptr, *u_ = nullptr, *x_ = nullptr, *y_ = nullptr,
+  detail::DeviceBlock mem_;
+  double *P_ = nullptr, *q_ = nullptr, *A_ = nullptr, *l_ = nullptr, *u_ = nullptr, *x_ = nullptr, *y_ = nullptr,
          *wx_ = nullptr, *wy_ = nullptr, *ulA_ = nullptr, *ull_ = nullptr, *ulu_ = nullptr;
   G * g_        = nullptr;
   U * udes_     = nullptr;

@@ -22,6 +22,7 @@
 #include <string>
 #include <vector>
 
+#include "detail/device_arena.hpp"
 #include "detail/ekf_lane.hpp"
 #include "ekf.hpp"
 
@@ -138,10 +139,6 @@ __global__ void __launch_bounds__(64) ekf_step_fused_kernel(const int64_t B, con
   L::tile_store<NN>(Pg, item0, B, lds, lane);
 }
 
-inline void ekf_hip_check(hipError_t e, const char * what)
-{
-  if (e != hipSuccess) throw std::runtime_error(std::string("ekf_device: ") + what + ": " + hipGetErrorString(e));
-}
 }  // namespace detail
 
 template<class G, class Dyn, class Meas, int Ny, EKFStepper Stp = EKFStepper::Euler>
@@ -154,25 +151,20 @@ public:
   {
     if (B_ < 1) throw std::invalid_argument("EKFSwarmDevice: at least one filter");
     const size_t B = (size_t)B_, nn = (size_t)N * N;
-    const size_t doubles = B * (nn * (Stp == EKFStepper::RK4 ? 4 : 2) + (size_t)Ny * N + 2 * (size_t)Ny + N) + nn + (size_t)Ny * Ny + 2;
-    detail::ekf_hip_check(hipMalloc(reinterpret_cast<void **>(&mem_), doubles * 8 + B * (sizeof(G) + 4) + 64), "hipMalloc");
-    double * d = mem_;
-    P_ = d; d += B * nn;  A_ = d; d += B * nn;
-    if constexpr (Stp == EKFStepper::RK4) { Am_ = d; d += B * nn; Ae_ = d; d += B * nn; }
-    H_ = d; d += B * Ny * N;  y_ = d; d += B * Ny;  r_ = d; d += B * Ny;  delta_ = d; d += B * N;
-    Q_ = d; d += nn;  R_ = d; d += Ny * Ny;  dt_ = d; d += 2;
-    g_    = reinterpret_cast<G *>(d);
-    info_ = reinterpret_cast<int32_t *>(g_ + B);
+    constexpr size_t stage = Stp == EKFStepper::RK4 ? 1 : 0;  // the stage matrices of RK4 only
+    detail::DeviceArena a;
+    a.add(&P_, B * nn); a.add(&A_, B * nn); a.add(&Am_, stage * B * nn); a.add(&Ae_, stage * B * nn);
+    a.add(&H_, B * Ny * N); a.add(&y_, B * Ny); a.add(&r_, B * Ny); a.add(&delta_, B * N);
+    a.add(&Q_, nn); a.add(&R_, (size_t)Ny * Ny); a.add(&dt_, 2);
+    a.add(&g_, B); a.add(&info_, B);
+    mem_ = detail::DeviceBlock(a, "ekf_device");
+    if constexpr (Stp != EKFStepper::RK4) Am_ = Ae_ = nullptr;
     std::vector<G> g0(B, G::Identity());  // EKF's defaults: identity estimate, identity covariance (ekf.hpp:141-144)
     std::vector<CovT> P0(B, CovT::Identity());
     reset(g0, P0);
   }
   EKFSwarmDevice(const EKFSwarmDevice &)             = delete;
   EKFSwarmDevice & operator=(const EKFSwarmDevice &) = delete;
-  ~EKFSwarmDevice()
-  {
-    if (mem_) (void)hipFree(mem_);
-  }
 
   int64_t size() const { return B_; }
 
@@ -205,19 +197,13 @@ public:
   /// the same on arrays of size() entries (a shard of a larger swarm: multi_device.hpp)
   void reset(const G * g, const CovT * P)
   {
-    detail::ekf_hip_check(hipMemcpy(g_, g, (size_t)B_ * sizeof(G), hipMemcpyHostToDevice), "hipMemcpy(states)");
-    detail::ekf_hip_check(hipMemcpy(P_, P, (size_t)B_ * sizeof(CovT), hipMemcpyHostToDevice), "hipMemcpy(covariances)");
+    check(detail::upload(g_, g, (size_t)B_), "hipMemcpy(states)");
+    check(detail::upload(P_, P->a.data(), (size_t)B_ * N * N), "hipMemcpy(covariances)");
   }
-  void estimates(G * out) const { detail::ekf_hip_check(hipMemcpy(out, g_, (size_t)B_ * sizeof(G), hipMemcpyDeviceToHost), "hipMemcpy(states)"); }
-  void covariances(CovT * out) const
-  {
-    detail::ekf_hip_check(hipMemcpy(out, P_, (size_t)B_ * sizeof(CovT), hipMemcpyDeviceToHost), "hipMemcpy(covariances)");
-  }
-  void update_info(int32_t * out) const { detail::ekf_hip_check(hipMemcpy(out, info_, (size_t)B_ * 4, hipMemcpyDeviceToHost), "hipMemcpy(info)"); }
-  void upload_measurements(const Vec<Ny> * y)
-  {
-    detail::ekf_hip_check(hipMemcpy(y_, y, (size_t)B_ * sizeof(Vec<Ny>), hipMemcpyHostToDevice), "hipMemcpy(measurements)");
-  }
+  void estimates(G * out) const { check(detail::download(out, g_, (size_t)B_), "hipMemcpy(states)"); }
+  void covariances(CovT * out) const { check(detail::download(out->a.data(), P_, (size_t)B_ * N * N), "hipMemcpy(covariances)"); }
+  void update_info(int32_t * out) const { check(detail::download(out, info_, (size_t)B_), "hipMemcpy(info)"); }
+  void upload_measurements(const Vec<Ny> * y) { check(detail::upload(y_, y->data(), (size_t)B_ * Ny), "hipMemcpy(measurements)"); }
   /// resident buffers, for callers that produce measurements or consume estimates on the device
   G * device_estimates() { return g_; }
   double * device_covariances() { return P_; }
@@ -267,9 +253,9 @@ public:
       predict(Q, tau);
       update_resident(R);
     } else if (one_launch_) {
-      hipLaunchKernelGGL((detail::ekf_step_fused_kernel<G, Dyn, Meas, Ny>), grid(), dim3(64), 0, nullptr, B_, f_, h_, 0.0, tau, Q, R, g_, y_, P_,
-                         info_);
-      detail::ekf_hip_check(hipGetLastError(), "ekf_step_fused_kernel");
+      hipLaunchKernelGGL((detail::ekf_step_fused_kernel<G, Dyn, Meas, Ny>), detail::lane_grid(B_), dim3(64), 0, nullptr, B_, f_, h_, 0.0, tau, Q,
+                         R, g_, y_, P_, info_);
+      check(hipGetLastError(), "ekf_step_fused_kernel");
     } else {
       upload_small(Q_, Q.a.data(), (size_t)N * N);
       upload_small(R_, R.a.data(), (size_t)Ny * Ny);
@@ -283,31 +269,28 @@ public:
 
 private:
   static void sfb_check_(sfb_status st) { detail::ekf_check(st); }
-  void upload_small(double * dst, const double * src, size_t n)
-  {
-    detail::ekf_hip_check(hipMemcpy(dst, src, n * 8, hipMemcpyHostToDevice), "hipMemcpy");
-  }
+  static void check(hipError_t e, const char * what) { detail::hip_check(e, "ekf_device", what); }
+  void upload_small(double * dst, const double * src, size_t n) { check(detail::upload(dst, src, n), "hipMemcpy"); }
   void upload_measurements(const std::vector<Vec<Ny>> & y)
   {
     if ((int64_t)y.size() != B_) throw std::invalid_argument("EKFSwarmDevice: one measurement per filter");
     upload_measurements(y.data());
   }
-  dim3 grid() const { return dim3((unsigned)((B_ + 63) / 64)); }
   void linearise_dyn(double t, double h)
   {
-    hipLaunchKernelGGL((detail::ekf_predict_lin_kernel<G, Dyn, Stp == EKFStepper::RK4>), grid(), dim3(64), 0, nullptr, B_, f_, t, h, g_, A_, Am_,
-                       Ae_);
-    detail::ekf_hip_check(hipGetLastError(), "ekf_predict_lin_kernel");
+    hipLaunchKernelGGL((detail::ekf_predict_lin_kernel<G, Dyn, Stp == EKFStepper::RK4>), detail::lane_grid(B_), dim3(64), 0, nullptr, B_, f_, t, h,
+                       g_, A_, Am_, Ae_);
+    check(hipGetLastError(), "ekf_predict_lin_kernel");
   }
   void linearise_meas()
   {
-    hipLaunchKernelGGL((detail::ekf_update_lin_kernel<G, Meas, Ny>), grid(), dim3(64), 0, nullptr, B_, h_, g_, y_, H_, r_);
-    detail::ekf_hip_check(hipGetLastError(), "ekf_update_lin_kernel");
+    hipLaunchKernelGGL((detail::ekf_update_lin_kernel<G, Meas, Ny>), detail::lane_grid(B_), dim3(64), 0, nullptr, B_, h_, g_, y_, H_, r_);
+    check(hipGetLastError(), "ekf_update_lin_kernel");
   }
   void apply()
   {
-    hipLaunchKernelGGL((detail::ekf_apply_kernel<G>), grid(), dim3(64), 0, nullptr, B_, g_, delta_);
-    detail::ekf_hip_check(hipGetLastError(), "ekf_apply_kernel");
+    hipLaunchKernelGGL((detail::ekf_apply_kernel<G>), detail::lane_grid(B_), dim3(64), 0, nullptr, B_, g_, delta_);
+    check(hipGetLastError(), "ekf_apply_kernel");
   }
   void substep(double t, double h)
   {
@@ -323,7 +306,7 @@ private:
   Meas h_;
   int64_t B_;
   bool one_launch_ = true;
-  double * mem_ = nullptr;
+  detail::DeviceBlock mem_;
   double *P_ = nullptr, *A_ = nullptr, *Am_ = nullptr, *Ae_ = nullptr, *H_ = nullptr, *y_ = nullptr, *r_ = nullptr, *delta_ = nullptr;
   double *Q_ = nullptr, *R_ = nullptr, *dt_ = nullptr;
   G * g_          = nullptr;

@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "detail/device_arena.hpp"
 #include "mpc.hpp"
 
 namespace smooth_feedback_amd {
@@ -105,10 +106,6 @@ __global__ void __launch_bounds__(64) mpc_linearise_kernel(const int64_t B, cons
   if (bad) atomicOr(misfit, 1);
 }
 
-inline void mpc_hip_check(hipError_t e, const char * what)
-{
-  if (e != hipSuccess) throw std::runtime_error(std::string("mpc_device: ") + what + ": " + hipGetErrorString(e));
-}
 }  // namespace detail
 
 /// MPCSwarmDevice with the linearisation on the GPU.  `proto` is the host MPC object of the same model (structure probing,
@@ -140,12 +137,10 @@ public:
     const int Nn = mpc_.N();
     std::vector<double> tau((size_t)Nn + 1);
     for (int i = 0; i <= Nn; ++i) tau[(size_t)i] = mpc_.mesh().node(i);
-    detail::mpc_hip_check(hipMalloc(reinterpret_cast<void **>(&dmem_), ((size_t)Nn + 1 + (size_t)B_) * 8 + (size_t)B_ * sizeof(X) + 16), "hipMalloc");
-    dtau_    = reinterpret_cast<double *>(dmem_);
-    dt_      = dtau_ + Nn + 1;
-    dx_      = reinterpret_cast<X *>(dt_ + B_);
-    dmisfit_ = reinterpret_cast<int *>(dx_ + B_);
-    detail::mpc_hip_check(hipMemcpy(dtau_, tau.data(), tau.size() * 8, hipMemcpyHostToDevice), "hipMemcpy(tau)");
+    detail::DeviceArena a;
+    a.add(&dtau_, tau.size()); a.add(&dt_, (size_t)B_); a.add(&dx_, (size_t)B_); a.add(&dmisfit_, 1);
+    dmem_ = detail::DeviceBlock(a, "mpc_device");
+    check(detail::upload(dtau_, tau.data(), tau.size()), "hipMemcpy(tau)");
     build_map();
     du0_.resize((size_t)B_ * Nu);
     iter_.resize((size_t)B_);
@@ -157,7 +152,6 @@ public:
   {
     sfb_mpc_swarm_destroy(swarm_);
     mpc_.solver().unpin_plan();
-    if (dmem_) (void)hipFree(dmem_);
   }
 
   void reset_warmstart() { sfb_check(sfb_mpc_swarm_reset_warmstart(swarm_)); }
@@ -173,11 +167,11 @@ public:
   /// the same on arrays of size() entries (a shard of a larger swarm: multi_device.hpp)
   void step(const double * t, const X * xs, U * us, QPSolutionStatus * codes)
   {
-    detail::mpc_hip_check(hipMemcpy(dt_, t, (size_t)B_ * 8, hipMemcpyHostToDevice), "hipMemcpy(t)");
-    detail::mpc_hip_check(hipMemcpy(dx_, xs, (size_t)B_ * sizeof(X), hipMemcpyHostToDevice), "hipMemcpy(x)");
+    check(detail::upload(dt_, t, (size_t)B_), "hipMemcpy(t)");
+    check(detail::upload(dx_, xs, (size_t)B_), "hipMemcpy(x)");
     linearise();
     int misfit = 0;
-    detail::mpc_hip_check(hipMemcpy(&misfit, dmisfit_, sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(flag)");
+    check(detail::download(&misfit, dmisfit_, 1), "hipMemcpy(flag)");
     if (misfit && packed_) {
       // a linearisation has a non-zero where the probe saw none: unpacked records from now on (same results; warm
       // starts and solver memory of the swarm are untouched), and this tick's records once more
@@ -201,10 +195,11 @@ public:
   /// the records of the last tick (device -> host), [agents][record_doubles()]
   void copy_records(double * out) const
   {
-    detail::mpc_hip_check(hipMemcpy(out, drec_, (size_t)B_ * (size_t)map_.rec_doubles * 8, hipMemcpyDeviceToHost), "hipMemcpy(records)");
+    check(detail::download(out, drec_, (size_t)B_ * (size_t)map_.rec_doubles), "hipMemcpy(records)");
   }
 
 private:
+  static void check(hipError_t e, const char * what) { detail::hip_check(e, "mpc_device", what); }
   void build_map()
   {
     const int Nn = mpc_.N();
@@ -237,11 +232,11 @@ private:
   }
   void linearise()
   {
-    detail::mpc_hip_check(hipMemsetAsync(dmisfit_, 0, sizeof(int), nullptr), "hipMemsetAsync");
+    check(hipMemsetAsync(dmisfit_, 0, sizeof(int), nullptr), "hipMemsetAsync");
     const int64_t threads = B_ * (map_.N + 1);
-    hipLaunchKernelGGL((detail::mpc_linearise_kernel<X, U, Ncr, Model>), dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, nullptr, B_, map_,
+    hipLaunchKernelGGL((detail::mpc_linearise_kernel<X, U, Ncr, Model>), detail::lane_grid(threads), dim3(64), 0, nullptr, B_, map_,
                        model_, dtau_, dt_, dx_, drec_, dmisfit_);
-    detail::mpc_hip_check(hipGetLastError(), "mpc_linearise_kernel");
+    check(hipGetLastError(), "mpc_linearise_kernel");
   }
 
   MPCT & mpc_;
@@ -252,7 +247,7 @@ private:
   std::unique_ptr<typename MPCT::DeviceLayout> layout_;
   sfb_mpc_swarm * swarm_ = nullptr;
   Map map_{};
-  char * dmem_   = nullptr;
+  detail::DeviceBlock dmem_;
   double * dtau_ = nullptr, *dt_ = nullptr, *drec_ = nullptr;
   X * dx_        = nullptr;
   int * dmisfit_ = nullptr;

@@ -258,7 +258,7 @@ public:
     cut_.for_each([&](size_t i, const DeviceShards::Shard & s) {
       part_[i]->upload_measurements(y.data() + s.first);
       part_[i]->step_resident(Q, tau, R);
-      detail::ekf_hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");  // (asynchronous launch: the tick is over -- and its faults are reported -- when every shard's is)
+      detail::hip_check(hipDeviceSynchronize(), "ekf_device", "hipDeviceSynchronize");  // (asynchronous launch: the tick is over -- and its faults are reported -- when every shard's is)
     });
   }
 

@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "detail/device_arena.hpp"
 #include "pid.hpp"
 
 namespace smooth_feedback_amd {
@@ -88,10 +89,6 @@ __global__ void __launch_bounds__(64) pid_swarm_rollout_kernel(const int64_t B, 
   m.cost[b]   = cost;
 }
 
-inline void pid_hip_check(hipError_t e, const char * what)
-{
-  if (e != hipSuccess) throw std::runtime_error(std::string("pid_device: ") + what + ": " + hipGetErrorString(e));
-}
 }  // namespace detail
 
 template<class G, class Traj>
@@ -106,11 +103,10 @@ public:
     if (B_ < 1) throw std::invalid_argument("PIDSwarmDevice: at least one agent");
     if (!(prm_.windup_limit >= 0.0)) throw std::invalid_argument("PIDSwarmDevice: windup_limit must be >= 0");
     const size_t B = (size_t)B_;
-    detail::pid_hip_check(hipMalloc(reinterpret_cast<void **>(&mem_), B * (6 * N + 2) * sizeof(double) + B * sizeof(G) + 64), "hipMalloc");
-    double * d = mem_;
-    m_.v = d; d += B * N;  m_.i_err = d; d += B * N;  m_.kp = d; d += B * N;  m_.kd = d; d += B * N;  m_.ki = d; d += B * N;
-    m_.u = d; d += B * N;  m_.t_last = d; d += B;  m_.cost = d; d += B;
-    m_.x = reinterpret_cast<G *>(d);
+    detail::DeviceArena a;
+    a.add(&m_.v, B * N); a.add(&m_.i_err, B * N); a.add(&m_.kp, B * N); a.add(&m_.kd, B * N); a.add(&m_.ki, B * N);
+    a.add(&m_.u, B * N); a.add(&m_.t_last, B); a.add(&m_.cost, B); a.add(&m_.x, B);
+    mem_ = detail::DeviceBlock(a, "pid_device");
     Tangent one{}, zero{};
     one.fill(1.0);
     set_state(std::vector<G>(B, G::Identity()), std::vector<Tangent>(B, zero));
@@ -119,10 +115,6 @@ public:
   }
   PIDSwarmDevice(const PIDSwarmDevice &)             = delete;
   PIDSwarmDevice & operator=(const PIDSwarmDevice &) = delete;
-  ~PIDSwarmDevice()
-  {
-    if (mem_) (void)hipFree(mem_);
-  }
 
   int64_t size() const { return B_; }
 
@@ -130,7 +122,7 @@ public:
   {
     need(x.size(), "state");
     need(v.size(), "velocity");
-    detail::pid_hip_check(hipMemcpy(m_.x, x.data(), (size_t)B_ * sizeof(G), hipMemcpyHostToDevice), "hipMemcpy(states)");
+    check(detail::upload(m_.x, x.data(), (size_t)B_), "hipMemcpy(states)");
     up(m_.v, v);
   }
   /// gains per agent, or one set for the whole swarm (set_kp / set_kd / set_ki of every controller)
@@ -149,7 +141,7 @@ public:
   {
     need(t_last.size(), "t_last");
     up(m_.i_err, i_err);
-    detail::pid_hip_check(hipMemcpy(m_.t_last, t_last.data(), (size_t)B_ * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(t_last)");
+    check(detail::upload(m_.t_last, t_last.data(), (size_t)B_), "hipMemcpy(t_last)");
   }
   void reset_integral() { up(m_.i_err, std::vector<Tangent>((size_t)B_, Tangent{})); }
   /// fresh controllers: zero integral, no last call
@@ -160,8 +152,8 @@ public:
   /// PID::operator() at time t for every agent, on the resident states: writes inputs()
   void step(double t)
   {
-    hipLaunchKernelGGL((detail::pid_swarm_step_kernel<G, Traj>), grid(), dim3(64), 0, nullptr, B_, traj_, t, prm_.windup_limit, m_);
-    detail::pid_hip_check(hipGetLastError(), "pid_swarm_step_kernel");
+    hipLaunchKernelGGL((detail::pid_swarm_step_kernel<G, Traj>), detail::lane_grid(B_), dim3(64), 0, nullptr, B_, traj_, t, prm_.windup_limit, m_);
+    check(hipGetLastError(), "pid_swarm_step_kernel");
   }
   /// `steps` closed-loop ticks of length dt from t0 (tick k at t0 + k dt: law, clamp, double-integrator step) in one launch:
   /// updates the states, velocities and the controllers' state, writes inputs() (last tick) and costs()
@@ -169,16 +161,16 @@ public:
   {
     if (steps < 0 || !(dt == dt) || dt - dt != 0.0) throw std::invalid_argument("PIDSwarmDevice: steps >= 0 and a finite dt");
     if (steps == 0) return;
-    hipLaunchKernelGGL((detail::pid_swarm_rollout_kernel<G, Traj>), grid(), dim3(64), 0, nullptr, B_, traj_, t0, dt, steps, prm_.windup_limit,
+    hipLaunchKernelGGL((detail::pid_swarm_rollout_kernel<G, Traj>), detail::lane_grid(B_), dim3(64), 0, nullptr, B_, traj_, t0, dt, steps, prm_.windup_limit,
                        u_max_.has_value(), u_max_.value_or(Tangent{}), m_);
-    detail::pid_hip_check(hipGetLastError(), "pid_swarm_rollout_kernel");
+    check(hipGetLastError(), "pid_swarm_rollout_kernel");
   }
 
   /// device -> host (synchronises with the launches above: null stream)
   std::vector<G> states() const
   {
     std::vector<G> out((size_t)B_);
-    detail::pid_hip_check(hipMemcpy(out.data(), m_.x, (size_t)B_ * sizeof(G), hipMemcpyDeviceToHost), "hipMemcpy(states)");
+    check(detail::download(out.data(), m_.x, (size_t)B_), "hipMemcpy(states)");
     return out;
   }
   std::vector<Tangent> velocities() const { return down(m_.v); }
@@ -187,7 +179,7 @@ public:
   std::vector<double> costs() const
   {
     std::vector<double> out((size_t)B_);
-    detail::pid_hip_check(hipMemcpy(out.data(), m_.cost, (size_t)B_ * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(costs)");
+    check(detail::download(out.data(), m_.cost, (size_t)B_), "hipMemcpy(costs)");
     return out;
   }
   /// resident buffers, for callers that produce states or consume inputs on the device
@@ -204,21 +196,21 @@ private:
   {
     need(src.size(), "tangent");
     static_assert(sizeof(Tangent) == N * sizeof(double));
-    detail::pid_hip_check(hipMemcpy(dst, src.data(), (size_t)B_ * sizeof(Tangent), hipMemcpyHostToDevice), "hipMemcpy");
+    check(detail::upload(dst, src.data()->data(), (size_t)B_ * N), "hipMemcpy");
   }
   std::vector<Tangent> down(const double * src) const
   {
     std::vector<Tangent> out((size_t)B_);
-    detail::pid_hip_check(hipMemcpy(out.data(), src, (size_t)B_ * sizeof(Tangent), hipMemcpyDeviceToHost), "hipMemcpy");
+    check(detail::download(out.data()->data(), src, (size_t)B_ * N), "hipMemcpy");
     return out;
   }
-  dim3 grid() const { return dim3((unsigned)((B_ + 63) / 64)); }
+  static void check(hipError_t e, const char * what) { detail::hip_check(e, "pid_device", what); }
 
   Traj traj_;
   int64_t B_;
   PIDParams prm_;
   std::optional<Tangent> u_max_;
-  double * mem_ = nullptr;
+  detail::DeviceBlock mem_;
   detail::PIDSwarmBuffers<G> m_{};
 };
 

@@ -811,14 +811,22 @@ static sfb_status dense_host_impl(const sfb_qp_params *prm, int64_t batch, int n
   if (st != SFB_OK) return st;
   if (batch == 0) return SFB_OK;
 
-  const size_t B = (size_t)batch, N = (size_t)n, M = (size_t)m;
-  const size_t in_d  = B * (N * N + N + M * N + 2 * M) + (warm_x ? B * (N + M) : 0);
-  const size_t out_d = B * (N + M + 1);
+  const size_t B = (size_t)batch, N = (size_t)n, M = (size_t)m, W = warm_x ? B : 0;
+  using S = sfb::Staging;
+  S s;
+  double *dP, *dq, *dA, *dl, *du, *dwx, *dwy, *dx, *dy, *dobj;
+  uint32_t *dit;
+  int32_t *dcode;
+  s.add(&dP, B * N * N, S::In, P); s.add(&dq, B * N, S::In, q); s.add(&dA, B * M * N, S::In, A);
+  s.add(&dl, B * M, S::In, l); s.add(&du, B * M, S::In, u);
+  s.add(&dwx, W * N, S::In, warm_x); s.add(&dwy, W * M, S::In, warm_y);
+  s.add(&dx, B * N, S::Out, x); s.add(&dy, B * M, S::Out, y); s.add(&dobj, B, S::Out, obj);
+  s.add(&dit, B, S::Out, iter); s.add(&dcode, B, S::Out, code);
   // Staging memory of the host-pointer entry point: ONE buffer per device is kept between calls (ASIFilter solves one
   // small QP per tick through here, and a hipMalloc / hipFree pair per call would dominate its latency).  The lock is
   // held only while the buffer is taken or handed back: concurrent callers do not serialise -- one of them gets the
   // kept buffer, the others allocate their own for the call.  sfb_host_staging_trim() frees what is kept.
-  const size_t bytes = (in_d + out_d) * sizeof(double) + B * (sizeof(uint32_t) + sizeof(int32_t));
+  const size_t bytes = s.bytes();
   int devid          = 0;
   hipError_t e       = hipGetDevice(&devid);
   if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
@@ -835,55 +843,23 @@ static sfb_status dense_host_impl(const sfb_qp_params *prm, int64_t batch, int n
     HostStage &s;
     ~Return() { host_stage_give(dev, s); }
   } ret{devid, mine};
-  char *dev = mine.mem;
+  if (!s.bind(mine.mem)) return fail(SFB_ERR_UNSUPPORTED, "more staged arrays than the table holds");
+  if (!warm_x) dwx = dwy = nullptr;
 
-  double *dP = reinterpret_cast<double *>(dev);
-  double *dq = dP + B * N * N;
-  double *dA = dq + B * N;
-  double *dl = dA + B * M * N;
-  double *du = dl + B * M;
-  double *dwx = du + B * M, *dwy = nullptr;
-  double *dx = dwx;
-  if (warm_x) {
-    dwy = dwx + B * N;
-    dx  = dwy + B * M;
-  } else {
-    dwx = nullptr;
-  }
-  double *dy     = dx + B * N;
-  double *dobj   = dy + B * M;
-  uint32_t *dit  = reinterpret_cast<uint32_t *>(dobj + B);
-  int32_t *dcode = reinterpret_cast<int32_t *>(dit + B);
-
-  auto H2D = [&](void *d, const void *h, size_t nb) { return hipMemcpy(d, h, nb, hipMemcpyHostToDevice); };
-  auto D2H = [&](void *h, const void *d, size_t nb) { return hipMemcpy(h, d, nb, hipMemcpyDeviceToHost); };
   st = SFB_OK;
   using clk = std::chrono::steady_clock;
   auto ms   = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
   const auto tv0 = clk::now();
   auto tv1 = tv0, tv2 = tv0;
-  do {
-    if ((e = H2D(dP, P, B * N * N * 8)) != hipSuccess) break;
-    if ((e = H2D(dq, q, B * N * 8)) != hipSuccess) break;
-    if ((e = H2D(dA, A, B * M * N * 8)) != hipSuccess) break;
-    if ((e = H2D(dl, l, B * M * 8)) != hipSuccess) break;
-    if ((e = H2D(du, u, B * M * 8)) != hipSuccess) break;
-    if (warm_x) {
-      if ((e = H2D(dwx, warm_x, B * N * 8)) != hipSuccess) break;
-      if ((e = H2D(dwy, warm_y, B * M * 8)) != hipSuccess) break;
-    }
+  if ((e = s.upload()) == hipSuccess) {
     tv1 = clk::now();
     st = (tall ? sfb_qp_dense_tall_solve_batch : sfb_qp_dense_solve_batch)(prm, batch, n, m, dP, dq, dA, dl, du, dwx, dwy, dx, dy, dobj, dit,
                                                                            dcode, nullptr);
-    if (st != SFB_OK) break;
-    if ((e = hipDeviceSynchronize()) != hipSuccess) break;
-    tv2 = clk::now();
-    if ((e = D2H(x, dx, B * N * 8)) != hipSuccess) break;
-    if ((e = D2H(y, dy, B * M * 8)) != hipSuccess) break;
-    if (obj && (e = D2H(obj, dobj, B * 8)) != hipSuccess) break;
-    if (iter && (e = D2H(iter, dit, B * 4)) != hipSuccess) break;
-    if ((e = D2H(code, dcode, B * 4)) != hipSuccess) break;
-  } while (false);
+    if (st == SFB_OK && (e = hipDeviceSynchronize()) == hipSuccess) {
+      tv2 = clk::now();
+      e   = s.download();
+    }
+  }
   if (e != hipSuccess) st = hip_fail(e, "sfb_qp_dense_solve_batch_host");
   const auto tv3 = clk::now();
   if (st == SFB_OK && prm->verbose && batch == 1 && !tall) {  // (inputs still on the device)
@@ -940,46 +916,34 @@ sfb_status sfb_qp_dense_solve_batch_host_phases(const sfb_qp_params *prm, int64_
   st = require_device();
   if (st != SFB_OK) return st;
   if (batch == 0) return SFB_OK;
-  const size_t B = (size_t)batch, N = (size_t)n, M = (size_t)m, TR = B * (size_t)trace_rows * 5, PH = phase_us ? B * 16 : 0;
-  const size_t doubles = B * (N * N + N + M * N + 2 * M) + (warm_x ? B * (N + M) : 0) + B * (N + M + 1) + TR + PH;
-  char *mem    = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&mem), doubles * 8 + B * 8);
-  if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-  double *dP = reinterpret_cast<double *>(mem), *dq = dP + B * N * N, *dA = dq + B * N, *dl = dA + B * M * N, *du = dl + B * M, *nx = du + B * M;
-  double *dwx = nullptr, *dwy = nullptr;
-  if (warm_x) { dwx = nx; dwy = dwx + B * N; nx = dwy + B * M; }
-  double *dx = nx, *dy = dx + B * N, *dobj = dy + B * M, *dtr = dobj + B;
-  double *dph    = dtr + TR;
-  uint32_t *dit  = reinterpret_cast<uint32_t *>(dph + PH);
-  int32_t *dcode = reinterpret_cast<int32_t *>(dit + B);
-  auto H2D = [&](void *d, const void *h, size_t nb) { return hipMemcpy(d, h, nb, hipMemcpyHostToDevice); };
-  auto D2H = [&](void *h, const void *d, size_t nb) { return hipMemcpy(h, d, nb, hipMemcpyDeviceToHost); };
-  do {
-    if ((e = H2D(dP, P, B * N * N * 8)) != hipSuccess) break;
-    if ((e = H2D(dq, q, B * N * 8)) != hipSuccess) break;
-    if ((e = H2D(dA, A, B * M * N * 8)) != hipSuccess) break;
-    if ((e = H2D(dl, l, B * M * 8)) != hipSuccess) break;
-    if ((e = H2D(du, u, B * M * 8)) != hipSuccess) break;
-    if (warm_x && ((e = H2D(dwx, warm_x, B * N * 8)) != hipSuccess || (e = H2D(dwy, warm_y, B * M * 8)) != hipSuccess)) break;
-    if (TR) {  // unused rows keep ITER = -1
-      std::vector<double> init(TR, 0.0);
-      for (size_t r = 0; r < TR; r += 5) init[r] = -1.0;
-      if ((e = H2D(dtr, init.data(), TR * 8)) != hipSuccess) break;
-    }
-    if (PH && (e = hipMemset(dph, 0, PH * 8)) != hipSuccess) break;
+  const size_t B = (size_t)batch, N = (size_t)n, M = (size_t)m, W = warm_x ? B : 0, TR = B * (size_t)trace_rows * 5, PH = phase_us ? B * 16 : 0;
+  using S = sfb::Staging;
+  S s;
+  double *dP, *dq, *dA, *dl, *du, *dwx, *dwy, *dx, *dy, *dobj, *dtr, *dph;
+  uint32_t *dit;
+  int32_t *dcode;
+  s.add(&dP, B * N * N, S::In, P); s.add(&dq, B * N, S::In, q); s.add(&dA, B * M * N, S::In, A);
+  s.add(&dl, B * M, S::In, l); s.add(&du, B * M, S::In, u);
+  s.add(&dwx, W * N, S::In, warm_x); s.add(&dwy, W * M, S::In, warm_y);
+  s.add(&dx, B * N, S::Out, x); s.add(&dy, B * M, S::Out, y); s.add(&dobj, B, S::Out, obj);
+  s.add(&dtr, TR, S::Out, trace); s.add(&dph, PH);  // (16 doubles of phase scratch per item, 6 of them come down)
+  s.add(&dit, B, S::Out, iter); s.add(&dcode, B, S::Out, code);
+  sfb::DeviceBlock blk;
+  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
+  if (!warm_x) dwx = dwy = nullptr;
+  hipError_t e = s.upload();
+  if (e == hipSuccess && TR) {  // unused rows keep ITER = -1
+    std::vector<double> init(TR, 0.0);
+    for (size_t r = 0; r < TR; r += 5) init[r] = -1.0;
+    e = sfb::upload(dtr, init.data(), TR);
+  }
+  if (e == hipSuccess && PH) e = hipMemset(dph, 0, PH * 8);
+  if (e == hipSuccess) {
     st = sfb_qp_dense_solve_batch_phases(prm, batch, n, m, dP, dq, dA, dl, du, dwx, dwy, dx, dy, dobj, dit, dcode, TR ? dtr : nullptr, trace_rows,
                                          PH ? dph : nullptr, nullptr);
-    if (st != SFB_OK) break;
-    if ((e = hipDeviceSynchronize()) != hipSuccess) break;
-    if ((e = D2H(x, dx, B * N * 8)) != hipSuccess) break;
-    if ((e = D2H(y, dy, B * M * 8)) != hipSuccess) break;
-    if (obj && (e = D2H(obj, dobj, B * 8)) != hipSuccess) break;
-    if (iter && (e = D2H(iter, dit, B * 4)) != hipSuccess) break;
-    if ((e = D2H(code, dcode, B * 4)) != hipSuccess) break;
-    if (TR && (e = D2H(trace, dtr, TR * 8)) != hipSuccess) break;
-    if (PH && (e = D2H(phase_us, dph, B * 6 * 8)) != hipSuccess) break;
-  } while (false);
-  (void)hipFree(mem);
+    if (st == SFB_OK && (e = hipDeviceSynchronize()) == hipSuccess && (e = s.download()) == hipSuccess && PH)
+      e = sfb::download(phase_us, dph, B * 6);
+  }
   if (e != hipSuccess) return hip_fail(e, "sfb_qp_dense_solve_batch_host_trace");
   return st;
 }

@@ -4,9 +4,11 @@
 
 #include <functional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/sfb.h"
+#include "../../include/smooth_feedback_amd/detail/device_arena.hpp"
 #include "qp_dense_kernel.h"
 
 namespace sfb {
@@ -32,6 +34,50 @@ int verbose_table_rows(const sfb_qp_params *prm);
 // this thread's sfb_last_error).
 std::vector<int> device_list();
 sfb_status run_sharded(int64_t batch, const std::function<sfb_status(int device, int64_t first, int64_t count)> &fn);
+// Staging of a host-pointer entry point: every array is declared once -- device pointer, count, host pointer and
+// direction -- in the order it lies in the device buffer.  bytes() is what the buffer must hold, bind() hands out the
+// device pointers, upload() / download() copy the In / Out arrays whose host pointer is given, in declaration order, up
+// to the first error.  A NULL host pointer still reserves its space.  Where the memory comes from is the caller's business.
+class Staging {
+public:
+  enum Dir { Scratch = 0, In = 1, Out = 2, InOut = 3 };
+  template<class T>
+  void add(T **dev, size_t count, Dir dir = Scratch, const std::remove_const_t<T> *host = nullptr)
+  {
+    const int i = arena_.add(dev, count);
+    if (i >= 0) host_[i] = {const_cast<std::remove_const_t<T> *>(host), dir};
+  }
+  size_t bytes() const { return arena_.bytes(); }
+  bool bind(void *base) { return arena_.bind(base); }
+  hipError_t upload() const { return copy(In, hipMemcpyHostToDevice); }
+  hipError_t download() const { return copy(Out, hipMemcpyDeviceToHost); }
+
+private:
+  hipError_t copy(int dir, hipMemcpyKind kind) const
+  {
+    for (int i = 0; i < arena_.size(); ++i) {
+      if (!(host_[i].dir & dir) || !host_[i].p || !arena_.bytes(i)) continue;
+      const bool up      = kind == hipMemcpyHostToDevice;
+      const hipError_t e = hipMemcpy(up ? arena_.at(i) : host_[i].p, up ? host_[i].p : arena_.at(i), arena_.bytes(i), kind);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
+  struct Host { void *p; int dir; };
+  smooth_feedback_amd::detail::DeviceArena arena_;
+  Host host_[smooth_feedback_amd::detail::DeviceArena::kCapacity];
+};
+using smooth_feedback_amd::detail::DeviceBlock;
+using smooth_feedback_amd::detail::download;
+using smooth_feedback_amd::detail::upload;
+// memory for one call: a block of s.bytes(), bound to s and freed with `blk`
+inline sfb_status stage_per_call(Staging &s, DeviceBlock &blk)
+{
+  blk = DeviceBlock(s.bytes());
+  if (blk.error() != hipSuccess) return hip_fail(blk.error(), "hipMalloc");
+  return s.bind(blk.get()) ? SFB_OK : fail(SFB_ERR_UNSUPPORTED, "more staged arrays than the table holds");
+}
+
 struct SparsePlanHost;
 const SparsePlanHost &plan_host(const sfb_sparse_qp_plan *plan);  // capi_sparse.hip: the pattern the kernel works on
 const SparsePlanHost &plan_io(const sfb_sparse_qp_plan *plan);    // the caller's pattern (== plan_host unless pruned)

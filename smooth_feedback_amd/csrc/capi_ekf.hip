@@ -79,27 +79,21 @@ sfb_status sfb_ekf_predict_rk4_batch_host(int64_t batch, int dof, const double *
   if (st != SFB_OK) return st;
   if (batch == 0) return SFB_OK;
   const size_t B = (size_t)batch, nn = (size_t)dof * dof;
-  const size_t nQ = q_shared ? nn : B * nn, nT = dt_shared ? 1 : B, nA = A_mid ? 3 : 1;
-  double *dev = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&dev), ((1 + nA) * B * nn + nQ + nT) * sizeof(double));
-  if (e != hipSuccess) return sfb::hip_fail(e, "hipMalloc");
-  double *dP = dev, *dA = dP + B * nn, *dAm = dA + B * nn, *dAe = dAm + B * nn, *dQ = dA + nA * B * nn, *ddt = dQ + nQ;
-  e = hipMemcpy(dP, P, B * nn * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dA, A, B * nn * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess && A_mid) e = hipMemcpy(dAm, A_mid, B * nn * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess && A_end) e = hipMemcpy(dAe, A_end, B * nn * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dQ, Q, nQ * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(ddt, dt, nT * 8, hipMemcpyHostToDevice);
-  st = SFB_OK;
+  const size_t nQ = q_shared ? nn : B * nn, nT = dt_shared ? 1 : B;
+  using S = sfb::Staging;
+  S s;
+  double *dP, *dA, *dAm, *dAe, *dQ, *ddt;
+  s.add(&dP, B * nn, S::InOut, P); s.add(&dA, B * nn, S::In, A);
+  s.add(&dAm, A_mid ? B * nn : 0, S::In, A_mid); s.add(&dAe, A_end ? B * nn : 0, S::In, A_end);
+  s.add(&dQ, nQ, S::In, Q); s.add(&ddt, nT, S::In, dt);
+  sfb::DeviceBlock blk;
+  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
+  hipError_t e = s.upload();
   if (e == hipSuccess) {
     st = sfb_ekf_predict_rk4_batch(batch, dof, dA, A_mid ? dAm : nullptr, A_end ? dAe : nullptr, dQ, q_shared, ddt,
                                    dt_shared, dP, nullptr);
-    if (st == SFB_OK) {
-      e = hipDeviceSynchronize();
-      if (e == hipSuccess) e = hipMemcpy(P, dP, B * nn * 8, hipMemcpyDeviceToHost);
-    }
+    if (st == SFB_OK && (e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
   }
-  (void)hipFree(dev);
   if (e != hipSuccess) return sfb::hip_fail(e, "sfb_ekf_predict_rk4_batch_host");
   return st;
 }
@@ -142,38 +136,25 @@ sfb_status sfb_ekf_step_batch_host(int64_t batch, int dof, int ny, const double 
   if (st != SFB_OK) return st;
   if (batch == 0) return SFB_OK;
   const size_t B = (size_t)batch, nn = (size_t)dof * dof, mn = (size_t)ny * dof, mm = (size_t)ny * ny;
-  struct Buf { const void *h; size_t bytes; void **d; };
-  double *dA = nullptr, *dQ = nullptr, *ddt = nullptr, *dH = nullptr, *dR = nullptr, *dr = nullptr, *dP = nullptr,
-         *ddelta = nullptr;
-  int32_t *dinfo = nullptr;
-  std::vector<void *> owned;
-  hipError_t e = hipSuccess;
-  auto up = [&](const double *h, size_t cnt, double **d) {
-    if (e != hipSuccess || !h) return;
-    e = hipMalloc(reinterpret_cast<void **>(d), cnt * 8);
-    if (e != hipSuccess) return;
-    owned.push_back(*d);
-    e = hipMemcpy(*d, h, cnt * 8, hipMemcpyHostToDevice);
-  };
-  up(P, B * nn, &dP);
-  if (predict) { up(A, B * nn, &dA); up(Q, q_shared ? nn : B * nn, &dQ); up(dt, dt_shared ? 1 : B, &ddt); }
-  if (update) {
-    up(H, B * mn, &dH); up(R, r_shared ? mm : B * mm, &dR); up(r, B * ny, &dr);
-    if (e == hipSuccess) { e = hipMalloc(reinterpret_cast<void **>(&ddelta), B * dof * 8); if (e == hipSuccess) owned.push_back(ddelta); }
-    if (e == hipSuccess && info) { e = hipMalloc(reinterpret_cast<void **>(&dinfo), B * 4); if (e == hipSuccess) owned.push_back(dinfo); }
-  }
-  st = SFB_OK;
+  using S = sfb::Staging;
+  S s;  // (the arrays of a half that is not asked for take no space)
+  double *dP, *dA, *dQ, *ddt, *dH, *dR, *dr, *ddelta;
+  int32_t *dinfo;
+  s.add(&dP, B * nn, S::InOut, P);
+  s.add(&dA, predict ? B * nn : 0, S::In, A); s.add(&dQ, predict ? (q_shared ? nn : B * nn) : 0, S::In, Q);
+  s.add(&ddt, predict ? (dt_shared ? 1 : B) : 0, S::In, dt);
+  s.add(&dH, update ? B * mn : 0, S::In, H); s.add(&dR, update ? (r_shared ? mm : B * mm) : 0, S::In, R);
+  s.add(&dr, update ? B * ny : 0, S::In, r); s.add(&ddelta, update ? B * dof : 0, S::Out, delta);
+  s.add(&dinfo, update && info ? B : 0, S::Out, info);
+  sfb::DeviceBlock blk;
+  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
+  auto given = [](const void *h, auto *d) { return h ? d : nullptr; };  // ekf_common refuses what the caller left out
+  hipError_t e = s.upload();
   if (e == hipSuccess) {
-    st = ekf_common(batch, dof, ny, dA, dQ, q_shared, ddt, dt_shared, dH, dR, r_shared, dr, dP, ddelta, dinfo, predict,
-                    update, nullptr);
-    if (st == SFB_OK) {
-      e = hipDeviceSynchronize();
-      if (e == hipSuccess) e = hipMemcpy(P, dP, B * nn * 8, hipMemcpyDeviceToHost);
-      if (e == hipSuccess && update) e = hipMemcpy(delta, ddelta, B * dof * 8, hipMemcpyDeviceToHost);
-      if (e == hipSuccess && update && info) e = hipMemcpy(info, dinfo, B * 4, hipMemcpyDeviceToHost);
-    }
+    st = ekf_common(batch, dof, ny, given(A, dA), given(Q, dQ), q_shared, given(dt, ddt), dt_shared, given(H, dH), given(R, dR), r_shared,
+                    given(r, dr), dP, given(delta, ddelta), given(info, dinfo), predict, update, nullptr);
+    if (st == SFB_OK && (e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
   }
-  for (void *p : owned) (void)hipFree(p);
   if (e != hipSuccess) return sfb::hip_fail(e, "sfb_ekf_step_batch_host");
   return st;
 }

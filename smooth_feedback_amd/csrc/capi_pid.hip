@@ -20,25 +20,6 @@ sfb_status pid_check(const sfb_pid_group *group, int64_t batch, double windup_li
   return SFB_OK;
 }
 
-// host staging: one device allocation, arrays uploaded one after the other
-struct Stage {
-  double *dev = nullptr, *next = nullptr;
-  hipError_t e = hipSuccess;
-  explicit Stage(size_t doubles) { e = hipMalloc(reinterpret_cast<void **>(&dev), (doubles ? doubles : 1) * sizeof(double)); next = dev; }
-  ~Stage() { if (dev) (void)hipFree(dev); }
-  double *up(const double *h, size_t n)
-  {
-    double *d = next;
-    next += n;
-    if (e == hipSuccess && h) e = hipMemcpy(d, h, n * sizeof(double), hipMemcpyHostToDevice);
-    return d;
-  }
-  void down(double *h, const double *d, size_t n)
-  {
-    if (e == hipSuccess) e = hipMemcpy(h, d, n * sizeof(double), hipMemcpyDeviceToHost);
-  }
-};
-
 }  // namespace
 
 extern "C" {
@@ -121,19 +102,21 @@ sfb_status sfb_pid_step_batch_host(const sfb_pid_group *group, int64_t batch, do
   if (st != SFB_OK) return st;
   if (batch == 0) return SFB_OK;
   const size_t B = (size_t)batch, E = (size_t)grp.elem, D = (size_t)grp.dofs, Bd = des_shared ? 1 : B, Bg = gains_shared ? 1 : B;
-  Stage s(B * (E + 3 * D + 1) + Bd * (E + 2 * D) + Bg * 3 * D);
-  if (s.e != hipSuccess) return sfb::hip_fail(s.e, "hipMalloc");
-  double *dx = s.up(x, B * E), *dv = s.up(v, B * D), *dg = s.up(g_des, Bd * E), *dvd = s.up(v_des, Bd * D), *dad = s.up(a_des, Bd * D);
-  double *dkp = s.up(kp, Bg * D), *dkd = s.up(kd, Bg * D), *dki = s.up(ki, Bg * D);
-  double *die = s.up(i_err, B * D), *dtl = s.up(t_last, B), *du = s.up(nullptr, B * D);
-  if (s.e != hipSuccess) return sfb::hip_fail(s.e, "sfb_pid_step_batch_host upload");
+  using S = sfb::Staging;
+  S s;
+  double *dx, *dv, *dg, *dvd, *dad, *dkp, *dkd, *dki, *die, *dtl, *du;
+  s.add(&dx, B * E, S::In, x); s.add(&dv, B * D, S::In, v);
+  s.add(&dg, Bd * E, S::In, g_des); s.add(&dvd, Bd * D, S::In, v_des); s.add(&dad, Bd * D, S::In, a_des);
+  s.add(&dkp, Bg * D, S::In, kp); s.add(&dkd, Bg * D, S::In, kd); s.add(&dki, Bg * D, S::In, ki);
+  s.add(&die, B * D, S::InOut, i_err); s.add(&dtl, B, S::InOut, t_last); s.add(&du, B * D, S::Out, u);
+  sfb::DeviceBlock blk;
+  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
+  hipError_t e = s.upload();
+  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_pid_step_batch_host upload");
   st = sfb_pid_step_batch(group, batch, t, dx, dv, dg, dvd, dad, des_shared, dkp, dkd, dki, gains_shared, windup_limit, die, dtl, du, nullptr);
   if (st != SFB_OK) return st;
-  s.e = hipDeviceSynchronize();
-  s.down(i_err, die, B * D);
-  s.down(t_last, dtl, B);
-  s.down(u, du, B * D);
-  if (s.e != hipSuccess) return sfb::hip_fail(s.e, "sfb_pid_step_batch_host");
+  if ((e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
+  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_pid_step_batch_host");
   return SFB_OK;
 }
 
@@ -154,23 +137,22 @@ sfb_status sfb_pid_rollout_batch_host(const sfb_pid_group *group, int64_t batch,
   if (st != SFB_OK) return st;
   if (batch == 0 || steps == 0) return SFB_OK;
   const size_t B = (size_t)batch, E = (size_t)grp.elem, D = (size_t)grp.dofs, Bd = des_shared ? 1 : B, Bg = gains_shared ? 1 : B;
-  Stage s(B * (E + 3 * D + 2) + Bd * (E + D) + Bg * 3 * D + D);
-  if (s.e != hipSuccess) return sfb::hip_fail(s.e, "hipMalloc");
-  double *dx = s.up(x, B * E), *dv = s.up(v, B * D), *dg = s.up(g_des0, Bd * E), *dvd = s.up(v_des, Bd * D);
-  double *dkp = s.up(kp, Bg * D), *dkd = s.up(kd, Bg * D), *dki = s.up(ki, Bg * D), *dum = s.up(u_max, D);
-  double *die = s.up(i_err, B * D), *dtl = s.up(t_last, B), *du = s.up(nullptr, B * D), *dc = s.up(nullptr, B);
-  if (s.e != hipSuccess) return sfb::hip_fail(s.e, "sfb_pid_rollout_batch_host upload");
+  using S = sfb::Staging;
+  S s;
+  double *dx, *dv, *dg, *dvd, *dkp, *dkd, *dki, *dum, *die, *dtl, *du, *dc;
+  s.add(&dx, B * E, S::InOut, x); s.add(&dv, B * D, S::InOut, v);
+  s.add(&dg, Bd * E, S::In, g_des0); s.add(&dvd, Bd * D, S::In, v_des);
+  s.add(&dkp, Bg * D, S::In, kp); s.add(&dkd, Bg * D, S::In, kd); s.add(&dki, Bg * D, S::In, ki); s.add(&dum, D, S::In, u_max);
+  s.add(&die, B * D, S::InOut, i_err); s.add(&dtl, B, S::InOut, t_last); s.add(&du, B * D, S::Out, u_last); s.add(&dc, B, S::Out, cost);
+  sfb::DeviceBlock blk;
+  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
+  hipError_t e = s.upload();
+  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_pid_rollout_batch_host upload");
   st = sfb_pid_rollout_batch(group, batch, t0, dt, steps, dx, dv, dg, dvd, des_shared, dkp, dkd, dki, gains_shared, windup_limit,
                              u_max ? dum : nullptr, die, dtl, du, dc, nullptr);
   if (st != SFB_OK) return st;
-  s.e = hipDeviceSynchronize();
-  s.down(x, dx, B * E);
-  s.down(v, dv, B * D);
-  s.down(i_err, die, B * D);
-  s.down(t_last, dtl, B);
-  s.down(u_last, du, B * D);
-  s.down(cost, dc, B);
-  if (s.e != hipSuccess) return sfb::hip_fail(s.e, "sfb_pid_rollout_batch_host");
+  if ((e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
+  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_pid_rollout_batch_host");
   return SFB_OK;
 }
 

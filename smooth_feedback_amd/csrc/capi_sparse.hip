@@ -449,10 +449,21 @@ sfb_status sfb_sparse_qp_solve_batch_host_phases(sfb_sparse_qp_plan *plan, const
   const sfb::SparsePlanHost &h = sfb::plan_io(plan);  // the caller's pattern (strides of the value arrays)
   const size_t B = (size_t)batch, N = (size_t)h.n, M = (size_t)h.m, NP = (size_t)h.nnzP, NA = (size_t)h.nnzA;
   const size_t wsb  = ws_layout(plan, batch).total;  // multiple of 8
-  const size_t TR = (trace ? B * (size_t)trace_rows * 5 : 0) + (phase_us ? B * 6 : 0);  // the table, then the phase times
-  const size_t TR0 = trace ? B * (size_t)trace_rows * 5 : 0;
-  const size_t in_d = B * (NP + N + NA + 2 * M) + (warm_x ? B * (N + M) : 0), out_d = B * (N + M + 1) + TR;
-  const size_t bytes = (in_d + out_d) * sizeof(double) + wsb + B * 8;
+  const size_t TR0 = trace ? B * (size_t)trace_rows * 5 : 0, W = warm_x ? B : 0;
+  using S = sfb::Staging;
+  S s;  // the solver's workspace first (reuse_factor below), then the arrays; the phase times follow the table
+  char *dws;
+  double *dPx, *dq, *dAx, *dl, *du, *dwx, *dwy, *dx, *dy, *dobj, *dtrace, *dphase;
+  uint32_t *dit;
+  int32_t *dcode;
+  s.add(&dws, wsb);
+  s.add(&dPx, B * NP, S::In, Px); s.add(&dq, B * N, S::In, q); s.add(&dAx, B * NA, S::In, Ax);
+  s.add(&dl, B * M, S::In, l); s.add(&du, B * M, S::In, u);
+  s.add(&dwx, W * N, S::In, warm_x); s.add(&dwy, W * M, S::In, warm_y);
+  s.add(&dx, B * N, S::Out, x); s.add(&dy, B * M, S::Out, y); s.add(&dobj, B, S::Out, obj);
+  s.add(&dtrace, TR0, S::InOut, trace); s.add(&dphase, phase_us ? B * 6 : 0, S::Out, phase_us);
+  s.add(&dit, B, S::Out, iter); s.add(&dcode, B, S::Out, code);
+  const size_t bytes = s.bytes();
   int devid    = 0;
   hipError_t e = hipGetDevice(&devid);
   if (e != hipSuccess) return sfb::hip_fail(e, "hipGetDevice");
@@ -474,6 +485,7 @@ sfb_status sfb_sparse_qp_solve_batch_host_phases(sfb_sparse_qp_plan *plan, const
     cache.second = bytes;
     hd->batch    = -1;
   }
+  if (!s.bind(cache.first)) return sfb::fail(SFB_ERR_UNSUPPORTED, "more staged arrays than the table holds");
   if (hd->stream == nullptr && (e = hipStreamCreateWithFlags(&hd->stream, hipStreamNonBlocking)) != hipSuccess) {
     hd->stream = nullptr;
     return sfb::hip_fail(e, "hipStreamCreateWithFlags");
@@ -492,35 +504,14 @@ sfb_status sfb_sparse_qp_solve_batch_host_phases(sfb_sparse_qp_plan *plan, const
   hd->batch  = batch;
   hd->origin = tl_multi_origin;
   prm = &prm_call;
-  char *devmem = cache.first;
-  double *dws = reinterpret_cast<double *>(devmem);
-  double *dPx = reinterpret_cast<double *>(devmem + wsb);
-  double *dq = dPx + B * NP, *dAx = dq + B * N, *dl = dAx + B * NA, *du = dl + B * M;
-  double *dwx = nullptr, *dwy = nullptr, *dx = du + B * M;
-  if (warm_x) { dwx = dx; dwy = dwx + B * N; dx = dwy + B * M; }
-  double *dy = dx + B * N, *dobj = dy + B * M, *dtrace = dobj + B;
-  uint32_t *dit  = reinterpret_cast<uint32_t *>(dtrace + TR);
-  int32_t *dcode = reinterpret_cast<int32_t *>(dit + B);
-  auto H2D = [&](void *d, const void *hh, size_t nb) { return nb ? hipMemcpy(d, hh, nb, hipMemcpyHostToDevice) : hipSuccess; };
-  auto D2H = [&](void *hh, const void *d, size_t nb) { return nb ? hipMemcpy(hh, d, nb, hipMemcpyDeviceToHost) : hipSuccess; };
+  if (!warm_x) dwx = dwy = nullptr;
   using clk = std::chrono::steady_clock;
   auto ms   = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
   const auto tv0 = clk::now();
   auto tv1 = tv0, tv2 = tv0;
+  for (size_t r = 0; r < TR0; ++r) trace[r] = (r % 5 == 0) ? -1.0 : 0.0;  // unused rows keep ITER = -1
   do {
-    if ((e = H2D(dPx, Px, B * NP * 8)) != hipSuccess) break;
-    if ((e = H2D(dq, q, B * N * 8)) != hipSuccess) break;
-    if ((e = H2D(dAx, Ax, B * NA * 8)) != hipSuccess) break;
-    if ((e = H2D(dl, l, B * M * 8)) != hipSuccess) break;
-    if ((e = H2D(du, u, B * M * 8)) != hipSuccess) break;
-    if (warm_x) {
-      if ((e = H2D(dwx, warm_x, B * N * 8)) != hipSuccess) break;
-      if ((e = H2D(dwy, warm_y, B * M * 8)) != hipSuccess) break;
-    }
-    if (trace) {  // unused rows keep ITER = -1
-      for (size_t r = 0; r < TR0; ++r) trace[r] = (r % 5 == 0) ? -1.0 : 0.0;
-      if ((e = H2D(dtrace, trace, TR0 * 8)) != hipSuccess) break;
-    }
+    if ((e = s.upload()) != hipSuccess) break;
     tv1 = clk::now();
     // The uploads are synchronous copies on the null stream, the launches go to a stream that does not synchronise with it:
     // a copy out of pageable memory may return once its data is STAGED, so the launch stream is made to wait for the null
@@ -528,20 +519,14 @@ sfb_status sfb_sparse_qp_solve_batch_host_phases(sfb_sparse_qp_plan *plan, const
     if ((e = hipEventRecord(hd->uploaded, nullptr)) != hipSuccess) break;
     if ((e = hipStreamWaitEvent(hd->stream, hd->uploaded, 0)) != hipSuccess) break;
     st = solve_batch_impl(plan, prm, batch, dPx, dq, dAx, dl, du, dwx, dwy, dx, dy, dobj, dit, dcode, dws, nullptr, hd->stream,
-                          trace ? dtrace : nullptr, trace ? trace_rows : 0, phase_us ? dtrace + TR0 : nullptr);
+                          trace ? dtrace : nullptr, trace ? trace_rows : 0, phase_us ? dphase : nullptr);
     if (st != SFB_OK) {
       (void)hipStreamSynchronize(hd->stream);
       break;
     }
     if ((e = hipStreamSynchronize(hd->stream)) != hipSuccess) break;
     tv2 = clk::now();
-    if ((e = D2H(x, dx, B * N * 8)) != hipSuccess) break;
-    if ((e = D2H(y, dy, B * M * 8)) != hipSuccess) break;
-    if (obj && (e = D2H(obj, dobj, B * 8)) != hipSuccess) break;
-    if (iter && (e = D2H(iter, dit, B * 4)) != hipSuccess) break;
-    if ((e = D2H(code, dcode, B * 4)) != hipSuccess) break;
-    if (trace && (e = D2H(trace, dtrace, TR0 * 8)) != hipSuccess) break;
-    if (phase_us && (e = D2H(phase_us, dtrace + TR0, B * 6 * 8)) != hipSuccess) break;
+    e   = s.download();
   } while (false);
   if (e != hipSuccess) st = sfb::hip_fail(e, "sfb_sparse_qp_solve_batch_host");
   if (st == SFB_OK && !vtrace.empty()) {  // the table of qp_solver.hpp:409-420, :490-501 (TIME: device clock, microseconds)
