@@ -16,6 +16,7 @@
 #include <smooth_feedback_amd/mpc.hpp>
 #include <smooth/feedback/mpc.hpp>  // the reference's include path and namespace (sfbx_test_mpc_api)
 #include <smooth/feedback/pid.hpp>  // likewise (sfbx_test_pid_api, sfbx_pid_host)
+#include <smooth/feedback/spline.hpp>  // likewise (sfbx_test_pid_spline_api, sfbx_spline_*)
 
 #include "lie_eval.h"
 #include "rigid_body_model.h"
@@ -1460,6 +1461,169 @@ int sfbx_pid_host(int group, int64_t batch, int ncalls, const double * times, co
 {
   if (batch < 0 || ncalls < 0) return -1;
   return pid_dispatch(group, [&]<class G>() { pid_host<G>(batch, ncalls, times, x, v, gd, vd, ad, kp, kd, ki, windup, u_out, ie_out); });
+}
+
+// ---- splines ----
+namespace {
+
+// caller code against <smooth/feedback/pid.hpp> and <smooth/feedback/spline.hpp>: a controller told to follow a curve.
+// Five rounds; each draws four SE2 knots for the times 0, 1, 2, 3, fits the cubic, hands it to a controller (kp = 2,
+// kd = 3) with the curve's time 0 at 0.5 s, calls the controller at 1 s and compares with the law written out from the
+// curve at 0.5.  Both value categories of set_xdes(t0, spline) are used.
+int test_pid_spline_api(double * out)
+{
+  namespace sf = smooth::feedback;
+  using Sec    = std::chrono::duration<double>;
+  using PidT   = sf::PID<Sec, sf::SE2>;
+  std::mt19937_64 rng(29);
+  std::uniform_real_distribution<double> d(-1.0, 1.0);
+  double worst = 0.0, moving = 1e300;
+  for (int round = 0; round < 5; ++round) {
+    std::vector<sf::SE2> knots;
+    for (int i = 0; i < 4; ++i) knots.push_back(sf::SE2::FromAngle(1.5 * d(rng), 2 * d(rng), 2 * d(rng)));
+    const sf::Spline<3, sf::SE2> curve = sf::fit_spline_cubic(std::vector<double>{0, 1, 2, 3}, knots);
+    PidT pid;
+    pid.set_kp(2);
+    pid.set_kd(3);
+    if (round % 2) pid.set_xdes(Sec(0.5), curve);
+    else pid.set_xdes(Sec(0.5), sf::Spline<3, sf::SE2>(curve));
+    const sf::SE2 g = sf::SE2::FromAngle(3 * d(rng), d(rng), d(rng));
+    const sf::SE2::Tangent v{d(rng), d(rng), d(rng)};
+    const auto u = pid(Sec(1.0), g, v);
+    sf::SE2::Tangent v_des, a_des;
+    const sf::SE2 g_des = curve(0.5, v_des, a_des);
+    const auto e        = rminus(g_des, g);
+    double num = 0, den = 0, speed = 0;
+    for (int i = 0; i < 3; ++i) {
+      const double expect = a_des[i] + 3 * (v_des[i] - v[i]) + 2 * e[i];
+      num += (u[i] - expect) * (u[i] - expect);
+      den += expect * expect;
+      speed += v_des[i] * v_des[i] + a_des[i] * a_des[i];
+    }
+    worst  = std::max(worst, std::sqrt(num / den));
+    moving = std::min(moving, speed);  // the curve is in motion at 0.5: the check is not one of a held pose
+  }
+  out[0] = worst;
+  out[1] = moving;
+  return (worst <= 1e-12 && moving > 1e-6) ? 0 : 1;
+}
+
+template<class G>
+typename G::Tangent tangent_of(const double * p)
+{
+  typename G::Tangent t{};
+  for (int i = 0; i < G::Dof; ++i) t[i] = p[i];
+  return t;
+}
+
+template<class G>
+void spline_fit_host(int64_t batch, int64_t nknots, const double * tk, const double * gk, double * V)
+{
+  constexpr int E = PIDFlat<G>::E, D = G::Dof;
+  for (int64_t b = 0; b < batch; ++b) {
+    std::vector<G> gg;
+    for (int64_t i = 0; i < nknots; ++i) gg.push_back(PIDFlat<G>::load(gk + (b * nknots + i) * E));
+    const Spline<3, G> c = fit_spline_cubic(std::vector<double>(tk + b * nknots, tk + (b + 1) * nknots), gg);
+    std::copy(c.control_flat().begin(), c.control_flat().end(), V + b * (nknots - 1) * 3 * D);
+  }
+}
+
+template<int K, class G>
+Spline<K, G> spline_from_flat(int64_t b, int64_t nknots, const double * tk, const double * gk, const double * V)
+{
+  constexpr int E = PIDFlat<G>::E, D = G::Dof;
+  return Spline<K, G>(std::vector<double>(tk + b * nknots, tk + (b + 1) * nknots), std::vector<double>(gk + b * nknots * E, gk + (b + 1) * nknots * E),
+                      std::vector<double>(V + b * (nknots - 1) * K * D, V + (b + 1) * (nknots - 1) * K * D));
+}
+
+template<int K, class G>
+void spline_eval_host(int64_t batch, int64_t nknots, const double * tk, const double * gk, const double * V, int64_t nt, const double * t, double * g,
+                      double * vel, double * acc)
+{
+  constexpr int E = PIDFlat<G>::E, D = G::Dof;
+  for (int64_t b = 0; b < batch; ++b) {
+    const Spline<K, G> c = spline_from_flat<K, G>(b, nknots, tk, gk, V);
+    for (int64_t k = 0; k < nt; ++k) {
+      typename G::Tangent v, a;
+      const int64_t r = b * nt + k;
+      PIDFlat<G>::store(c(t[r], v, a), g + r * E);
+      for (int i = 0; i < D; ++i) {
+        vel[r * D + i] = v[i];
+        acc[r * D + i] = a[i];
+      }
+    }
+  }
+}
+
+// pid_rollout (pid.hpp) along Spline<3, G> on the CPU, one agent after the other
+template<class G>
+void pid_rollout_spline_host(int64_t batch, double t0, double dt, int64_t steps, double * x, double * v, int64_t nknots, const double * tk,
+                             const double * gk, const double * V, const double * ts0, const double * kp, const double * kd, const double * ki,
+                             double windup, const double * u_max, double * ie, double * t_last, double * u_last, double * cost)
+{
+  using Flat      = PIDFlat<G>;
+  constexpr int E = Flat::E, D = G::Dof;
+  for (int64_t b = 0; b < batch; ++b) {
+    const Spline<3, G> c = spline_from_flat<3, G>(b, nknots, tk, gk, V);
+    const double origin  = ts0 ? ts0[b] : 0.0;
+    G xb     = Flat::load(x + b * E);
+    auto vb  = tangent_of<G>(v + b * D), ieb = tangent_of<G>(ie + b * D);
+    typename G::Tangent ul{};
+    const auto traj = [&](double t) {
+      PIDDesired<G> d;
+      d.g = c(t - origin, d.v, d.a);
+      return d;
+    };
+    cost[b] = pid_rollout<G>(traj, t0, dt, steps, xb, vb, tangent_of<G>(kp + b * D), tangent_of<G>(kd + b * D), tangent_of<G>(ki + b * D), windup,
+                             u_max != nullptr, u_max ? tangent_of<G>(u_max) : typename G::Tangent{}, t_last[b], ieb, ul);
+    Flat::store(xb, x + b * E);
+    for (int i = 0; i < D; ++i) {
+      v[b * D + i]      = vb[i];
+      ie[b * D + i]     = ieb[i];
+      u_last[b * D + i] = ul[i];
+    }
+  }
+}
+
+}  // namespace
+
+int sfbx_test_pid_spline_api(double * out) { return test_pid_spline_api(out); }
+
+int sfbx_lie_Ad(int group, int64_t count, const double * g, const double * a, double * out)
+{
+  if (count < 0) return -1;
+  return pid_dispatch(group, [&]<class G>() {
+    for (int64_t b = 0; b < count; ++b) {
+      const auto r = PIDFlat<G>::load(g + b * PIDFlat<G>::E).Ad(tangent_of<G>(a + b * G::Dof));
+      for (int i = 0; i < G::Dof; ++i) out[b * G::Dof + i] = r[i];
+    }
+  });
+}
+
+int sfbx_spline_fit_host(int group, int64_t batch, int64_t nknots, const double * tk, const double * gk, double * V)
+{
+  if (batch < 0 || nknots < 2) return -1;
+  return pid_dispatch(group, [&]<class G>() { spline_fit_host<G>(batch, nknots, tk, gk, V); });
+}
+
+int sfbx_spline_eval_host(int group, int degree, int64_t batch, int64_t nknots, const double * tk, const double * gk, const double * V, int64_t nt,
+                          const double * t, double * g, double * vel, double * acc)
+{
+  if (batch < 0 || nknots < 2 || nt < 0 || (degree != 2 && degree != 3)) return -1;
+  return pid_dispatch(group, [&]<class G>() {
+    if (degree == 2) spline_eval_host<2, G>(batch, nknots, tk, gk, V, nt, t, g, vel, acc);
+    else spline_eval_host<3, G>(batch, nknots, tk, gk, V, nt, t, g, vel, acc);
+  });
+}
+
+int sfbx_pid_rollout_spline_host(int group, int64_t batch, double t0, double dt, int64_t steps, double * x, double * v, int64_t nknots,
+                                 const double * tk, const double * gk, const double * V, const double * ts0, const double * kp, const double * kd,
+                                 const double * ki, double windup, const double * u_max, double * ie, double * t_last, double * u_last, double * cost)
+{
+  if (batch < 0 || steps < 0 || nknots < 2) return -1;
+  return pid_dispatch(group, [&]<class G>() {
+    pid_rollout_spline_host<G>(batch, t0, dt, steps, x, v, nknots, tk, gk, V, ts0, kp, kd, ki, windup, u_max, ie, t_last, u_last, cost);
+  });
 }
 
 int sfbx_arena_selftest(void)

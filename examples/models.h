@@ -149,6 +149,25 @@ int sfbx_pid_host(int group, int64_t batch, int ncalls, const double *times, con
 int sfbx_pid_rollout_host(int group, int64_t batch, double t0, double dt, int64_t steps, double *x, double *v, const double *g0,
                           const double *w, const double *kp, const double *kd, const double *ki, double windup, const double *u_max,
                           double *ie, double *t_last, double *u_last, double *cost);
+/* PID<T, G>::set_xdes(t0, spline) through <smooth/feedback/pid.hpp> and <smooth/feedback/spline.hpp> (host only): five rounds
+ * of a controller (kp = 2, kd = 3) following the cubic fitted through four random SE2 knots at times 0, 1, 2, 3, curve origin
+ * at 0.5 s, called at 1 s, against the law written out from the curve at 0.5.  out [2]: worst relative error, smallest
+ * |v_des|^2 + |a_des|^2 met.  Returns 0 when the error is <= 1e-12 and the curve was in motion. */
+int sfbx_test_pid_spline_api(double *out);
+/* Ad_g a on the host (lie.hpp), groups as sfbx_pid_host: g [count][elem], a and out [count][dof] */
+int sfbx_lie_Ad(int group, int64_t count, const double *g, const double *a, double *out);
+/* fit_spline_cubic per agent: tk [batch][nknots], gk [batch][nknots][elem] -> V [batch][nknots-1][3][dof] */
+int sfbx_spline_fit_host(int group, int64_t batch, int64_t nknots, const double *tk, const double *gk, double *V);
+/* Spline<degree, G>::operator() per agent, degree 2 or 3: V [batch][nknots-1][degree][dof], t [batch][nt] ->
+ * g [batch][nt][elem], vel and acc [batch][nt][dof] */
+int sfbx_spline_eval_host(int group, int degree, int64_t batch, int64_t nknots, const double *tk, const double *gk, const double *V,
+                          int64_t nt, const double *t, double *g, double *vel, double *acc);
+/* pid_rollout of pid.hpp along Spline<3, G> on the CPU: arguments as sfb_pid_rollout_spline_batch_host with per-agent splines
+ * and gains */
+int sfbx_pid_rollout_spline_host(int group, int64_t batch, double t0, double dt, int64_t steps, double *x, double *v, int64_t nknots,
+                                 const double *tk, const double *gk, const double *V, const double *ts0, const double *kp,
+                                 const double *kd, const double *ki, double windup, const double *u_max, double *ie, double *t_last,
+                                 double *u_last, double *cost);
 /* mesh: nodes (N+1), weights (N+1), Dus ((K+1)*K col-major) for `n` intervals of K points */
 int sfbx_mesh(int n_ivals, int K, double *nodes, double *weights, double *Dus);
 

@@ -612,4 +612,66 @@ int sfbx_pid_swarm_device(int64_t batch, double t0, double dt, int64_t steps, co
   return rc;
 }
 
+/* PIDSwarmDevice<SE3, SplineTrajectory<3, SE3>> (pid_device.hpp, spline.hpp): the swarm of sfbx_pid_swarm_device following
+ * cubic splines -- tk [nknots], gk [nknots][7], V [nknots-1][3][6] per agent, or ONE of each with spline_shared != 0 -- at
+ * t - ts0[agent] (ts0 [batch] nullable).  rollout(t0, dt, steps), steps >= 1.  Out as sfbx_pid_swarm_device. */
+int sfbx_pid_swarm_spline_device(int64_t batch, double t0, double dt, int64_t steps, const double * x, const double * v, const double * ie,
+                                 const double * t_last, const double * kp, const double * kd, const double * ki, int64_t nknots, const double * tk,
+                                 const double * gk, const double * V, int spline_shared, const double * ts0, double windup, const double * u_max,
+                                 double * x_out, double * v_out, double * ie_out, double * u_out, double * cost_out)
+{
+  if (batch < 1 || steps < 1 || nknots < 2) return -1;
+  double *dtk, *dgk, *dV, *dts;
+  int rc = 0;
+  try {
+    const size_t B = (size_t)batch, K = (size_t)nknots, Bs = spline_shared ? 1 : B;
+    using T6       = SE3::Tangent;
+    const auto tangents = [&](const double * p) {
+      std::vector<T6> out(B);
+      for (size_t b = 0; b < B; ++b)
+        for (int i = 0; i < 6; ++i) out[b][i] = p[6 * b + i];
+      return out;
+    };
+    const auto poses = [&](const double * p) {
+      std::vector<SE3> out(B);
+      for (size_t b = 0; b < B; ++b) out[b] = PIDFlat<SE3>::load(p + 7 * b);
+      return out;
+    };
+    detail::DeviceArena a;
+    a.add(&dtk, Bs * K); a.add(&dgk, Bs * K * 7); a.add(&dV, Bs * (K - 1) * 18); a.add(&dts, ts0 ? B : 0);
+    const detail::DeviceBlock mem(a, "pid_device");
+    detail::hip_check(detail::upload(dtk, tk, Bs * K), "pid_device", "hipMemcpy");
+    detail::hip_check(detail::upload(dgk, gk, Bs * K * 7), "pid_device", "hipMemcpy");
+    detail::hip_check(detail::upload(dV, V, Bs * (K - 1) * 18), "pid_device", "hipMemcpy");
+    if (ts0) detail::hip_check(detail::upload(dts, ts0, B), "pid_device", "hipMemcpy");
+    using Traj = SplineTrajectory<3, SE3>;
+    PIDSwarmDevice<SE3, Traj> swarm(Traj{nknots - 1, dtk, dgk, dV, spline_shared != 0, ts0 ? dts : nullptr}, batch, PIDParams{windup});
+    swarm.set_state(poses(x), tangents(v));
+    swarm.set_gains(tangents(kp), tangents(kd), tangents(ki));
+    swarm.set_integral(tangents(ie), std::vector<double>(t_last, t_last + B));
+    if (u_max) {
+      T6 um{};
+      for (int i = 0; i < 6; ++i) um[i] = u_max[i];
+      swarm.set_u_max(um);
+    }
+    swarm.rollout(t0, dt, steps);
+    const auto xs = swarm.states();
+    const auto vs = swarm.velocities(), is = swarm.integrals(), us = swarm.inputs();
+    const auto cs = swarm.costs();
+    for (size_t b = 0; b < B; ++b) {
+      PIDFlat<SE3>::store(xs[b], x_out + 7 * b);
+      for (int i = 0; i < 6; ++i) {
+        v_out[6 * b + i]  = vs[b][i];
+        ie_out[6 * b + i] = is[b][i];
+        u_out[6 * b + i]  = us[b][i];
+      }
+      cost_out[b] = cs[b];
+    }
+  } catch (const std::exception & e) {
+    std::fprintf(stderr, "sfbx_pid_swarm_spline_device: %s\n", e.what());
+    rc = -2;
+  }
+  return rc;
+}
+
 }  // extern "C"

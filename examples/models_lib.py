@@ -396,6 +396,60 @@ def pid_rollout_host(group, t0, dt, steps, x, v, g0, w, kp, kd, ki, ie, t_last, 
     return dict(x=x, v=v, i_err=ie, t_last=t_last, u_last=u, cost=cost)
 
 
+def test_pid_spline_api():
+    """PID::set_xdes(t0, spline) under the reference's include paths (models.h): (ok, [worst relative error, least motion])"""
+    out = np.zeros(2)
+    rc = lib().sfbx_test_pid_spline_api(_p(out))
+    return rc == 0, out
+
+
+def lie_Ad(group, g, a):
+    """Ad_g a of lie.hpp on the host: g [n][elem], a [n][dof] -> [n][dof]"""
+    g, a = np.ascontiguousarray(g, dtype=np.float64), np.ascontiguousarray(a, dtype=np.float64)
+    out = np.zeros_like(a)
+    rc = lib().sfbx_lie_Ad(PID_GROUPS[group], C.c_int64(len(g)), _p(g), _p(a), _p(out))
+    assert rc == 0, rc
+    return out
+
+
+def spline_fit_host(group, tk, gk):
+    """fit_spline_cubic per agent: tk [B][S+1], gk [B][S+1][elem] -> V [B][S][3][dof]"""
+    tk, gk = np.ascontiguousarray(tk, dtype=np.float64), np.ascontiguousarray(gk, dtype=np.float64)
+    B, K = tk.shape
+    D = sum(d for _, d in PID_PARTS[group])
+    V = np.zeros((B, K - 1, 3, D))
+    rc = lib().sfbx_spline_fit_host(PID_GROUPS[group], C.c_int64(B), C.c_int64(K), _p(tk), _p(gk), _p(V))
+    assert rc == 0, rc
+    return V
+
+
+def spline_eval_host(group, tk, gk, V, t):
+    """Spline<K, G>::operator() per agent (K = V.shape[2], 2 or 3): t [B][nt] -> g [B][nt][elem], vel, acc [B][nt][dof]"""
+    tk, gk, V, t = [np.ascontiguousarray(a, dtype=np.float64) for a in (tk, gk, V, t)]
+    B, K = tk.shape
+    nt, E, D = t.shape[1], gk.shape[2], V.shape[3]
+    g, vel, acc = np.zeros((B, nt, E)), np.zeros((B, nt, D)), np.zeros((B, nt, D))
+    rc = lib().sfbx_spline_eval_host(PID_GROUPS[group], int(V.shape[2]), C.c_int64(B), C.c_int64(K), _p(tk), _p(gk), _p(V), C.c_int64(nt), _p(t),
+                                     _p(g), _p(vel), _p(acc))
+    assert rc == 0, rc
+    return g, vel, acc
+
+
+def pid_rollout_spline_host(group, t0, dt, steps, x, v, tk, gk, V, kp, kd, ki, ie, t_last, ts0=None, windup=np.inf, u_max=None):
+    """pid_rollout (pid.hpp) along Spline<3, G> on the CPU; arrays as smooth_feedback_amd.pid_rollout_spline_batch_host (per agent)"""
+    x, v, ie, t_last = [np.array(a, dtype=np.float64, order="C") for a in (x, v, ie, t_last)]
+    tk, gk, V, kp, kd, ki = [np.ascontiguousarray(a, dtype=np.float64) for a in (tk, gk, V, kp, kd, ki)]
+    um = None if u_max is None else np.ascontiguousarray(u_max, dtype=np.float64)
+    ts = None if ts0 is None else np.ascontiguousarray(ts0, dtype=np.float64)
+    B = len(x)
+    u = np.zeros_like(v); cost = np.zeros(B)
+    rc = lib().sfbx_pid_rollout_spline_host(PID_GROUPS[group], C.c_int64(B), C.c_double(t0), C.c_double(dt), C.c_int64(steps), _p(x), _p(v),
+                                            C.c_int64(tk.shape[1]), _p(tk), _p(gk), _p(V), None if ts is None else _p(ts), _p(kp), _p(kd), _p(ki),
+                                            C.c_double(windup), None if um is None else _p(um), _p(ie), _p(t_last), _p(u), _p(cost))
+    assert rc == 0, rc
+    return dict(x=x, v=v, i_err=ie, t_last=t_last, u_last=u, cost=cost)
+
+
 def pid_swarm_device(t0, dt, steps, x, v, ie, t_last, kp, kd, ki, g0, w, kind, windup=np.inf, u_max=None):
     """PIDSwarmDevice<SE3, functor> (pid_device.hpp, models_device.hip): rollout(t0, dt, steps), or one step(t0) for steps == 0,
     of agents tracking rplus(g0, t w) (kind 0) or a twist of changing size along w (kind 1).  Returns dict x, v, ie, u, cost."""
@@ -406,5 +460,22 @@ def pid_swarm_device(t0, dt, steps, x, v, ie, t_last, kp, kd, ki, g0, w, kind, w
     out = dict(x=np.zeros((B, 7)), v=np.zeros((B, 6)), ie=np.zeros((B, 6)), u=np.zeros((B, 6)), cost=np.zeros(B))
     rc = dev_lib().sfbx_pid_swarm_device(C.c_int64(B), C.c_double(t0), C.c_double(dt), C.c_int64(steps), *[_p(a) for a in arrs], _p(kind),
                                          C.c_double(windup), None if um is None else _p(um), *[_p(out[k]) for k in ("x", "v", "ie", "u", "cost")])
+    assert rc == 0, rc
+    return out
+
+
+def pid_swarm_spline_device(t0, dt, steps, x, v, ie, t_last, kp, kd, ki, tk, gk, V, ts0=None, windup=np.inf, u_max=None):
+    """PIDSwarmDevice<SE3, SplineTrajectory<3, SE3>> (pid_device.hpp, spline.hpp, models_device.hip): rollout(t0, dt, steps) of
+    agents following their splines (tk [B][S+1], gk [B][S+1][7], V [B][S][3][6]) or ONE spline (no batch axis) at t - ts0.
+    Returns dict x, v, ie, u, cost."""
+    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (x, v, ie, t_last, kp, kd, ki)]
+    tk, gk, V = [np.ascontiguousarray(a, dtype=np.float64) for a in (tk, gk, V)]
+    B = len(arrs[0])
+    um = None if u_max is None else np.ascontiguousarray(u_max, dtype=np.float64)
+    ts = None if ts0 is None else np.ascontiguousarray(ts0, dtype=np.float64)
+    out = dict(x=np.zeros((B, 7)), v=np.zeros((B, 6)), ie=np.zeros((B, 6)), u=np.zeros((B, 6)), cost=np.zeros(B))
+    rc = dev_lib().sfbx_pid_swarm_spline_device(C.c_int64(B), C.c_double(t0), C.c_double(dt), C.c_int64(steps), *[_p(a) for a in arrs],
+                                                C.c_int64(tk.shape[-1]), _p(tk), _p(gk), _p(V), int(tk.ndim == 1), None if ts is None else _p(ts),
+                                                C.c_double(windup), None if um is None else _p(um), *[_p(out[k]) for k in ("x", "v", "ie", "u", "cost")])
     assert rc == 0, rc
     return out

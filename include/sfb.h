@@ -640,6 +640,52 @@ sfb_status sfb_pid_rollout_batch_host(const sfb_pid_group *group, int64_t batch,
                                       double windup_limit, const double *u_max, double *i_err, double *t_last,
                                       double *u_last, double *cost);
 
+/* ------------------------------------------------------------------------------------------
+ * Batched Lie-group cubic splines (include/smooth_feedback_amd/spline.hpp: Spline<3, G>, fit_spline_cubic) and the PID
+ * rollout that tracks them: waypoints -> curve -> closed loop without leaving the GPU.  The group is an sfb_pid_group,
+ * elements and tangents are stored as for sfb_pid_*.  A spline has nknots = S + 1 >= 2 knots; per agent
+ *   tk [S+1] knot times, strictly increasing | gk [S+1][elem] knot elements | V [S][3][dof] control differences
+ * and the curve on segment i is g_i exp(B_1(u) v_i1) exp(B_2(u) v_i2) exp(B_3(u) v_i3) with the cumulative cubic Bernstein
+ * basis, u = (s - tk[i]) / (tk[i+1] - tk[i]).  Before tk[0] the value is (g_0, 0, 0), after tk[S] it is (g_S, 0, 0).
+ * spline_shared != 0: ONE spline (tk, gk, V) for every agent.  ts0 [batch], nullable (NULL: 0): agent b sees its spline at
+ * time t - ts0[b], so a shared curve can be flown staggered.  One agent per GPU lane, a bundle part by part.  Device
+ * pointers, asynchronous on `stream`.  SFB_ERR_INVALID_ARG, in this order, for a bad descriptor, batch < 0, nknots < 2,
+ * nt < 0, steps < 0, a non-finite t0 / dt, a negative or NaN windup_limit, a NULL array with work to do; then
+ * SFB_ERR_NO_DEVICE without a device: all before any device work, and there is no CPU fallback.  The device entry
+ * points cannot see the knot times and trust them; the _host variants also refuse, when there is work to do (batch > 0,
+ * and nt > 0 or steps > 0), knot times that are not finite and strictly increasing.
+ * ---------------------------------------------------------------------------------------- */
+/* The interpolating C^1 cubic through gk at tk (fit_spline_cubic; tk_shared != 0: one row of knot times for every agent).
+ * Out: V.  Precondition: consecutive knots, after the end-velocity corrections, stay away from rotation angle pi. */
+sfb_status sfb_spline_fit_cubic_batch(const sfb_pid_group *group, int64_t batch, int64_t nknots, const double *tk,
+                                      int tk_shared, const double *gk, double *V, void *stream);
+/* nt times per agent: t [batch][nt], or [nt] with t_shared != 0.  Out: g [batch][nt][elem], body velocity vel and body
+ * acceleration acc [batch][nt][dof].  nt == 0 writes nothing. */
+sfb_status sfb_spline_eval_batch(const sfb_pid_group *group, int64_t batch, int64_t nknots, const double *tk,
+                                 const double *gk, const double *V, int spline_shared, const double *ts0, int64_t nt,
+                                 const double *t, int t_shared, double *g, double *vel, double *acc, void *stream);
+/* sfb_pid_rollout_batch with the spline as the desired trajectory: every other argument and all semantics are the same
+ * (tick k at t0 + k dt, clamp, closed-form double-integrator step, u_last, cost in tick order, steps == 0 writes
+ * nothing); agent b tracks (g, vel, acc) of its spline at t_k - ts0[b]. */
+sfb_status sfb_pid_rollout_spline_batch(const sfb_pid_group *group, int64_t batch, double t0, double dt, int64_t steps,
+                                        double *x, double *v, int64_t nknots, const double *tk, const double *gk,
+                                        const double *V, int spline_shared, const double *ts0, const double *kp,
+                                        const double *kd, const double *ki, int gains_shared, double windup_limit,
+                                        const double *u_max, double *i_err, double *t_last, double *u_last, double *cost,
+                                        void *stream);
+/* Host-pointer variants (stage through device memory, synchronous). */
+sfb_status sfb_spline_fit_cubic_batch_host(const sfb_pid_group *group, int64_t batch, int64_t nknots, const double *tk,
+                                           int tk_shared, const double *gk, double *V);
+sfb_status sfb_spline_eval_batch_host(const sfb_pid_group *group, int64_t batch, int64_t nknots, const double *tk,
+                                      const double *gk, const double *V, int spline_shared, const double *ts0,
+                                      int64_t nt, const double *t, int t_shared, double *g, double *vel, double *acc);
+sfb_status sfb_pid_rollout_spline_batch_host(const sfb_pid_group *group, int64_t batch, double t0, double dt,
+                                             int64_t steps, double *x, double *v, int64_t nknots, const double *tk,
+                                             const double *gk, const double *V, int spline_shared, const double *ts0,
+                                             const double *kp, const double *kd, const double *ki, int gains_shared,
+                                             double windup_limit, const double *u_max, double *i_err, double *t_last,
+                                             double *u_last, double *cost);
+
 /*
  * Synthetic workload of the reference benchmark: random_qp(m, n, density, rng)
  * (benchmarks/bench_types.hpp:19-41) drawn `batch` times from ONE std::default_random_engine

@@ -3,7 +3,8 @@
 // The reference gets this from pettni/smooth (absent here): right-invariant conventions
 //   rplus(g, a) = g * exp(a),  rminus(a, b) = log(b^-1 * a),  body velocities d^r x_t = f
 // (reference README.md:17-18, mpc.hpp:498,505,518, ekf.hpp:137).  Only what the hot path's callers
-// need is restated: R^n, SE(2), SO(3), SE(3) and Bundle<...> with exp/log, ad and dr_expinv (the inverse right
+// need is restated: R^n, SE(2), SO(3), SE(3) and Bundle<...> with exp/log, ad, the group adjoint Ad (as an action on a
+// tangent: Ad_g a = vee(g hat(a) g^-1), what the splines of spline.hpp need) and dr_expinv (the inverse right
 // Jacobian used by MPCCE::jacobian, mpc.hpp:293-301).  Semantics as summarised in SURVEY.md section
 // 8 ("smooth semantics the host side must restate").  Every operation is pinned to 60-digit values computed from the
 // matrix groups (tests/golden/lie_reference.npz; tests/test_lie_host.py on the host, tests/test_lie_gpu.py in device code;
@@ -96,6 +97,7 @@ struct Rn {
     return t;
   }
   SFB_LIE_HD static Mat<N, N> ad(const Tangent &) { return Mat<N, N>::Zero(); }
+  SFB_LIE_HD Tangent Ad(const Tangent &a) const { return a; }  // Ad_g a = vee(g hat(a) g^-1): commutative
   SFB_LIE_HD static Mat<N, N> dr_expinv(const Tangent &) { return Mat<N, N>::Identity(); }
 };
 
@@ -175,6 +177,8 @@ struct SE2 {
     m(1, 0) = a[2];  m(1, 2) = -a[0];
     return m;
   }
+  // Ad_g a = vee(g hat(a) g^-1) = (R v - omega J p, omega),  J = [[0, -1], [1, 0]]
+  SFB_LIE_HD Tangent Ad(const Tangent &a) const { return {c * a[0] - s * a[1] + a[2] * y, s * a[0] + c * a[1] - a[2] * x, a[2]}; }
   // inverse of the right Jacobian of exp:  I + ad/2 + (1/th^2 - (1+cos th)/(2 th sin th)) ad^2
   SFB_LIE_HD static Mat<3, 3> dr_expinv(const Tangent &a)
   {
@@ -238,6 +242,12 @@ struct SO3 {
     m(1, 0) = a[2];  m(1, 2) = -a[0];
     m(2, 0) = -a[1]; m(2, 1) = a[0];
     return m;
+  }
+  // Ad_q a = R(q) a = a + w t + u x t with t = 2 u x a, u the vector part
+  SFB_LIE_HD Tangent Ad(const Tangent &a) const
+  {
+    const double t0 = 2.0 * (y * a[2] - z * a[1]), t1 = 2.0 * (z * a[0] - x * a[2]), t2 = 2.0 * (x * a[1] - y * a[0]);
+    return {a[0] + w * t0 + (y * t2 - z * t1), a[1] + w * t1 + (z * t0 - x * t2), a[2] + w * t2 + (x * t1 - y * t0)};
   }
   SFB_LIE_HD static Mat<3, 3> dr_expinv(const Tangent &a)
   {
@@ -367,6 +377,12 @@ struct SE3 {
     m(2, 3) = -a[1]; m(2, 4) = a[0];
     return m;
   }
+  // Ad_g (v, w) = vee(g hat(a) g^-1) = (R v + p x R w, R w)
+  SFB_LIE_HD Tangent Ad(const Tangent &a) const
+  {
+    const Vec<3> rv = rotate(q, {a[0], a[1], a[2]}), rw = rotate(q, {a[3], a[4], a[5]}), pw = detail::cross(p, rw);
+    return {rv[0] + pw[0], rv[1] + pw[1], rv[2] + pw[2], rw[0], rw[1], rw[2]};
+  }
   // inverse of the right Jacobian of exp, sum_n B_n^+ ad^n / n!, in block form: ad is block upper triangular with equal
   // diagonal blocks, so a function of it is [[J, Q], [0, J]] with J = SO3::dr_expinv(w) = I + W/2 + k W^2 and Q the
   // derivative of J in the direction v:  Q = V/2 + k (W V + V W) + 2 (w.v) k'(th^2) W^2   (W = hat(w), V = hat(v))
@@ -437,6 +453,16 @@ struct Bundle {
     for_parts([&](auto I, int off) {
       using G       = std::tuple_element_t<decltype(I)::value, std::tuple<Gs...>>;
       const auto ti = rminus(std::get<decltype(I)::value>(a.parts), std::get<decltype(I)::value>(b.parts));
+      for (int i = 0; i < G::Dof; ++i) t[off + i] = ti[i];
+    });
+    return t;
+  }
+  SFB_LIE_HD Tangent Ad(const Tangent &a) const  // per part
+  {
+    Tangent t{};
+    for_parts([&](auto I, int off) {
+      using G       = std::tuple_element_t<decltype(I)::value, std::tuple<Gs...>>;
+      const auto ti = std::get<decltype(I)::value>(parts).Ad(seg<G::Dof, 0>(a, off));
       for (int i = 0; i < G::Dof; ++i) t[off + i] = ti[i];
     });
     return t;

@@ -5,9 +5,8 @@
 // below calls it for one controller on the CPU (one controller has nothing to send to a GPU: O(dim) arithmetic), the
 // batched kernels of libsfb.so (csrc/pid.hip, sfb_pid_step_batch / sfb_pid_rollout_batch) and the device swarm front
 // (pid_device.hpp) call it for one agent per GPU lane.  Next to it: the double-integrator step that closes the loop on
-// that system, and the flat storage of a group element the C-ABI uses.
-//
-// Not mirrored: the smooth::Spline overloads of set_xdes (pid.hpp:142-159) -- pettni/smooth is absent.
+// that system, and the flat storage of a group element the C-ABI uses.  The Spline overloads of set_xdes (pid.hpp:142-159)
+// take the Spline<K, G> of spline.hpp, which this header includes at its end.
 #pragma once
 #include <cmath>
 #include <functional>
@@ -20,6 +19,10 @@
 #include "time.hpp"
 
 namespace smooth_feedback_amd {
+
+template<int K, class G>
+  requires(K >= 1 && K <= 5)
+class Spline;  // spline.hpp
 
 /// pid.hpp:17-21
 struct PIDParams {
@@ -227,7 +230,24 @@ public:
   /// pid.hpp:134
   void reset_integral() { i_err_.fill(0.0); }
 
-  /// pid.hpp:177-186 (the Spline overloads have no counterpart here)
+  /// pid.hpp:142-159: track a spline whose time 0 is t0 -- the desired triple at t is the spline at
+  /// time_trait<T>::minus(t, t0) (held pose at rest outside its knots)
+  template<int K>
+  void set_xdes(T t0, const Spline<K, G> & c)
+  {
+    set_xdes(t0, Spline<K, G>(c));
+  }
+  template<int K>
+  void set_xdes(T t0, Spline<K, G> && c)
+  {
+    x_des_ = [t0 = std::move(t0), c = std::move(c)](T t) -> TrajectoryReturnT {
+      Tangent vel{}, acc{};
+      G g = c(time_trait<T>::minus(t, t0), vel, acc);
+      return TrajectoryReturnT(std::move(g), std::move(vel), std::move(acc));
+    };
+  }
+
+  /// pid.hpp:177-186
   void set_xdes(const std::function<TrajectoryReturnT(T)> & f)
   {
     auto f_copy = f;
@@ -250,3 +270,5 @@ private:
 };
 
 }  // namespace smooth_feedback_amd
+
+#include "spline.hpp"

@@ -12,8 +12,9 @@ from .qp import (QPBatchSolution, QPSolution, QPSolutionStatus, QPSolver, QPSolv
 
 from .ekf import (ekf_predict_batch_device, ekf_predict_batch_host, ekf_predict_stepper_batch_device,  # noqa: F401
                   ekf_predict_update_batch_device, ekf_step_batch_host, ekf_update_batch_device)
-from .pid import (PIDGroup, pid_rollout_batch_device, pid_rollout_batch_host, pid_step_batch_device,  # noqa: F401
-                  pid_step_batch_host)
+from .pid import (PIDGroup, pid_rollout_batch_device, pid_rollout_batch_host, pid_rollout_spline_batch_host,  # noqa: F401
+                  pid_step_batch_device, pid_step_batch_host)
+from .spline import spline_eval_batch_host, spline_fit_cubic_batch_host  # noqa: F401
 from .mpc import LIE_RN, LIE_SE2, LIE_SE3, LIE_SO3, MPCLayout, MPCSwarm  # noqa: F401
 
 __version__ = "0.1.0"

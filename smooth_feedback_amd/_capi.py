@@ -130,6 +130,12 @@ def _load():
     L.sfb_pid_step_batch.argtypes = L.sfb_pid_step_batch_host.argtypes + [vp]
     L.sfb_pid_rollout_batch_host.argtypes = [grp, i64, dbl, dbl, i64] + [dp] * 4 + [i32] + [dp] * 3 + [i32, dbl] + [dp] * 5
     L.sfb_pid_rollout_batch.argtypes = L.sfb_pid_rollout_batch_host.argtypes + [vp]
+    L.sfb_spline_fit_cubic_batch_host.argtypes = [grp, i64, i64, dp, i32, dp, dp]
+    L.sfb_spline_fit_cubic_batch.argtypes = L.sfb_spline_fit_cubic_batch_host.argtypes + [vp]
+    L.sfb_spline_eval_batch_host.argtypes = [grp, i64, i64, dp, dp, dp, i32, dp, i64, dp, i32, dp, dp, dp]
+    L.sfb_spline_eval_batch.argtypes = L.sfb_spline_eval_batch_host.argtypes + [vp]
+    L.sfb_pid_rollout_spline_batch_host.argtypes = [grp, i64, dbl, dbl, i64, dp, dp, i64, dp, dp, dp, i32, dp] + [dp] * 3 + [i32, dbl] + [dp] * 5
+    L.sfb_pid_rollout_spline_batch.argtypes = L.sfb_pid_rollout_spline_batch_host.argtypes + [vp]
     lay = C.POINTER(SfbMPCLayout)
     L.sfb_mpc_record_doubles.argtypes = [lay, i32]
     L.sfb_mpc_record_doubles.restype = i64

@@ -107,6 +107,56 @@ def pid_rollout_batch_host(group, t0, dt, steps, x, v, g_des0, v_des, kp, kd, ki
     return dict(x=x, v=v, i_err=ie, t_last=tl, u_last=u, cost=cost)
 
 
+def _spline_arrays(g, B, tk, gk, V, ts0):
+    """the spline arguments of the C-ABI: tk (S+1,), gk (S+1, elem), V (S, 3, dof) for ONE shared spline, or each with a
+    leading batch axis; ts0 (B,) or None.  -> tk, gk, V, shared flag, nknots, ts0"""
+    tk = np.ascontiguousarray(tk, dtype=np.float64)
+    gk = np.ascontiguousarray(gk, dtype=np.float64)
+    V = np.ascontiguousarray(V, dtype=np.float64)
+    shared = 1 if tk.ndim == 1 else 0
+    K = tk.shape[-1]
+    lead = () if shared else (B,)
+    if tk.shape != lead + (K,) or gk.shape != lead + (K, g.elem) or V.shape != lead + (K - 1, 3, g.dof):
+        raise ValueError("spline: expected tk %r, gk %r, V %r (all shared or all per agent), got %r, %r, %r"
+                         % (lead + (K,), lead + (K, g.elem), lead + (K - 1, 3, g.dof), tk.shape, gk.shape, V.shape))
+    if ts0 is not None:
+        ts0 = np.ascontiguousarray(ts0, dtype=np.float64)
+        if ts0.shape != (B,):
+            raise ValueError("ts0: expected shape (%d,), got %r" % (B, ts0.shape))
+    return tk, gk, V, shared, K, ts0
+
+
+def pid_rollout_spline_batch_host(group, t0, dt, steps, x, v, tk, gk, V, kp, kd, ki, i_err, t_last, ts0=None, windup_limit=np.inf, u_max=None):
+    """pid_rollout_batch_host with a cubic spline as the desired trajectory (sfb_pid_rollout_spline_batch_host): agent b
+    tracks its spline -- tk (B, S+1), gk (B, S+1, elem), V (B, S, 3, dof) as spline_fit_cubic_batch_host returns them, or
+    ONE spline without the batch axis -- at t_k - ts0[b] (ts0 (B,) or None: 0).  Everything else, and the returned dict, as
+    pid_rollout_batch_host."""
+    g = _group(group)
+    x = np.array(x, dtype=np.float64, order="C")
+    B = x.shape[0]
+    x = np.array(_rows(x, B, g.elem, "x")[0])
+    v = np.array(_rows(v, B, g.dof, "v")[0])
+    tk, gk, V, shared, K, ts0 = _spline_arrays(g, B, tk, gk, V, ts0)
+    kp, f0 = _rows(kp, B, g.dof, "kp", True)
+    kd, f1 = _rows(kd, B, g.dof, "kd", True)
+    ki, f2 = _rows(ki, B, g.dof, "ki", True)
+    gains_shared = _shared_together([f0, f1, f2], "kp, kd, ki")
+    ie = np.array(_rows(i_err, B, g.dof, "i_err")[0])
+    tl = np.array(_rows(np.reshape(t_last, (-1, 1)), B, 1, "t_last")[0]).reshape(B)
+    um = None
+    if u_max is not None:
+        um = np.ascontiguousarray(u_max, dtype=np.float64)
+        if um.shape != (g.dof,):
+            raise ValueError("u_max: expected shape (%d,), got %r" % (g.dof, um.shape))
+    u = np.zeros((B, g.dof))
+    cost = np.zeros(B)
+    _capi.check(_capi.lib.sfb_pid_rollout_spline_batch_host(C.byref(g.c), B, float(t0), float(dt), int(steps), _ptr(x), _ptr(v), K, _ptr(tk), _ptr(gk),
+                                                            _ptr(V), shared, _ptr(ts0) if ts0 is not None else None, _ptr(kp), _ptr(kd), _ptr(ki),
+                                                            gains_shared, float(windup_limit), _ptr(um) if um is not None else None, _ptr(ie),
+                                                            _ptr(tl), _ptr(u), _ptr(cost)))
+    return dict(x=x, v=v, i_err=ie, t_last=tl, u_last=u, cost=cost)
+
+
 def pid_step_batch_device(group, B, t, dx, dv, dg_des, dv_des, da_des, des_shared, dkp, dkd, dki, gains_shared, windup_limit, di_err, dt_last, du,
                           stream=0):
     """sfb_pid_step_batch on device pointers (ints), asynchronous on `stream`."""
