@@ -980,7 +980,7 @@ int sfbx_test_ekf(double * err)
 
 int sfbx_mesh(int n_ivals, int K, double * nodes, double * weights, double * Dus)
 {
-  Mesh m(n_ivals, K);
+  UniformMesh m(n_ivals, K);
   for (int i = 0; i <= m.N_colloc(); ++i) {
     nodes[i] = m.node(i);
     weights[i] = m.weight(i);

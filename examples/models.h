@@ -171,6 +171,36 @@ int sfbx_pid_rollout_spline_host(int group, int64_t batch, double t0, double dt,
 /* mesh: nodes (N+1), weights (N+1), Dus ((K+1)*K col-major) for `n` intervals of K points */
 int sfbx_mesh(int n_ivals, int K, double *nodes, double *weights, double *Dus);
 
+/* ---- collocation layer (collocation.cpp): the ph mesh Mesh<kmin, kmax> for <5,10>, <5,5>, <8,8>, <3,6>, <4,4>, <13,13> (-1: no such
+ * instantiation) built as Mesh(n, k) and driven by an op script: ops [nops][3] rows (code, a, b) with 0 refine_ph(a, b),
+ * 1 increase_degrees, 2 decrease_degrees, 3 set_N_colloc_ival(a, b), 4 refine_errors taking (target, errs[N_ivals]) from
+ * opdata.  Out: nivals (-3 when above cap_ivals), K, tau0 [nivals], all nodes / weights [N + 1], the interval
+ * differentiation ((K + 1) x K) and integration (K x K) matrices row-major and concatenated, and for nt times t
+ * eval(t, vals, p, extend) [nt][dim] with interval_find(t) in found. */
+int sfbx_mesh_script(int kmin, int kmax, int n, int k, int nops, const int32_t *ops, const double *opdata, int cap_ivals,
+                     int32_t *nivals, int32_t *K, double *tau0, double *nodes, double *weights, double *diffmat, double *intmat,
+                     int nt, const double *t, int dim, const double *vals, int p, int extend, double *eval_out, int32_t *found);
+/* mesh_dyn_error on the script's mesh with its degrees raised by one; x(t), u(t) are the script's mesh polynomials through
+ * vals_x [N + 1][nx] (extended) and vals_u [N][nu] (not extended).  Built-in dynamics fid: 0 time only, the derivative of
+ * sum_k coef[d][k] t^k (coef [nx][4]); 1 harmonic pairs (x2, -x1); 2 pendulum pairs (x2, -sin x1 + u[pair mod nu]).
+ * (nx, nu) in {(1,0), (1,1), (2,0), (2,1), (2,2), (12,2)} (-5 otherwise).  Out: errs [nivals]. */
+int sfbx_mesh_dyn_error_host(int kmin, int kmax, int n, int k, int nops, const int32_t *ops, const double *opdata, int fid,
+                             const double *coef, int nx, int nu, double t0, double tf, const double *vals_x, const double *vals_u,
+                             double *errs);
+/* flat_dynamics of model 0 (vehicle, SE2 x R^3, inputs R^2) / 1 (rigid body, SE3 x R^6, inputs R^6), row by row: elements
+ * xl, ul in the flat storage of lie_eval.h, tangents dxl, e [rows][Nx], v [rows][Nu].  Out: [rows][Nx]. */
+int sfbx_flat_dynamics_host(int model, int rows, const double *xl, const double *dxl, const double *ul, const double *e,
+                            const double *v, double *out);
+/* MPC::dyn_error(t[b], primal[b]) of the host front for GIVEN primals [batch][n] (variant 6 / 12: the vehicles, 13: the rigid
+ * body; -1 otherwise).  Out: errs [batch][ceil(K / 4)]. */
+int sfbx_mpc_dyn_error_host(int variant, int K, double tf, int64_t batch, const double *t, const double *primal, double *errs);
+/* one tick of the host front from the state xdes(t) (+) dx0 at time t, then MPC::dyn_error(t) of the plan it stored; before
+ * the tick dyn_error(t) must throw (-3 if it does not).  Out: errs [ceil(K / 4)], the tick's status code. */
+int sfbx_mpc_tick_dyn_error_host(int variant, int K, double tf, double t, const double *dx0, double *errs, int32_t *code);
+/* the reference's mesh and dyn-error tests as caller code against <smooth/feedback/collocation/{mesh,dyn_error}.hpp>: 0, or the number of
+ * the first expectation that fails */
+int sfbx_test_collocation_api(void);
+
 #ifdef __cplusplus
 }
 #endif

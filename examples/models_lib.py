@@ -479,3 +479,119 @@ def pid_swarm_spline_device(t0, dt, steps, x, v, ie, t_last, kp, kd, ki, tk, gk,
                                                 C.c_double(windup), None if um is None else _p(um), *[_p(out[k]) for k in ("x", "v", "ie", "u", "cost")])
     assert rc == 0, rc
     return out
+
+
+# ---- collocation layer (examples/collocation.cpp)
+def _script_args(spec, ops, opdata):
+    ops = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 3)
+    opdata = np.ascontiguousarray(opdata if opdata is not None else [], dtype=np.float64)
+    kmin, kmax, n, k = [int(v) for v in spec]
+    return (kmin, kmax, n, k, len(ops), _p(ops), _p(opdata)), (ops, opdata)
+
+
+def mesh_script(spec, ops=(), opdata=None, t=(), vals=None, p=0, extend=True, cap_ivals=256):
+    """Mesh<kmin, kmax>(n, k) (spec = kmin, kmax, n, k) after the op script (sfbx_mesh_script): dict K, tau0, nodes, weights,
+    diffmat / intmat (lists of per-interval matrices), and with times t and node values vals (N (+1), dim): eval (nt, dim),
+    found (nt,).  Raises LookupError for an instantiation the harness does not carry."""
+    args, keep = _script_args(spec, ops, opdata)
+    kcap = int(spec[1]) + 1
+    nivals = C.c_int32()
+    K = np.zeros(cap_ivals, np.int32); tau0 = np.zeros(cap_ivals)
+    nodes = np.zeros(cap_ivals * kcap + 1); weights = np.zeros_like(nodes)
+    D = np.zeros(cap_ivals * (kcap + 1) * kcap); I = np.zeros(cap_ivals * kcap * kcap)
+    t = np.ascontiguousarray(t, dtype=np.float64)
+    vals = np.ascontiguousarray(vals if vals is not None else np.zeros((cap_ivals * kcap + 1, 1)), dtype=np.float64)
+    ev = np.zeros((len(t), vals.shape[1])); found = np.zeros(len(t), np.int32)
+    rc = lib().sfbx_mesh_script(*args, cap_ivals, C.byref(nivals), _p(K), _p(tau0), _p(nodes), _p(weights), _p(D), _p(I), len(t), _p(t),
+                                vals.shape[1], _p(vals), int(p), 1 if extend else 0, _p(ev), _p(found))
+    if rc == -1:
+        raise LookupError("no Mesh<%d, %d> in the harness" % (spec[0], spec[1]))
+    assert rc == 0, rc
+    n = nivals.value
+    K = K[:n].copy()
+    N = int(K.sum())
+    dm, im, a, b = [], [], 0, 0
+    for k in K:
+        dm.append(D[a:a + (k + 1) * k].reshape(k + 1, k)); a += (k + 1) * k
+        im.append(I[b:b + k * k].reshape(k, k)); b += k * k
+    return {"K": K, "tau0": tau0[:n].copy(), "nodes": nodes[:N + 1].copy(), "weights": weights[:N + 1].copy(), "diffmat": dm, "intmat": im,
+            "eval": ev, "found": found}
+
+
+def mesh_dyn_error_host(spec, ops, opdata, fid, coef, t0, tf, vals_x, vals_u):
+    """mesh_dyn_error on the script's mesh raised by one degree, for the built-in dynamics `fid` (sfbx_mesh_dyn_error_host)."""
+    args, keep = _script_args(spec, ops, opdata)
+    vals_x = np.ascontiguousarray(vals_x, dtype=np.float64); vals_u = np.ascontiguousarray(vals_u, dtype=np.float64)
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    errs = np.full(4096, np.nan)
+    rc = lib().sfbx_mesh_dyn_error_host(*args, int(fid), _p(coef), vals_x.shape[1], vals_u.shape[1], C.c_double(t0), C.c_double(tf), _p(vals_x),
+                                        _p(vals_u), _p(errs))
+    assert rc == 0, rc
+    return errs[~np.isnan(errs)]
+
+
+def flat_dynamics_host(model, xl, dxl, ul, e, v):
+    """flat_dynamics of model 0 (vehicle) / 1 (rigid body), row by row (sfbx_flat_dynamics_host)."""
+    xl, dxl, ul, e, v = [np.ascontiguousarray(a, dtype=np.float64) for a in (xl, dxl, ul, e, v)]
+    out = np.zeros_like(e)
+    assert lib().sfbx_flat_dynamics_host(int(model), len(e), _p(xl), _p(dxl), _p(ul), _p(e), _p(v), _p(out)) == 0
+    return out
+
+
+def mpc_dyn_error_host(variant, K, tf, t, primal):
+    """MPC::dyn_error of the host front for given primals (B, n) at times t (B,) -> (B, ceil(K / 4)) (sfbx_mpc_dyn_error_host)."""
+    primal = np.ascontiguousarray(np.atleast_2d(primal), dtype=np.float64)
+    B = len(primal)
+    t = np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.float64), (B,)))
+    errs = np.zeros((B, -(-K // 4)))
+    assert primal.shape[1] == mpc_dims(variant, K)["n"], primal.shape
+    assert lib().sfbx_mpc_dyn_error_host(variant, K, C.c_double(tf), C.c_int64(B), _p(t), _p(primal), _p(errs)) == 0
+    return errs
+
+
+def mpc_tick_dyn_error_host(variant, K, tf, t, dx0):
+    """one tick of the host front from xdes(t) (+) dx0, then MPC::dyn_error(t) of its plan -> (errs, status code)."""
+    x = np.ascontiguousarray(dx0, dtype=np.float64)
+    errs, code = np.zeros(-(-K // 4)), C.c_int32()
+    rc = lib().sfbx_mpc_tick_dyn_error_host(variant, K, C.c_double(tf), C.c_double(t), _p(x), _p(errs), C.byref(code))
+    assert rc == 0, rc
+    return errs, code.value
+
+
+def mpc_audit_device(variant, K, tf, t, primal, code=None):
+    """the fused audit kernel of mesh_device.hpp on given plans (B, n) (sfbx_mpc_audit_device) -> dict errs (B, nivals),
+    agent_max (B,), ival_max (nivals,), skipped."""
+    primal = np.ascontiguousarray(np.atleast_2d(primal), dtype=np.float64)
+    B, nivals = len(primal), -(-K // 4)
+    assert primal.shape[1] == mpc_dims(variant, K)["n"], primal.shape
+    t = np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.float64), (B,)))
+    code = None if code is None else np.ascontiguousarray(code, dtype=np.int32)
+    errs, amax, imax, skipped = np.zeros((B, nivals)), np.zeros(B), np.zeros(nivals), C.c_int32(-1)
+    rc = dev_lib().sfbx_mpc_audit_device(variant, K, C.c_double(tf), C.c_int64(B), _p(t), _p(primal), _p(code) if code is not None else None,
+                                         _p(errs), _p(amax), _p(imax), C.byref(skipped))
+    assert rc == 0, rc
+    return {"errs": errs, "agent_max": amax, "ival_max": imax, "skipped": skipped.value}
+
+
+def mpc_swarm_devlin_audit(variant, K, tf, t, dx0, audit=True, target=1e-3):
+    """one tick of MPCSwarmDeviceLin from xdes(t[b]) (+) dx0[b], optionally its audit(), then the same tick again
+    (sfbx_mpc_swarm_devlin_audit) -> dict primal (B, n), code, u_next (B, Nu), and with audit: errs (B, nivals), agent_max,
+    ival_max, skipped, refined_ivals, audit_seconds (a second, warmed audit() call, wall clock), audit_kernel_seconds (its two launches between device
+    events, least of five); tick_seconds is the second tick (wall clock)."""
+    dx0 = np.ascontiguousarray(dx0, dtype=np.float64)
+    B, nivals, d = len(dx0), -(-K // 4), mpc_dims(variant, K)
+    t = np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.float64), (B,)))
+    primal, code, u_next = np.zeros((B, d["n"])), np.zeros(B, np.int32), np.zeros((B, d["Nu"]))
+    errs, amax, imax, skipped, refined = np.zeros((B, nivals)), np.zeros(B), np.zeros(nivals), C.c_int32(-1), C.c_int32(-1)
+    seconds = np.zeros(3)
+    rc = dev_lib().sfbx_mpc_swarm_devlin_audit(variant, K, C.c_double(tf), C.c_int64(B), _p(t), _p(dx0), 1 if audit else 0, C.c_double(target),
+                                               _p(primal), _p(code), _p(errs), _p(amax), _p(imax), C.byref(skipped), C.byref(refined), _p(u_next), _p(seconds))
+    assert rc == 0, rc
+    out = {"primal": primal, "code": code, "u_next": u_next, "tick_seconds": seconds[0]}
+    if audit:
+        out.update(audit_seconds=seconds[1], audit_kernel_seconds=seconds[2], errs=errs, agent_max=amax, ival_max=imax, skipped=skipped.value, refined_ivals=refined.value)
+    return out
+
+
+def test_collocation_api():
+    return lib().sfbx_test_collocation_api()

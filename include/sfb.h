@@ -534,6 +534,10 @@ sfb_status sfb_mpc_swarm_step_resident(sfb_mpc_swarm *swarm, const sfb_qp_params
 sfb_status sfb_mpc_swarm_set_jac_keep(sfb_mpc_swarm *swarm, const uint8_t *jac_keep, int64_t *record_doubles);
 /* Device buffers of the last tick (Ax [agents][nnzA], l, u [agents][m]) for inspection; valid until the next call. */
 sfb_status sfb_mpc_swarm_debug_buffers(sfb_mpc_swarm *swarm, const double **Ax, const double **l, const double **u);
+/* Device buffers of the last tick's solution (primal [agents][n], dual [agents][m], code [agents]; each nullable), for
+ * work that continues on the device, such as the dynamics-error audit of mesh_device.hpp; valid until the next call. */
+sfb_status sfb_mpc_swarm_device_solution(sfb_mpc_swarm *swarm, const double **primal, const double **dual,
+                                         const int32_t **code);
 
 /* ------------------------------------------------------------------------------------------
  * Batched Lie-group EKF: covariance propagation and Kalman update for `batch` independent filters.
@@ -685,6 +689,47 @@ sfb_status sfb_pid_rollout_spline_batch_host(const sfb_pid_group *group, int64_t
                                              const double *kp, const double *kd, const double *ki, int gains_shared,
                                              double windup_limit, const double *u_max, double *i_err, double *t_last,
                                              double *u_last, double *cost);
+
+/* ------------------------------------------------------------------------------------------
+ * ph collocation meshes (include/smooth_feedback_amd/mesh.hpp: Mesh<Kmin, Kmax>) and the batched dynamics-error
+ * estimate (include/smooth_feedback_amd/dyn_error.hpp; reference collocation/dyn_error.hpp:28-73).  Model-free: the
+ * caller evaluates its dynamics between the two calls, as with the EKF.
+ *   1. sfb_mesh_resample_batch carries node values of the mesh to the points of the same mesh with every degree raised
+ *      by one (K_s + 2 points per interval, the interval's end point included);
+ *   2. the caller evaluates F = f(t, X, U) at those points (their times: t0 + (tf - t0) tau, tau from sfb_mesh_raised_nodes);
+ *   3. sfb_mesh_dyn_error_batch integrates F through every interval and reports how far that lands from X.
+ * The mesh is described by HOST arrays (also in the device-pointer entry points): K [nivals] collocation points per
+ * interval, tau0 [nivals] interval starts on [0, 1], tau0[0] == 0, strictly increasing, below 1.  N = sum K.  The
+ * library builds the per-degree tables (resampling weights, integration matrices) on the host in double
+ * from the code of mesh.hpp and keeps them and the interval list on the device.  One GPU lane per (agent, interval,
+ * raised point).  SFB_ERR_INVALID_ARG, in this order, for a NULL mesh or mesh array, nivals < 1, a K below 1 or with
+ * K + 1 > 14, interval starts that are not as above, batch < 0, dim / nx < 0, a NULL array with work to do; then
+ * SFB_ERR_NO_DEVICE without a device: all before any device work, and there is no CPU fallback.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct sfb_mesh {
+  int32_t nivals;
+  const int32_t *K;   /* [nivals] host */
+  const double *tau0; /* [nivals] host */
+} sfb_mesh;
+/* The points of the degree-raised mesh on [0, 1]: tau [sum_s (K_s + 2)], interval by interval, both end points included
+ * (the order of the rows sfb_mesh_resample_batch writes).  Host arrays, CPU only: needs no device. */
+sfb_status sfb_mesh_raised_nodes(const sfb_mesh *mesh, double *tau);
+/* vals [batch][N + 1][dim] (extend != 0) or [batch][N][dim] (extend == 0: the last interval's polynomial goes through its
+ * own K points only, Mesh::eval with extend = false).  Out: out [batch][sum_s (K_s + 2)][dim], interval by interval; an
+ * interval's end point appears again as the next interval's first.  batch == 0 or dim == 0 writes nothing. */
+sfb_status sfb_mesh_resample_batch(const sfb_mesh *mesh, int64_t batch, int32_t dim, int extend, const double *vals,
+                                   double *out, void *stream);
+/* X, F [batch][sum_s (K_s + 2)][nx] in the layout sfb_mesh_resample_batch writes (F at an interval's end point is never
+ * read); horizon [batch] = tf - t0.  Out: errs [batch][nivals],
+ *   Xest_j = X_0 + horizon sum_{i < Ke} F_i I(i, j - 1),  err = max_j |Xest_j - X_j| / (1 + max_{j >= 1} |X_j|),
+ * Ke = K_s + 1, I the raised interval's integration matrix on [0, 1].  nx == 0 writes zeros. */
+sfb_status sfb_mesh_dyn_error_batch(const sfb_mesh *mesh, int64_t batch, int32_t nx, const double *horizon,
+                                    const double *X, const double *F, double *errs, void *stream);
+/* Host-pointer variants (stage through device memory, synchronous). */
+sfb_status sfb_mesh_resample_batch_host(const sfb_mesh *mesh, int64_t batch, int32_t dim, int extend, const double *vals,
+                                        double *out);
+sfb_status sfb_mesh_dyn_error_batch_host(const sfb_mesh *mesh, int64_t batch, int32_t nx, const double *horizon,
+                                         const double *X, const double *F, double *errs);
 
 /*
  * Synthetic workload of the reference benchmark: random_qp(m, n, density, rng)

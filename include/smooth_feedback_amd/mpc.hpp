@@ -25,10 +25,12 @@
 #include <optional>
 #include <limits>
 #include <memory>
+#include <stdexcept>
 #include <thread>
 #include <utility>
 #include <vector>
 
+#include "dyn_error.hpp"
 #include "lie.hpp"
 #include "mesh.hpp"
 #include "qp.hpp"
@@ -208,7 +210,7 @@ public:
   int ncon() const { return Nx * N() + Ncr * N() + Nx; }
   int uvar_B() const { return Nx * (N() + 1); }
   const QuadraticProgramSparse<> & qp() const { return qp_; }
-  const Mesh & mesh() const { return mesh_; }
+  const UniformMesh & mesh() const { return mesh_; }
   const MPCParams & params() const { return prm_; }
   SparseQPSolver & solver() { return solver_; }
   /// Elimination stages for the solver's constrained minimum-degree order (unknowns of a lower stage are eliminated
@@ -594,6 +596,51 @@ public:
     return solve_tick(t, x, u_traj, x_traj);
   }
 
+  /// Collocation dynamics-error estimate of a plan (collocation/dyn_error.hpp:28-73 on the flattened dynamics of
+  /// ocp_flatten.hpp:166-177), one figure per mesh interval: how far the TRUE dynamics, integrated through the
+  /// interval, land from the plan's polynomials, relative to the size of the state deviation.  The plan is the primal
+  /// [dx_0 .. dx_N | du_0 .. du_{N-1}] of a tick at time t: e(tau), v(tau) are the mesh polynomials through its node
+  /// values (as qpsol_to_ocpsol: x extended by the value at 1, u not), audited on the mesh with degrees raised by one.
+  std::vector<double> dyn_error(const T & t, const double * primal) const
+  {
+    // the law of the fused GPU audit (mesh_device.hpp), interval by interval: node values -> the Ke + 1 = Kmesh + 2 points
+    // of the raised interval by the resampling weights (Mesh::eval at those points, without going through a time and
+    // back), flat_dynamics at the first Ke, interval_dyn_error
+    constexpr int K = Kmesh, Ke = Kmesh + 1;
+    const MeshMat Wc = detail::resample_weights(K, true), Wo = detail::resample_weights(K, false);
+    const detail::LgrTable & up = detail::lgr_table(Ke);
+    const std::remove_cvref_t<F> f = f_;
+    const int nivals  = mesh_.N_ivals();
+    const double tf   = prm_.tf, half = 0.5 / (double)nivals;
+    const double * dx = primal, *du = primal + uvar_B();
+    std::vector<double> errs((std::size_t)nivals), Xv((std::size_t)(Ke + 1) * Nx), Fv((std::size_t)Ke * Nx);
+    for (int s = 0; s < nivals; ++s) {
+      const bool closed = s + 1 < nivals;
+      for (int p = 0; p <= Ke; ++p) {
+        TangentX e{};
+        typename U::Tangent v{};
+        for (int i = 0; i <= K; ++i) {
+          for (int d = 0; d < Nx; ++d) e[d] += Wc(p, i) * dx[(std::size_t)(s * K + i) * Nx + d];
+          if (i < K || closed)
+            for (int d = 0; d < Nu; ++d) v[d] += (closed ? Wc(p, i) : Wo(p, i)) * du[(std::size_t)(s * K + i) * Nu + d];
+        }
+        for (int d = 0; d < Nx; ++d) Xv[(std::size_t)p * Nx + d] = e[d];
+        if (p == Ke) break;  // the dynamics at the interval's end point are not used
+        const T ts        = tplus(t, tf * ((double)s / (double)nivals + half * (up.tau[(std::size_t)p] + 1.0)));
+        const TangentX fv = flat_dynamics(f, des_->xdes(ts), des_->dxdes(ts), des_->udes(ts), e, v);
+        for (int d = 0; d < Nx; ++d) Fv[(std::size_t)p * Nx + d] = fv[d];
+      }
+      errs[(std::size_t)s] = interval_dyn_error(Ke, Nx, Xv.data(), Nx, Fv.data(), Nx, up.Ius.a.data(), tf * half);
+    }
+    return errs;
+  }
+  /// ... of the plan the last operator() call solved for (whatever its status); throws if there is none
+  std::vector<double> dyn_error(const T & t) const
+  {
+    if (last_primal_.empty()) throw std::logic_error("MPC::dyn_error: no solution stored (call operator() first)");
+    return dyn_error(t, last_primal_.data());
+  }
+
 private:
   std::pair<U, QPSolutionStatus> solve_tick(const T & t, const X & x, std::vector<U> * u_traj, std::vector<X> * x_traj)
   {
@@ -605,7 +652,7 @@ private:
       probe_default(t, keep);
       analyze_solver(&keep);
     }
-    const QPSolution<> sol = solver_.solve(qp_, warm_ ? &*warm_ : nullptr);  // :491
+    QPSolution<> sol = solver_.solve(qp_, warm_ ? &*warm_ : nullptr);  // :491
     const int Nn = N();
     if (u_traj) {  // :494-500
       u_traj->resize(Nn);
@@ -627,7 +674,9 @@ private:
         (sol.code == QPSolutionStatus::Optimal || sol.code == QPSolutionStatus::MaxTime ||
          sol.code == QPSolutionStatus::MaxIterations))
       warm_ = sol;  // :510-516
-    return {input_from_primal(t, sol.primal.data()), sol.code};
+    const U u0 = input_from_primal(t, sol.primal.data());
+    last_primal_.swap(sol.primal);  // what dyn_error(t) audits: handed over, not copied
+    return {u0, sol.code};
   }
 
   // a new linearisation trajectory may have other explicit zeros: looked at by refresh_structure() at the next solve
@@ -716,7 +765,8 @@ private:
   CR cr_;
   Vec<Ncr> crl_{}, cru_{};
   MPCParams prm_{};
-  Mesh mesh_{};
+  UniformMesh mesh_{};
+  std::vector<double> last_primal_;
   std::shared_ptr<Des> des_ = std::make_shared<Des>();  // shared by copies, mpc.hpp:407
   QuadraticProgramSparse<> qp_;
   SparseQPSolver solver_;     // a copy drops the analysis (qp.hpp PlanHolder, qp_solver.hpp:209-231)

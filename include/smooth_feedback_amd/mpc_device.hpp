@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "detail/device_arena.hpp"
+#include "mesh_device.hpp"
 #include "mpc.hpp"
 
 namespace smooth_feedback_amd {
@@ -188,6 +189,62 @@ public:
       codes[(size_t)b] = static_cast<QPSolutionStatus>(code_[(size_t)b]);
     }
   }
+  /// what audit() brings back: 8 bytes per agent and per interval
+  struct Audit {
+    std::vector<double> agent_max;  // [agents] largest interval error of the agent's plan (NaN: the plan has a NaN)
+    std::vector<double> ival_max;   // [intervals] largest error over the agents whose plan the swarm keeps
+    int32_t skipped = 0;            // agents left out of ival_max (status not kept, or a NaN)
+  };
+  /// Dynamics-error audit (mesh_device.hpp: mpc_dyn_error_device) of the plans of the last step(), on the device, with
+  /// t the times that step was given.  `errs` (nullable) also receives the full [agents][intervals] table.  A separate
+  /// call: step() is as it was, and the next step() does not depend on it.
+  Audit audit(const double * t, std::vector<double> * errs = nullptr)
+  {
+    const int nivals = mpc_.mesh().N_ivals();
+    if (!daudit_.get()) {
+      detail::DeviceArena a;
+      a.add(&derrs_, (size_t)B_ * nivals); a.add(&damax_, (size_t)B_); a.add(&dimax_, (size_t)nivals); a.add(&dskip_, 1);
+      daudit_ = detail::DeviceBlock(a, "mpc_device");
+    }
+    const double * dprimal = nullptr;
+    const int32_t * dcode  = nullptr;
+    sfb_check(sfb_mpc_swarm_device_solution(swarm_, &dprimal, nullptr, &dcode));
+    check(detail::upload(dt_, t, (size_t)B_), "hipMemcpy(t)");
+    check(mpc_dyn_error_device(mpc_, model_, B_, dt_, dprimal, dcode, derrs_, damax_, dimax_, dskip_, nullptr), "mpc_audit_kernel");
+    Audit r;
+    r.agent_max.resize((size_t)B_);
+    r.ival_max.resize((size_t)nivals);
+    check(detail::download(r.agent_max.data(), damax_, (size_t)B_), "hipMemcpy(agent_max)");  // (synchronises with the launches)
+    check(detail::download(r.ival_max.data(), dimax_, (size_t)nivals), "hipMemcpy(ival_max)");
+    check(detail::download(&r.skipped, dskip_, 1), "hipMemcpy(skipped)");
+    if (errs) {
+      errs->resize((size_t)B_ * nivals);
+      check(detail::download(errs->data(), derrs_, errs->size()), "hipMemcpy(errs)");
+    }
+    return r;
+  }
+  /// the swarm's shared mesh refined where the audit's interval errors exceed `target` (Mesh::refine_errors);
+  /// rebuilding the swarm on it is the caller's business
+  Mesh<MPCT::Kmesh, MPCT::Kmesh> refined_mesh(const std::vector<double> & ival_max, double target) const
+  {
+    Mesh<MPCT::Kmesh, MPCT::Kmesh> m((std::size_t)mpc_.mesh().N_ivals(), (std::size_t)MPCT::Kmesh);
+    m.refine_errors(ival_max, target);
+    return m;
+  }
+  /// the solution of the last step() where it lies: device pointers, valid until the next call on the swarm
+  void device_solution(const double ** primal, const int32_t ** code) const
+  {
+    sfb_check(sfb_mpc_swarm_device_solution(swarm_, primal, nullptr, code));
+  }
+  /// the solution of the last step() (device -> host): primal [agents][n], code [agents]; each nullable
+  void copy_solution(double * primal, int32_t * code) const
+  {
+    const double * dprimal = nullptr;
+    const int32_t * dcode  = nullptr;
+    sfb_check(sfb_mpc_swarm_device_solution(swarm_, &dprimal, nullptr, &dcode));
+    if (primal) check(detail::download(primal, dprimal, (size_t)B_ * (size_t)mpc_.qp().n), "hipMemcpy(primal)");
+    if (code) check(detail::download(code, dcode, (size_t)B_), "hipMemcpy(code)");
+  }
   int64_t size() const { return B_; }
   const std::vector<uint32_t> & iterations() const { return iter_; }
   bool packed_records() const { return packed_; }
@@ -247,7 +304,9 @@ private:
   std::unique_ptr<typename MPCT::DeviceLayout> layout_;
   sfb_mpc_swarm * swarm_ = nullptr;
   Map map_{};
-  detail::DeviceBlock dmem_;
+  detail::DeviceBlock dmem_, daudit_;
+  double * derrs_ = nullptr, *damax_ = nullptr, *dimax_ = nullptr;
+  int32_t * dskip_ = nullptr;
   double * dtau_ = nullptr, *dt_ = nullptr, *drec_ = nullptr;
   X * dx_        = nullptr;
   int * dmisfit_ = nullptr;

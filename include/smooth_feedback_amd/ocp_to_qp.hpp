@@ -209,7 +209,7 @@ inline double & csr_at(const std::vector<int32_t> & ptr, const std::vector<int32
 
 /// ocp_to_qp_allocate, ocp_to_qp.hpp:40-114: sizes and the stored pattern (depends on the sizes only)
 template<class Ocp>
-void ocp_to_qp_allocate(QuadraticProgramSparse<> & qp, const Ocp &, const Mesh & mesh)
+void ocp_to_qp_allocate(QuadraticProgramSparse<> & qp, const Ocp &, const UniformMesh & mesh)
 {
   constexpr int Nx = Ocp::Nx, Nu = Ocp::Nu, Ncr = Ocp::Ncr, Nce = Ocp::Nce;
   const int N = mesh.N_colloc(), K = mesh.K;
@@ -283,7 +283,7 @@ void ocp_to_qp_allocate(QuadraticProgramSparse<> & qp, const Ocp &, const Mesh &
 /// xl_fun(t) -> X, ul_fun(t) -> U: linearisation trajectory on [0, tf]; dxl_fun(t) -> Vec<Nx>: its body velocity
 /// (nullptr-like empty std::function: central differences of xl_fun).
 template<class Ocp, class XL, class UL>
-void ocp_to_qp_update(QuadraticProgramSparse<> & qp, const Ocp & ocp, const Mesh & mesh, double tf, const XL & xl_fun,
+void ocp_to_qp_update(QuadraticProgramSparse<> & qp, const Ocp & ocp, const UniformMesh & mesh, double tf, const XL & xl_fun,
                       const UL & ul_fun, const std::function<Vec<Ocp::Nx>(double)> & dxl_fun = {})
 {
   using X = typename Ocp::X;
@@ -419,7 +419,7 @@ void ocp_to_qp_update(QuadraticProgramSparse<> & qp, const Ocp & ocp, const Mesh
 
 /// ocp_to_qp(), ocp_to_qp.hpp:421-435
 template<class Ocp, class XL, class UL>
-QuadraticProgramSparse<> ocp_to_qp(const Ocp & ocp, const Mesh & mesh, double tf, const XL & xl_fun, const UL & ul_fun,
+QuadraticProgramSparse<> ocp_to_qp(const Ocp & ocp, const UniformMesh & mesh, double tf, const XL & xl_fun, const UL & ul_fun,
                                    const std::function<Vec<Ocp::Nx>(double)> & dxl_fun = {})
 {
   QuadraticProgramSparse<> qp;
@@ -432,7 +432,7 @@ namespace detail {
 /// Mesh::eval (collocation/mesh.hpp:428-470), p = 0: Lagrange interpolation of the values r (one Vec<D> per node,
 /// N + 1 of them when `extend`, else N) in the interval that contains t in [0, 1].
 template<int D>
-Vec<D> mesh_eval(const Mesh & mesh, double t, const std::vector<Vec<D>> & r, bool extend)
+Vec<D> mesh_eval(const UniformMesh & mesh, double t, const std::vector<Vec<D>> & r, bool extend)
 {
   const int K = mesh.K, nI = mesh.N_ivals();
   int ival = (t <= 0) ? 0 : (t >= 1 ? nI - 1 : std::min(nI - 1, (int)(t * nI)));
@@ -453,7 +453,7 @@ Vec<D> mesh_eval(const Mesh & mesh, double t, const std::vector<Vec<D>> & r, boo
 
 /// qpsol_to_ocpsol(), ocp_to_qp.hpp:452-499
 template<class Ocp, class XL, class UL>
-OCPSolution<typename Ocp::X, typename Ocp::U> qpsol_to_ocpsol(const Ocp &, const Mesh & mesh, const QPSolution<> & qpsol, double tf,
+OCPSolution<typename Ocp::X, typename Ocp::U> qpsol_to_ocpsol(const Ocp &, const UniformMesh & mesh, const QPSolution<> & qpsol, double tf,
                                                               XL xl_fun, UL ul_fun)
 {
   using X = typename Ocp::X;

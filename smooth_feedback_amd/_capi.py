@@ -58,6 +58,12 @@ class SfbPIDGroup(C.Structure):
     _fields_ = [("nparts", C.c_int32), ("part_kind", C.c_void_p), ("part_dof", C.c_void_p)]
 
 
+class SfbMesh(C.Structure):
+    """sfb_mesh (include/sfb.h)."""
+
+    _fields_ = [("nivals", C.c_int32), ("K", C.c_void_p), ("tau0", C.c_void_p)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -136,6 +142,12 @@ def _load():
     L.sfb_spline_eval_batch.argtypes = L.sfb_spline_eval_batch_host.argtypes + [vp]
     L.sfb_pid_rollout_spline_batch_host.argtypes = [grp, i64, dbl, dbl, i64, dp, dp, i64, dp, dp, dp, i32, dp] + [dp] * 3 + [i32, dbl] + [dp] * 5
     L.sfb_pid_rollout_spline_batch.argtypes = L.sfb_pid_rollout_spline_batch_host.argtypes + [vp]
+    mesh = C.POINTER(SfbMesh)
+    L.sfb_mesh_raised_nodes.argtypes = [mesh, dp]
+    L.sfb_mesh_resample_batch_host.argtypes = [mesh, i64, i32, i32, dp, dp]
+    L.sfb_mesh_resample_batch.argtypes = L.sfb_mesh_resample_batch_host.argtypes + [vp]
+    L.sfb_mesh_dyn_error_batch_host.argtypes = [mesh, i64, i32, dp, dp, dp, dp]
+    L.sfb_mesh_dyn_error_batch.argtypes = L.sfb_mesh_dyn_error_batch_host.argtypes + [vp]
     lay = C.POINTER(SfbMPCLayout)
     L.sfb_mpc_record_doubles.argtypes = [lay, i32]
     L.sfb_mpc_record_doubles.restype = i64

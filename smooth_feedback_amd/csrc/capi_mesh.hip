@@ -1,0 +1,258 @@
+// C-ABI for the batched ph-mesh path (include/sfb.h): resampling onto the degree-raised mesh, dynamics-error estimate.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <vector>
+
+#include "../../include/sfb.h"
+#include "../../include/smooth_feedback_amd/mesh.hpp"
+#include "capi_common.h"
+#include "mesh_kernel.h"
+
+namespace {
+
+namespace L = smooth_feedback_amd;
+
+// what every entry point refuses first: the mesh, then the batch
+sfb_status mesh_check(const sfb_mesh *mesh, int64_t batch)
+{
+  if (!mesh || !mesh->K || !mesh->tau0) return sfb::fail(SFB_ERR_INVALID_ARG, "NULL mesh");
+  if (mesh->nivals < 1) return sfb::fail(SFB_ERR_INVALID_ARG, "mesh: nivals < 1");
+  for (int32_t s = 0; s < mesh->nivals; ++s)
+    if (mesh->K[s] < 1 || mesh->K[s] + 1 > sfb::kMeshMaxK + 1)
+      return sfb::fail(SFB_ERR_INVALID_ARG, "mesh: K outside 1 .. 13 (the raised interval has K + 1 <= 14 points)");
+  for (int32_t s = 0; s < mesh->nivals; ++s) {
+    const double t = mesh->tau0[s];
+    if (!(s == 0 ? t == 0.0 : t > mesh->tau0[s - 1]) || !(t < 1.0))
+      return sfb::fail(SFB_ERR_INVALID_ARG, "mesh: tau0 must start at 0, increase strictly and stay below 1");
+  }
+  if (batch < 0) return sfb::fail(SFB_ERR_INVALID_ARG, "batch < 0");
+  return SFB_OK;
+}
+
+int64_t mesh_nodes(const sfb_mesh *mesh)
+{
+  int64_t n = 0;
+  for (int32_t s = 0; s < mesh->nivals; ++s) n += mesh->K[s];
+  return n;
+}
+
+sfb_status resample_check(const sfb_mesh *mesh, int64_t batch, int32_t dim, const double *vals, double *out)
+{
+  const sfb_status st = mesh_check(mesh, batch);
+  if (st != SFB_OK) return st;
+  if (dim < 0) return sfb::fail(SFB_ERR_INVALID_ARG, "dim < 0");
+  if (batch > 0 && dim > 0 && (!vals || !out)) return sfb::fail(SFB_ERR_INVALID_ARG, "NULL array");
+  return SFB_OK;
+}
+
+sfb_status dyn_error_check(const sfb_mesh *mesh, int64_t batch, int32_t nx, const double *horizon, const double *X, const double *F, double *errs)
+{
+  const sfb_status st = mesh_check(mesh, batch);
+  if (st != SFB_OK) return st;
+  if (nx < 0) return sfb::fail(SFB_ERR_INVALID_ARG, "nx < 0");
+  if (batch > 0 && (!horizon || !errs || (nx > 0 && (!X || !F)))) return sfb::fail(SFB_ERR_INVALID_ARG, "NULL array");
+  return SFB_OK;
+}
+
+// The per-degree tables (once per device) and the interval lists of the meshes seen (per device and mesh content) live
+// on the device, so that an asynchronous launch never outlives what it reads.  A list is a few dozen bytes per
+// interval; when a device holds kMeshesKept distinct meshes its lists are dropped after a synchronise of that device.
+// The cache's lock is held from the lookup to the end of the launch call (with_device_mesh), so a thread that evicts
+// never frees a list between another thread's lookup and its launch; what has been launched is covered by the synchronise.
+constexpr size_t kMeshesKept = 64;
+struct MeshKey {
+  int device;
+  std::vector<int32_t> K;
+  std::vector<uint64_t> tau0;  // bit patterns
+  bool operator<(const MeshKey &o) const { return std::tie(device, K, tau0) < std::tie(o.device, o.K, o.tau0); }
+};
+struct MeshEntry {
+  sfb::DeviceBlock blk;
+  sfb::MeshDevice dev;
+};
+struct MeshCache {
+  std::mutex mu;
+  std::map<int, sfb::DeviceBlock> tables;
+  std::map<MeshKey, MeshEntry> meshes;
+};
+MeshCache &cache()
+{
+  static MeshCache *c = new MeshCache;  // never destroyed: device memory is not freed behind the runtime's back at exit
+  return *c;
+}
+
+std::vector<double> build_tables()
+{
+  constexpr int S = sfb::kMeshStride, T = S * S;
+  std::vector<double> t((size_t)sfb::kMeshMaxK * 3 * T, 0.0);
+  for (int K = 1; K <= sfb::kMeshMaxK; ++K) {
+    double *Wc = t.data() + (size_t)(K - 1) * 3 * T, *Wo = Wc + T, *I = Wo + T;
+    const L::MeshMat wc = L::detail::resample_weights(K, true), wo = L::detail::resample_weights(K, false);
+    const L::MeshMat &ius = L::detail::lgr_table(K + 1).Ius;
+    for (int j = 0; j < K + 2; ++j) {
+      for (int i = 0; i <= K; ++i) Wc[j * S + i] = wc(j, i);
+      for (int i = 0; i < K; ++i) Wo[j * S + i] = wo(j, i);
+    }
+    for (int j = 0; j <= K; ++j)
+      for (int i = 0; i <= K; ++i) I[j * S + i] = ius(i, j);
+  }
+  return t;
+}
+
+// launch(m) with the device copy of `mesh`, under the cache's lock
+template<class Launch>
+sfb_status with_device_mesh(const sfb_mesh *mesh, Launch &&launch)
+{
+  sfb::MeshDevice out{};
+  int device = 0;
+  hipError_t e = hipGetDevice(&device);
+  if (e != hipSuccess) return sfb::hip_fail(e, "hipGetDevice");
+  MeshCache &c = cache();
+  std::lock_guard<std::mutex> lock(c.mu);
+  auto tb = c.tables.find(device);
+  if (tb == c.tables.end()) {
+    const std::vector<double> t = build_tables();
+    sfb::DeviceBlock blk(t.size() * sizeof(double));
+    if (blk.error() != hipSuccess) return sfb::hip_fail(blk.error(), "hipMalloc");
+    if ((e = sfb::upload(static_cast<double *>(blk.get()), t.data(), t.size())) != hipSuccess) return sfb::hip_fail(e, "mesh tables upload");
+    tb = c.tables.emplace(device, std::move(blk)).first;
+  }
+  MeshKey key{device, std::vector<int32_t>(mesh->K, mesh->K + mesh->nivals), std::vector<uint64_t>(mesh->nivals)};
+  std::memcpy(key.tau0.data(), mesh->tau0, sizeof(double) * mesh->nivals);
+  auto it = c.meshes.find(key);
+  if (it == c.meshes.end()) {
+    size_t here = 0;
+    for (const auto &m : c.meshes) here += m.first.device == device ? 1 : 0;
+    if (here >= kMeshesKept) {
+      if ((e = hipDeviceSynchronize()) != hipSuccess) return sfb::hip_fail(e, "hipDeviceSynchronize");
+      for (auto m = c.meshes.begin(); m != c.meshes.end();) m = m->first.device == device ? c.meshes.erase(m) : std::next(m);
+    }
+    const int32_t n = mesh->nivals;
+    std::vector<sfb::MeshIval> iv(n);
+    std::vector<int32_t> rows;
+    int32_t N = 0, R = 0;
+    for (int32_t s = 0; s < n; ++s) {
+      const double tauf = s + 1 < n ? mesh->tau0[s + 1] : 1.0;
+      iv[s]             = sfb::MeshIval{mesh->K[s], N, R, s + 1 < n ? 1 : 0, (tauf - mesh->tau0[s]) / 2};
+      N += mesh->K[s];
+      R += mesh->K[s] + 2;
+      rows.insert(rows.end(), mesh->K[s] + 2, s);
+    }
+    sfb::Staging st;
+    sfb::MeshIval *div;
+    int32_t *drow;
+    st.add(&div, (size_t)n, sfb::Staging::In, iv.data());
+    st.add(&drow, rows.size(), sfb::Staging::In, rows.data());
+    MeshEntry ent;
+    const sfb_status rc = sfb::stage_per_call(st, ent.blk);
+    if (rc != SFB_OK) return rc;
+    if ((e = st.upload()) != hipSuccess) return sfb::hip_fail(e, "mesh upload");
+    ent.dev = sfb::MeshDevice{n, N, R, div, drow, nullptr};
+    it      = c.meshes.emplace(std::move(key), std::move(ent)).first;
+  }
+  out        = it->second.dev;
+  out.tables = static_cast<const double *>(tb->second.get());
+  return launch(out);
+}
+
+}  // namespace
+
+extern "C" {
+
+sfb_status sfb_mesh_resample_batch(const sfb_mesh *mesh, int64_t batch, int32_t dim, int extend, const double *vals, double *out, void *stream)
+{
+  sfb_status st = resample_check(mesh, batch, dim, vals, out);
+  if (st != SFB_OK) return st;
+  st = sfb::require_device();
+  if (st != SFB_OK) return st;
+  if (batch == 0 || dim == 0) return SFB_OK;
+  return with_device_mesh(mesh, [&](const sfb::MeshDevice &m) {
+    sfb::MeshResampleArgs a{};
+    a.m = m; a.batch = batch; a.dim = dim; a.extend = extend ? 1 : 0; a.vals = vals; a.out = out;
+    const hipError_t e = sfb::mesh_resample_launch(a, static_cast<hipStream_t>(stream));
+    return e != hipSuccess ? sfb::hip_fail(e, "mesh_resample_kernel launch") : SFB_OK;
+  });
+}
+
+sfb_status sfb_mesh_dyn_error_batch(const sfb_mesh *mesh, int64_t batch, int32_t nx, const double *horizon, const double *X, const double *F,
+                                    double *errs, void *stream)
+{
+  sfb_status st = dyn_error_check(mesh, batch, nx, horizon, X, F, errs);
+  if (st != SFB_OK) return st;
+  st = sfb::require_device();
+  if (st != SFB_OK) return st;
+  if (batch == 0) return SFB_OK;
+  return with_device_mesh(mesh, [&](const sfb::MeshDevice &m) {
+    sfb::MeshDynErrorArgs a{};
+    a.m = m; a.batch = batch; a.nx = nx; a.horizon = horizon; a.X = X; a.F = F; a.errs = errs;
+    const hipError_t e = sfb::mesh_dyn_error_launch(a, static_cast<hipStream_t>(stream));
+    return e != hipSuccess ? sfb::hip_fail(e, "mesh_dyn_error_kernel launch") : SFB_OK;
+  });
+}
+
+sfb_status sfb_mesh_raised_nodes(const sfb_mesh *mesh, double *tau)
+{
+  const sfb_status st = mesh_check(mesh, 0);
+  if (st != SFB_OK) return st;
+  if (!tau) return sfb::fail(SFB_ERR_INVALID_ARG, "NULL array");
+  for (int32_t s = 0; s < mesh->nivals; ++s) {
+    const std::vector<double> &x = L::detail::lgr_table(mesh->K[s] + 1).tau;  // K + 1 LGR points and +1
+    const double tau0 = mesh->tau0[s], al = ((s + 1 < mesh->nivals ? mesh->tau0[s + 1] : 1.0) - tau0) / 2;
+    for (const double v : x) *tau++ = tau0 + al * (v + 1);
+  }
+  return SFB_OK;
+}
+
+sfb_status sfb_mesh_resample_batch_host(const sfb_mesh *mesh, int64_t batch, int32_t dim, int extend, const double *vals, double *out)
+{
+  sfb_status st = resample_check(mesh, batch, dim, vals, out);
+  if (st != SFB_OK) return st;
+  st = sfb::require_device();
+  if (st != SFB_OK) return st;
+  if (batch == 0 || dim == 0) return SFB_OK;
+  const size_t B = (size_t)batch, D = (size_t)dim, N = (size_t)mesh_nodes(mesh), R = N + 2 * (size_t)mesh->nivals;
+  using S = sfb::Staging;
+  S s;
+  double *dv, *dout;
+  s.add(&dv, B * (N + (extend ? 1 : 0)) * D, S::In, vals); s.add(&dout, B * R * D, S::Out, out);
+  sfb::DeviceBlock blk;
+  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
+  hipError_t e = s.upload();
+  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_mesh_resample_batch_host upload");
+  st = sfb_mesh_resample_batch(mesh, batch, dim, extend, dv, dout, nullptr);
+  if (st != SFB_OK) return st;
+  if ((e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
+  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_mesh_resample_batch_host");
+  return SFB_OK;
+}
+
+sfb_status sfb_mesh_dyn_error_batch_host(const sfb_mesh *mesh, int64_t batch, int32_t nx, const double *horizon, const double *X, const double *F,
+                                         double *errs)
+{
+  sfb_status st = dyn_error_check(mesh, batch, nx, horizon, X, F, errs);
+  if (st != SFB_OK) return st;
+  st = sfb::require_device();
+  if (st != SFB_OK) return st;
+  if (batch == 0) return SFB_OK;
+  const size_t B = (size_t)batch, D = (size_t)nx, R = (size_t)mesh_nodes(mesh) + 2 * (size_t)mesh->nivals;
+  using S = sfb::Staging;
+  S s;
+  double *dh, *dX, *dF, *de;
+  s.add(&dh, B, S::In, horizon); s.add(&dX, B * R * D, S::In, X); s.add(&dF, B * R * D, S::In, F); s.add(&de, B * (size_t)mesh->nivals, S::Out, errs);
+  sfb::DeviceBlock blk;
+  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
+  hipError_t e = s.upload();
+  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_mesh_dyn_error_batch_host upload");
+  st = sfb_mesh_dyn_error_batch(mesh, batch, nx, dh, dX, dF, de, nullptr);
+  if (st != SFB_OK) return st;
+  if ((e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
+  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_mesh_dyn_error_batch_host");
+  return SFB_OK;
+}
+
+}  // extern "C"

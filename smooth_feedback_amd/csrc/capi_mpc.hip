@@ -579,4 +579,13 @@ sfb_status sfb_mpc_swarm_debug_buffers(sfb_mpc_swarm *S, const double **Ax, cons
   return SFB_OK;
 }
 
+sfb_status sfb_mpc_swarm_device_solution(sfb_mpc_swarm *S, const double **primal, const double **dual, const int32_t **code)
+{
+  if (!S) return sfb::fail(SFB_ERR_INVALID_ARG, "swarm is NULL");
+  if (primal) *primal = S->x;
+  if (dual) *dual = S->y;
+  if (code) *code = S->code;
+  return SFB_OK;
+}
+
 }  // extern "C"
