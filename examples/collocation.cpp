@@ -11,6 +11,7 @@
 
 #include <smooth/feedback/collocation/dyn_error.hpp>
 #include <smooth/feedback/collocation/mesh.hpp>
+#include <smooth/feedback/collocation/mesh_function.hpp>
 #include <smooth/feedback/mpc.hpp>
 
 #include "lie_eval.h"
@@ -57,6 +58,8 @@ int with_mesh(int kmin, int kmax, int n, int k, int nops, const int32_t * ops, c
     if (kmin == 3 && kmax == 6) return f(run_script<sf::Mesh<3, 6>>(n, k, nops, ops, opdata));
     if (kmin == 4 && kmax == 4) return f(run_script<sf::Mesh<4, 4>>(n, k, nops, ops, opdata));
     if (kmin == 13 && kmax == 13) return f(run_script<sf::Mesh<13, 13>>(n, k, nops, ops, opdata));  // the kernels' largest degree
+    if (kmin == 1 && kmax == 2) return f(run_script<sf::Mesh<1, 2>>(n, k, nops, ops, opdata));        // one point per interval
+    if (kmin == 4 && kmax == 6) return f(run_script<sf::Mesh<4, 6>>(n, k, nops, ops, opdata));
   } catch (const std::exception & e) {
     std::fprintf(stderr, "collocation harness: %s\n", e.what());
     return -2;
@@ -132,9 +135,298 @@ int with_mpc(int variant, int K, double tf, Fn && fn)
   return -1;
 }
 
+// ---- functions over a mesh (mesh_function.hpp) ----
+// what mesh_eval / mesh_integrate / mesh_dyn ask of a mesh, copied out of any Mesh<Kmin, Kmax>: one instantiation of the
+// functions per integrand instead of one per mesh type
+struct MeshCopy {
+  std::vector<double> nodes, weights;
+  std::vector<std::size_t> K;
+  std::vector<std::pair<double, sf::MeshMat>> D;
+  template<class M>
+  explicit MeshCopy(const M & m) : nodes(m.all_nodes()), weights(m.all_weights())
+  {
+    for (std::size_t s = 0; s < m.N_ivals(); ++s) K.push_back(m.N_colloc_ival(s)), D.push_back(m.interval_diffmat_unscaled(s));
+  }
+  std::size_t N_ivals() const { return K.size(); }
+  std::size_t N_colloc() const { return nodes.size() - 1; }
+  std::size_t N_colloc_ival(std::size_t s) const { return K[s]; }
+  const std::vector<double> & all_nodes() const { return nodes; }
+  const std::vector<double> & all_weights() const { return weights; }
+  const std::pair<double, sf::MeshMat> & interval_diffmat_unscaled(std::size_t s) const { return D[s]; }
+};
+
+// An integrand as data: output r is the sum of coef phi_ka(z_a) phi_kb(z_b) over its terms (rows r, a, ka, b, kb),
+// z = (t, x, u), phi_0 = 1, phi_1 = z, phi_2 = z^2, phi_3 = sin z, phi_4 = cos z; derivatives in closed form.
+struct Phi {
+  double v, d1, d2;
+  Phi(int k, double z)
+  {
+    switch (k) {
+    case 0: v = 1, d1 = 0, d2 = 0; break;
+    case 1: v = z, d1 = 1, d2 = 0; break;
+    case 2: v = z * z, d1 = 2 * z, d2 = 2; break;
+    case 3: v = std::sin(z), d1 = std::cos(z), d2 = -std::sin(z); break;
+    default: v = std::cos(z), d1 = -std::sin(z), d2 = -std::cos(z); break;
+    }
+  }
+};
+template<int NX, int NU, int NF>
+struct TermFn {
+  static constexpr int NV = 1 + NX + NU;
+  int nterms;
+  const int32_t * terms;
+  const double * coef;
+  static double coord(int a, double t, const sf::Rn<NX> & x, const sf::Rn<NU> & u) { return a == 0 ? t : a <= NX ? x.v[a - 1] : u.v[a - 1 - NX]; }
+  sf::Vec<NF> operator()(double t, const sf::Rn<NX> & x, const sf::Rn<NU> & u) const
+  {
+    sf::Vec<NF> f{};
+    for (int m = 0; m < nterms; ++m) {
+      const int32_t * q = terms + 5 * m;
+      f[q[0]] += coef[m] * Phi(q[2], coord(q[1], t, x, u)).v * Phi(q[4], coord(q[3], t, x, u)).v;
+    }
+    return f;
+  }
+  void jacobian(double t, const sf::Rn<NX> & x, const sf::Rn<NU> & u, sf::Mat<NF, NV> & J) const
+  {
+    J = sf::Mat<NF, NV>::Zero();
+    for (int m = 0; m < nterms; ++m) {
+      const int32_t * q = terms + 5 * m;
+      const Phi A(q[2], coord(q[1], t, x, u)), B(q[4], coord(q[3], t, x, u));
+      J(q[0], q[1]) += coef[m] * A.d1 * B.v;
+      J(q[0], q[3]) += coef[m] * A.v * B.d1;
+    }
+  }
+  void hessian(double t, const sf::Rn<NX> & x, const sf::Rn<NU> & u, sf::Mat<NV, NF * NV> & H) const
+  {
+    H = sf::Mat<NV, NF * NV>::Zero();
+    for (int m = 0; m < nterms; ++m) {
+      const int32_t * q = terms + 5 * m;
+      const int r = q[0], a = q[1], b = q[3];
+      const Phi A(q[2], coord(a, t, x, u)), B(q[4], coord(b, t, x, u));
+      H(a, r * NV + a) += coef[m] * A.d2 * B.v;
+      H(a, r * NV + b) += coef[m] * A.d1 * B.d1;
+      H(b, r * NV + a) += coef[m] * A.d1 * B.d1;
+      H(b, r * NV + b) += coef[m] * A.v * B.d2;
+    }
+  }
+};
+// the vehicle's dynamics on SE2 x R^3 as an integrand (t, x, u), with its Jacobian in the (t | x | u) form
+struct VehicleFn {
+  sfbx::VehicleDyn6 f;
+  sf::Vec<6> operator()(double, const sfbx::X6 & x, const sfbx::U2 & u) const { return f(x, u); }
+  void jacobian(double, const sfbx::X6 & x, const sfbx::U2 & u, sf::Mat<6, 9> & J) const
+  {
+    sf::Mat<6, 6> dx;
+    sf::Mat<6, 2> du;
+    f.jacobian(x, u, dx, du);
+    J = sf::Mat<6, 9>::Zero();
+    for (int r = 0; r < 6; ++r) {
+      for (int c = 0; c < 6; ++c) J(r, 1 + c) = dx(r, c);
+      for (int c = 0; c < 2; ++c) J(r, 7 + c) = du(r, c);
+    }
+  }
+};
+
+// an integrand given by its values at the nodes, for comparing the host front with the model-free kernels on the same
+// numbers: table [N][NF (2 + NX + NU)] holds node i's values, then its Jacobian row-major; the functions evaluate the
+// integrand once per node in node order, and jacobian() belongs to the node evaluated last
+template<int NX, int NU, int NF>
+struct TableFn {
+  static constexpr int NV = 1 + NX + NU;
+  const double * table;
+  mutable long node = -1;
+  sf::Vec<NF> operator()(double, const sf::Rn<NX> &, const sf::Rn<NU> &) const
+  {
+    ++node;
+    sf::Vec<NF> f{};
+    for (int r = 0; r < NF; ++r) f[r] = table[node * NF * (1 + NV) + r];
+    return f;
+  }
+  void jacobian(double, const sf::Rn<NX> &, const sf::Rn<NU> &, sf::Mat<NF, NV> & J) const
+  {
+    for (int r = 0; r < NF; ++r)
+      for (int c = 0; c < NV; ++c) J(r, c) = table[node * NF * (1 + NV) + NF + r * NV + c];
+  }
+};
+
+struct MeshFnOut {
+  int32_t * dims;  // rows, cols, nnz, d2 nnz, 1 when no output array moved between the calls
+  double * F;
+  int32_t *rowptr, *colind;
+  double * val;
+  int32_t *colptr2, *rowind2;
+  double * val2;
+};
+
+template<int FN, uint8_t Deriv, sf::diff::Type DT, class Fn, class X, class U>
+int meshfn_run(const MeshCopy & m, Fn & f, double t0, double tf, const std::vector<X> & xs, const std::vector<U> & us, bool scale,
+               const double * lambda, int calls, const MeshFnOut & o)
+{
+  sf::MeshValue<Deriv> out;
+  const void * where[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool stable = true;
+  for (int c = 0; c < calls; ++c) {
+    if constexpr (Deriv == 2) {
+      constexpr std::size_t nf = std::tuple_size_v<decltype(f(0.0, xs[0], us[0]))>;
+      if (c == 0) out.lambda.assign(lambda, lambda + (FN == 1 ? nf : nf * m.N_colloc()));
+    }
+    if constexpr (FN == 0) sf::mesh_eval<Deriv, DT>(out, m, f, t0, tf, xs, us, scale);
+    if constexpr (FN == 1) sf::mesh_integrate<Deriv, DT>(out, m, f, t0, tf, xs, us);
+    if constexpr (FN == 2) sf::mesh_dyn<Deriv, DT>(out, m, f, t0, tf, xs, us);
+    if (!out.allocated) return -7;
+    const void * now[4] = {out.F.data(), nullptr, nullptr, nullptr};
+    if constexpr (Deriv >= 1) now[1] = out.dF.val.data(), now[2] = out.dF.colind.data();
+    if constexpr (Deriv >= 2) now[3] = out.d2F.val.data();
+    for (int k = 0; k < 4; ++k) {
+      if (c > 0 && now[k] != where[k]) stable = false;
+      where[k] = now[k];
+    }
+  }
+  o.dims[0] = (int32_t)out.F.size();
+  o.dims[1] = o.dims[2] = o.dims[3] = 0;
+  o.dims[4] = stable ? 1 : 0;
+  std::copy(out.F.begin(), out.F.end(), o.F);
+  if constexpr (Deriv >= 1) {
+    if (out.dF.rows != (int32_t)out.F.size()) return -8;
+    o.dims[1] = out.dF.cols;
+    o.dims[2] = (int32_t)out.dF.val.size();
+    std::copy(out.dF.rowptr.begin(), out.dF.rowptr.end(), o.rowptr);
+    std::copy(out.dF.colind.begin(), out.dF.colind.end(), o.colind);
+    std::copy(out.dF.val.begin(), out.dF.val.end(), o.val);
+  }
+  if constexpr (Deriv >= 2) {
+    o.dims[3] = (int32_t)out.d2F.val.size();
+    std::copy(out.d2F.colptr.begin(), out.d2F.colptr.end(), o.colptr2);
+    std::copy(out.d2F.rowind.begin(), out.d2F.rowind.end(), o.rowind2);
+    std::copy(out.d2F.val.begin(), out.d2F.val.end(), o.val2);
+  }
+  return 0;
+}
+
+// (fn, deriv, numerical) at run time -> the instantiation; MaxDeriv and Dyn say what the state / input types allow
+template<int MaxDeriv, bool Dyn, class Fn, class X, class U>
+int meshfn_dispatch(int fn, int deriv, int numerical, const MeshCopy & m, Fn & f, double t0, double tf, const std::vector<X> & xs,
+                    const std::vector<U> & us, bool scale, const double * lambda, int calls, const MeshFnOut & o)
+{
+  using T = sf::diff::Type;
+#define SFBX_RUN(FN, D) \
+  if constexpr (D <= MaxDeriv && (FN < 2 || Dyn)) \
+    if (fn == FN && deriv == D) \
+      return numerical ? meshfn_run<FN, D, T::Numerical>(m, f, t0, tf, xs, us, scale, lambda, calls, o) \
+                       : meshfn_run<FN, D, T::Analytic>(m, f, t0, tf, xs, us, scale, lambda, calls, o);
+  SFBX_RUN(0, 0) SFBX_RUN(0, 1) SFBX_RUN(0, 2) SFBX_RUN(1, 0) SFBX_RUN(1, 1) SFBX_RUN(1, 2) SFBX_RUN(2, 0) SFBX_RUN(2, 1) SFBX_RUN(2, 2)
+#undef SFBX_RUN
+  return -6;  // no such (fn, deriv) for this shape
+}
+
+template<int NX, int NU, int NF>
+int meshfn_terms(int fn, int deriv, int numerical, const MeshCopy & m, int nterms, const int32_t * terms, const double * coef, double t0, double tf,
+                 const double * xs, const double * us, bool scale, const double * lambda, int calls, const MeshFnOut & o)
+{
+  for (int q = 0; q < nterms; ++q) {
+    const int32_t * t = terms + 5 * q;
+    if (t[0] < 0 || t[0] >= NF || t[1] < 0 || t[1] > NX + NU || t[3] < 0 || t[3] > NX + NU || t[2] < 0 || t[2] > 4 || t[4] < 0 || t[4] > 4) return -9;
+  }
+  const std::size_t N = m.N_colloc();
+  std::vector<sf::Rn<NX>> X(N + 1);
+  std::vector<sf::Rn<NU>> U(N);
+  for (std::size_t i = 0; i <= N; ++i)
+    for (int d = 0; d < NX; ++d) X[i].v[d] = xs[i * NX + d];
+  for (std::size_t i = 0; i < N; ++i)
+    for (int d = 0; d < NU; ++d) U[i].v[d] = us[i * NU + d];
+  TermFn<NX, NU, NF> f{nterms, terms, coef};
+  return meshfn_dispatch<2, NX == NF>(fn, deriv, numerical, m, f, t0, tf, X, U, scale, lambda, calls, o);
+}
+
 }  // namespace
 
 extern "C" {
+
+int sfbx_meshfn_host(int kmin, int kmax, int n, int k, int nops, const int32_t * ops, const double * opdata, int fn, int deriv, int numerical,
+                     int shape, int nterms, const int32_t * terms, const double * coef, double t0, double tf, const double * xs, const double * us,
+                     int scale, const double * lambda, int calls, int32_t * dims, double * F, int32_t * rowptr, int32_t * colind, double * val,
+                     int32_t * colptr2, int32_t * rowind2, double * val2)
+{
+  const MeshFnOut o{dims, F, rowptr, colind, val, colptr2, rowind2, val2};
+  return with_mesh(kmin, kmax, n, k, nops, ops, opdata, [&](const auto & mesh) {
+    const MeshCopy m(mesh);
+    switch (shape) {
+    case 0: return meshfn_terms<3, 2, 3>(fn, deriv, numerical, m, nterms, terms, coef, t0, tf, xs, us, scale != 0, lambda, calls, o);
+    case 1: return meshfn_terms<3, 2, 1>(fn, deriv, numerical, m, nterms, terms, coef, t0, tf, xs, us, scale != 0, lambda, calls, o);
+    case 2: return meshfn_terms<1, 0, 1>(fn, deriv, numerical, m, nterms, terms, coef, t0, tf, xs, us, scale != 0, lambda, calls, o);
+    case 3: return meshfn_terms<12, 2, 12>(fn, deriv, numerical, m, nterms, terms, coef, t0, tf, xs, us, scale != 0, lambda, calls, o);
+    case 4: {  // the vehicle on SE2 x R^3: states in the flat storage of lie_eval.h
+      const std::size_t N = m.N_colloc();
+      std::vector<sfbx::X6> X(N + 1);
+      std::vector<sfbx::U2> U(N);
+      for (std::size_t i = 0; i <= N; ++i) X[i] = sfbx::LieIO<sfbx::X6>::load(xs + 7 * i);
+      for (std::size_t i = 0; i < N; ++i) U[i] = sfbx::LieIO<sfbx::U2>::load(us + 2 * i);
+      VehicleFn f{};
+      return meshfn_dispatch<1, false>(fn, deriv, numerical, m, f, t0, tf, X, U, scale != 0, lambda, calls, o);
+    }
+    case 5: {  // (6, 2, 6) tabulated: coef is the table, orders 0 and 1, one call
+      if (deriv > 1 || numerical || calls != 1) return -6;
+      const std::size_t N = m.N_colloc();
+      std::vector<sf::Rn<6>> X(N + 1);
+      std::vector<sf::Rn<2>> U(N);
+      for (std::size_t i = 0; i <= N; ++i)
+        for (int d = 0; d < 6; ++d) X[i].v[d] = xs[i * 6 + d];
+      for (std::size_t i = 0; i < N; ++i)
+        for (int d = 0; d < 2; ++d) U[i].v[d] = us[i * 2 + d];
+      TableFn<6, 2, 6> f{coef};
+      return meshfn_dispatch<1, true>(fn, deriv, 0, m, f, t0, tf, X, U, scale != 0, lambda, calls, o);
+    }
+    default: return -5;
+    }
+  });
+}
+
+// the two trajectory scenarios of the reference's tests/test_collocation_mesh_function.cpp (:522-628) as caller code;
+// returns 0, or the number of the first expectation that fails
+int sfbx_test_mesh_function_api(void)
+{
+  namespace F = smooth::feedback;
+  const double t0 = 3, tf = 5;
+  F::Mesh<5, 5> m;
+  m.refine_ph(0, 40);
+  const std::size_t N = m.N_colloc();
+  const std::vector<F::Rn<0>> U(N);
+  const auto maxabs = [](const std::vector<double> & v) {
+    double r = 0;
+    for (const double e : v) r = std::max(r, std::fabs(e));
+    return r;
+  };
+  {  // x(t) = 0.1 t^2 - 0.4 t + 0.2
+    std::vector<F::Rn<1>> X(N + 1);
+    const auto nodes = m.all_nodes();
+    for (std::size_t i = 0; i <= N; ++i) {
+      const double s = t0 + (tf - t0) * nodes[i];
+      X[i].v[0]      = 0.1 * s * s - 0.4 * s + 0.2;
+    }
+    const auto df_dt = [](double t, const F::Rn<1> &, const F::Rn<0> &) { return F::Vec<1>{0.2 * t - 0.4}; };
+    const auto g     = [](double, const F::Rn<1> & x, const F::Rn<0> &) { return F::Vec<1>{0.1 + x.v[0] * x.v[0]}; };
+    F::MeshValue<0> out;
+    F::mesh_integrate(out, m, g, t0, tf, X, U);
+    if (!(std::fabs(out.F[0] - (0.217333 + 0.1 * (tf - t0))) <= 1e-4)) return 1;
+    F::MeshValue<1> dyn;
+    F::mesh_dyn<1>(dyn, m, df_dt, t0, tf, X, U);
+    if (dyn.F.size() != N || !(maxabs(dyn.F) <= 1e-8)) return 2;
+  }
+  {  // x(t) = 1.5 exp(-t)
+    std::vector<F::Rn<1>> X(N + 1);
+    const auto nodes = m.all_nodes();
+    for (std::size_t i = 0; i <= N; ++i) X[i].v[0] = 1.5 * std::exp(-(t0 + (tf - t0) * nodes[i]));
+    const auto df_dt = [](double, const F::Rn<1> & x, const F::Rn<0> &) { return F::Vec<1>{-x.v[0]}; };
+    const auto g     = [](double, const F::Rn<1> & x, const F::Rn<0> &) { return F::Vec<1>{x.v[0] * x.v[0]}; };
+    F::MeshValue<0> out;
+    F::mesh_integrate(out, m, g, t0, tf, X, U);
+    if (!(std::fabs(out.F[0] - 0.00273752) <= 1e-4)) return 3;
+    F::MeshValue<1> dyn;
+    F::mesh_dyn<1>(dyn, m, df_dt, t0, tf, X, U);
+    if (dyn.F.size() != N || !(maxabs(dyn.F) <= 1e-8)) return 4;
+  }
+  return 0;
+}
 
 int sfbx_mpc_dyn_error_host(int variant, int K, double tf, int64_t batch, const double * t, const double * primal, double * errs)
 {

@@ -171,7 +171,7 @@ int sfbx_pid_rollout_spline_host(int group, int64_t batch, double t0, double dt,
 /* mesh: nodes (N+1), weights (N+1), Dus ((K+1)*K col-major) for `n` intervals of K points */
 int sfbx_mesh(int n_ivals, int K, double *nodes, double *weights, double *Dus);
 
-/* ---- collocation layer (collocation.cpp): the ph mesh Mesh<kmin, kmax> for <5,10>, <5,5>, <8,8>, <3,6>, <4,4>, <13,13> (-1: no such
+/* ---- collocation layer (collocation.cpp): the ph mesh Mesh<kmin, kmax> for <5,10>, <5,5>, <8,8>, <3,6>, <4,4>, <13,13>, <1,2>, <4,6> (-1: no such
  * instantiation) built as Mesh(n, k) and driven by an op script: ops [nops][3] rows (code, a, b) with 0 refine_ph(a, b),
  * 1 increase_degrees, 2 decrease_degrees, 3 set_N_colloc_ival(a, b), 4 refine_errors taking (target, errs[N_ivals]) from
  * opdata.  Out: nivals (-3 when above cap_ivals), K, tau0 [nivals], all nodes / weights [N + 1], the interval
@@ -200,6 +200,23 @@ int sfbx_mpc_tick_dyn_error_host(int variant, int K, double tf, double t, const 
 /* the reference's mesh and dyn-error tests as caller code against <smooth/feedback/collocation/{mesh,dyn_error}.hpp>: 0, or the number of
  * the first expectation that fails */
 int sfbx_test_collocation_api(void);
+/* mesh_eval (fn 0) / mesh_integrate (1) / mesh_dyn (2) of mesh_function.hpp at order deriv, differentiating the integrand by its
+ * members (numerical 0) or by differences (1), on the script's mesh (also <1,2> and <4,6>).  Shapes 0 .. 3: an integrand given
+ * as a term table on Rn state and input with (nx, nu, nf) = (3,2,3), (3,2,1), (1,0,1), (12,2,12): terms [nterms][5] rows
+ * (r, a, ka, b, kb), output r += coef phi_ka(z_a) phi_kb(z_b), z = (t, x, u), phi = 1, z, z^2, sin z, cos z (-9: a row out of
+ * range); shape 4: the vehicle's dynamics on SE2 x R^3 (xs in the flat storage of lie_eval.h; deriv <= 1, fn <= 1); shape 5:
+ * (6, 2, 6) with the integrand tabulated, coef = [N][6 (1 + 9)] node by node the values, then the Jacobian row-major
+ * (deriv <= 1, analytic, calls == 1).  -5 / -6:
+ * no such shape / (fn, deriv) for it.  xs [N + 1][..], us [N][nu], lambda one per row of F (deriv 2).  The function is called
+ * `calls` times on one MeshValue.  Out: dims = rows, cols, nnz of dF, nnz of d2F, 1 when no output array moved between the
+ * calls; F; dF as CSR; d2F (upper triangle) as CSC. */
+int sfbx_meshfn_host(int kmin, int kmax, int n, int k, int nops, const int32_t *ops, const double *opdata, int fn, int deriv,
+                     int numerical, int shape, int nterms, const int32_t *terms, const double *coef, double t0, double tf,
+                     const double *xs, const double *us, int scale, const double *lambda, int calls, int32_t *dims, double *F,
+                     int32_t *rowptr, int32_t *colind, double *val, int32_t *colptr2, int32_t *rowind2, double *val2);
+/* the reference's two trajectory scenarios of mesh_function (tests/test_collocation_mesh_function.cpp:522-628) as caller code
+ * against <smooth/feedback/collocation/mesh_function.hpp>: 0, or the number of the first expectation that fails */
+int sfbx_test_mesh_function_api(void);
 
 #ifdef __cplusplus
 }

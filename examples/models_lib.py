@@ -595,3 +595,47 @@ def mpc_swarm_devlin_audit(variant, K, tf, t, dx0, audit=True, target=1e-3):
 
 def test_collocation_api():
     return lib().sfbx_test_collocation_api()
+
+
+MESHFN = {"eval": 0, "integrate": 1, "dyn": 2}
+MESHFN_SHAPES = {(3, 2, 3): 0, (3, 2, 1): 1, (1, 0, 1): 2, (12, 2, 12): 3, "vehicle": 4, "table": 5}
+
+
+def meshfn_host(spec, ops, opdata, fn, deriv, shape, terms, coef, t0, tf, xs, us, scale=False, lam=None, numerical=False, calls=1):
+    """mesh_eval / mesh_integrate / mesh_dyn (fn: a key of MESHFN) of the host front at order deriv on the script's mesh
+    (sfbx_meshfn_host); shape: a key of MESHFN_SHAPES, (nx, nu, nf) of an integrand given as a term table (terms (nterms, 5),
+    coef (nterms,)) or "vehicle".  xs (N + 1, ..), us (N, nu).  Returns dict F, stable, and with deriv >= 1 rowptr, colind, val,
+    cols (dF as CSR), with deriv 2 colptr2, rowind2, val2 (d2F, upper triangle, CSC).  LookupError for a shape or
+    (fn, deriv) the harness does not carry."""
+    args, keep = _script_args(spec, ops, opdata)
+    xs = np.ascontiguousarray(xs, dtype=np.float64); us = np.ascontiguousarray(us, dtype=np.float64)
+    terms = np.ascontiguousarray(terms, dtype=np.int32).reshape(-1, 5); coef = np.ascontiguousarray(coef, dtype=np.float64)
+    N = len(xs) - 1
+    if shape in ("vehicle", "table"):    # "table": coef (N, 6 * 10), node by node the values and the Jacobian row-major
+        nx, nu, nf = 6, 2, 6
+    else:
+        nx, nu, nf = shape
+    nv = 2 + nx * (N + 1) + nu * N
+    rows_cap = N * nf
+    nnz_cap = max(rows_cap * (2 + 17 + nx + nu), nf * nv)
+    lam = np.ascontiguousarray(lam if lam is not None else np.zeros(rows_cap), dtype=np.float64)
+    dims = np.zeros(5, np.int32)
+    F = np.zeros(rows_cap); rowptr = np.zeros(rows_cap + 1, np.int32); colind = np.zeros(nnz_cap, np.int32); val = np.zeros(nnz_cap)
+    colptr2 = np.zeros(nv + 1, np.int32); rowind2 = np.zeros(nv * (3 + nx + nu), np.int32); val2 = np.zeros(nv * (3 + nx + nu))
+    rc = lib().sfbx_meshfn_host(*args, MESHFN[fn], int(deriv), 1 if numerical else 0, MESHFN_SHAPES[shape], len(terms), _p(terms), _p(coef),
+                                C.c_double(t0), C.c_double(tf), _p(xs), _p(us), 1 if scale else 0, _p(lam), int(calls), _p(dims), _p(F),
+                                _p(rowptr), _p(colind), _p(val), _p(colptr2), _p(rowind2), _p(val2))
+    if rc in (-1, -5, -6):
+        raise LookupError("sfbx_meshfn_host: %d" % rc)
+    assert rc == 0, rc
+    rows, cols, nnz, nnz2, stable = [int(v) for v in dims]
+    out = {"F": F[:rows].copy(), "stable": bool(stable)}
+    if deriv >= 1:
+        out.update(rowptr=rowptr[:rows + 1].copy(), colind=colind[:nnz].copy(), val=val[:nnz].copy(), cols=cols)
+    if deriv >= 2:
+        out.update(colptr2=colptr2[:cols + 1].copy(), rowind2=rowind2[:nnz2].copy(), val2=val2[:nnz2].copy())
+    return out
+
+
+def test_mesh_function_api():
+    return lib().sfbx_test_mesh_function_api()

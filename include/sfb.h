@@ -731,6 +731,55 @@ sfb_status sfb_mesh_resample_batch_host(const sfb_mesh *mesh, int64_t batch, int
 sfb_status sfb_mesh_dyn_error_batch_host(const sfb_mesh *mesh, int64_t batch, int32_t nx, const double *horizon,
                                          const double *X, const double *F, double *errs);
 
+/* ------------------------------------------------------------------------------------------
+ * Functions over a mesh with first derivatives (include/smooth_feedback_amd/mesh_function.hpp: mesh_eval,
+ * mesh_integrate, mesh_dyn; reference collocation/mesh_function.hpp:114-665).  Model-free: the caller evaluates its
+ * model at the N collocation nodes (times t0 + (tf - t0) tau_i) and hands in
+ *   F  [batch][N][nf]                  the values, and
+ *   dF [batch][N][nf][1 + nx + nu]     the Jacobians, columns (t | x | u), right-Jacobians on a group;
+ * the library does everything that depends on the mesh, with the arithmetic of the host front (one source).  Variables
+ * are ordered [t0 | tf | x_0 .. x_N | u_0 .. u_{N-1}], numVars = 2 + nx (N + 1) + nu N.  The derivative of the two CSR
+ * outputs comes as values out_dF_val [batch][nnz] in the order of one pattern per mesh, shared by every agent -- the
+ * form (A pattern once, A values [agents][nnz]) a sparse QP plan consumes:
+ *   eval: row (node i, output r) holds t0, tf, the nx columns of x_i, the nu columns of u_i;
+ *   dyn:  row (node i = M_s + j of interval s, component d) holds t0, tf, for k = 0 .. K_s one entry (component d of
+ *         x_{M_s + k}; for k == j the whole nx-wide block), then the nu columns of u_i: 2 + K_s + nx + nu entries,
+ *         columns ascending -- the dyn row of sfb_mpc_layout with the two time columns in front.
+ * dF == NULL together with a NULL derivative output: values only.  nu == 0 is legal.  One GPU lane per output double.
+ * Errors as above (the mesh, then batch < 0), then nx < 0, nu < 0, nf < 0, sizes beyond 32-bit indices, dF without its
+ * output or the reverse, a NULL array with work to do; then SFB_ERR_NO_DEVICE for the compute entries.  batch == 0
+ * writes nothing.
+ * ---------------------------------------------------------------------------------------- */
+/* Patterns: rowptr [rows + 1], colind [nnz], rows = N nf (eval) or N nx (dyn).  Both arrays NULL: only *nnz is set.
+ * Host arrays, CPU only: needs no device. */
+sfb_status sfb_mesh_eval_pattern(const sfb_mesh *mesh, int32_t nx, int32_t nu, int32_t nf, int32_t *rowptr,
+                                 int32_t *colind, int64_t *nnz);
+sfb_status sfb_mesh_dyn_pattern(const sfb_mesh *mesh, int32_t nx, int32_t nu, int32_t *rowptr, int32_t *colind,
+                                int64_t *nnz);
+/* out_F [batch][N][nf] = w_i f_i (w_i: the quadrature weight when scale != 0, else 1) */
+sfb_status sfb_mesh_eval_batch(const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, int32_t nf, int scale,
+                               const double *t0, const double *tf, const double *F, const double *dF, double *out_F,
+                               double *out_dF_val, void *stream);
+/* out_F [batch][nf] = (tf - t0) sum_i w_i f_i, the nodes added in order; out_dF [batch][nf][numVars] dense, the
+ * columns of x_N zero */
+sfb_status sfb_mesh_integrate_batch(const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, int32_t nf,
+                                    const double *t0, const double *tf, const double *F, const double *dF,
+                                    double *out_F, double *out_dF, void *stream);
+/* X [batch][N + 1][nx]; F is [batch][N][nx].  out_F [batch][N][nx] = w_i ((tf - t0) f_i - alpha_s sum_k D(k, j) x_{M_s + k}) */
+sfb_status sfb_mesh_dyn_batch(const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, const double *t0,
+                              const double *tf, const double *X, const double *F, const double *dF, double *out_F,
+                              double *out_dF_val, void *stream);
+/* Host-pointer variants (stage through device memory, synchronous). */
+sfb_status sfb_mesh_eval_batch_host(const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, int32_t nf, int scale,
+                                    const double *t0, const double *tf, const double *F, const double *dF,
+                                    double *out_F, double *out_dF_val);
+sfb_status sfb_mesh_integrate_batch_host(const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, int32_t nf,
+                                         const double *t0, const double *tf, const double *F, const double *dF,
+                                         double *out_F, double *out_dF);
+sfb_status sfb_mesh_dyn_batch_host(const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, const double *t0,
+                                   const double *tf, const double *X, const double *F, const double *dF, double *out_F,
+                                   double *out_dF_val);
+
 /*
  * Synthetic workload of the reference benchmark: random_qp(m, n, density, rng)
  * (benchmarks/bench_types.hpp:19-41) drawn `batch` times from ONE std::default_random_engine

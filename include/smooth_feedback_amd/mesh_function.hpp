@@ -1,0 +1,488 @@
+// Functions over a collocation mesh with first and multiplier-weighted second derivatives (reference
+// collocation/mesh_function.hpp): MeshValue<Deriv>, mesh_eval (:114-246), mesh_integrate (:273-419), mesh_dyn (:450-665),
+// on plain arrays.  Variables [t0 | tf | x_0 .. x_N | u_0 .. u_{N-1}], numVars = 2 + nx (N + 1) + nu N.
+//
+// One law: the arithmetic of every output entry of orders 0 and 1 is written once below (namespace meshfn, SFB_LIE_HD);
+// the host loops of this header and the batched kernels of smooth_feedback_amd/csrc/mesh.hip both call it, and both add
+// sums over nodes in node order.  The sparsity patterns are built once as well (meshfn::*_pattern: the host front, and
+// sfb_mesh_eval_pattern / sfb_mesh_dyn_pattern of the C-ABI).
+//
+// dF is CSR in the form QuadraticProgramSparse::A_* has, d2F the upper triangle in CSC as P_*.  Derivatives with respect
+// to x and u are right-Jacobians.  mesh_eval and mesh_integrate take any state / input type of the Lie layer for
+// Deriv <= 1; mesh_dyn's defect subtracts sum_k D(k, j) x_k and therefore needs a vector state (Rn), as the reference's
+// `coef * x` does.  Deriv == 2 needs Rn state and input.
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <iterator>
+#include <limits>
+#include <tuple>
+#include <type_traits>
+#include <vector>
+
+#include "lie.hpp"
+#include "mesh.hpp"
+
+namespace smooth_feedback_amd {
+
+namespace diff {
+/// how the integrand is differentiated: by its jacobian / hessian members, by differences, or members where they exist
+enum class Type { Numerical, Analytic, Default };
+}  // namespace diff
+
+/// rows x cols CSR (QuadraticProgramSparse::A_*)
+struct MeshCsr {
+  int32_t rows = 0, cols = 0;
+  std::vector<int32_t> rowptr, colind;
+  std::vector<double> val;
+};
+/// upper triangle of a symmetric rows x cols matrix in CSC (QuadraticProgramSparse::P_*)
+struct MeshCsc {
+  int32_t rows = 0, cols = 0;
+  std::vector<int32_t> colptr, rowind;
+  std::vector<double> val;
+};
+
+template<uint8_t Deriv>
+struct MeshValue;
+template<>
+struct MeshValue<0> {
+  std::vector<double> F;  ///< function value
+  bool allocated{false};  ///< true: sizes and patterns are taken as correct and no output array is (re)allocated
+};
+template<>
+struct MeshValue<1> : public MeshValue<0> {
+  MeshCsr dF;  ///< size(F) x numVars
+};
+template<>
+struct MeshValue<2> : public MeshValue<1> {
+  std::vector<double> lambda;  ///< multipliers, one per row of F (set by the caller)
+  MeshCsc d2F;                 ///< numVars x numVars, upper triangle
+};
+
+/// zero the values, keep the patterns (lambda is the caller's)
+template<uint8_t Deriv>
+void set_zero(MeshValue<Deriv> & mv)
+{
+  for (double & v : mv.F) v = 0.0;
+  if constexpr (Deriv >= 1)
+    for (double & v : mv.dF.val) v = 0.0;
+  if constexpr (Deriv >= 2)
+    for (double & v : mv.d2F.val) v = 0.0;
+}
+
+// ---- the law: one function per kind of output entry (f: a model value, df*: an entry of its Jacobian (t | x | u)) ----
+namespace meshfn {
+
+// mesh_eval (:192-201); w is the quadrature weight when scaling, else 1
+SFB_LIE_HD inline double eval_F(double w, double f) { return w * f; }
+SFB_LIE_HD inline double eval_dt0(double w, double tau, double dft) { return (w * (1. - tau)) * dft; }
+SFB_LIE_HD inline double eval_dtf(double w, double tau, double dft) { return (w * tau) * dft; }
+SFB_LIE_HD inline double eval_dz(double w, double dfz) { return w * dfz; }
+
+// mesh_integrate (:348-361): what node i adds to the running sums (callers add in node order); h = tf - t0
+SFB_LIE_HD inline void integrate_F_add(double & acc, double w, double h, double f) { acc += w * h * f; }
+SFB_LIE_HD inline void integrate_dt0_add(double & acc, double w, double h, double tau, double f, double dft)
+{
+  acc += (w * h * (1. - tau)) * dft;
+  acc += (-w) * f;
+}
+SFB_LIE_HD inline void integrate_dtf_add(double & acc, double w, double h, double tau, double f, double dft)
+{
+  acc += (w * h * tau) * dft;
+  acc += w * f;
+}
+SFB_LIE_HD inline double integrate_dz(double w, double h, double dfz) { return (w * h) * dfz; }
+
+// mesh_dyn (:545-560, :626-664): row (node M + j of an interval of K points, component d); D(k, j) = Dcol[k], k = 0 .. K
+SFB_LIE_HD inline double dyn_coef(double w, double alpha, double Dkj) { return -w * alpha * Dkj; }
+/// F = w h f_d - w alpha sum_k D(k, j) x_{M + k, d}: the f term first, then k ascending; x: component d of x_M, rows ldx apart
+SFB_LIE_HD inline double dyn_F(int K, double w, double h, double alpha, const double * Dcol, double f, const double * x, int64_t ldx)
+{
+  double acc = w * h * f;
+  for (int k = 0; k <= K; ++k) acc += dyn_coef(w, alpha, Dcol[k]) * x[k * ldx];
+  return acc;
+}
+SFB_LIE_HD inline double dyn_dt0(double w, double h, double tau, double f, double dft)
+{
+  double acc = (-w) * f;
+  acc += (w * h * (1. - tau)) * dft;
+  return acc;
+}
+SFB_LIE_HD inline double dyn_dtf(double w, double h, double tau, double f, double dft)
+{
+  double acc = w * f;
+  acc += (w * h * tau) * dft;
+  return acc;
+}
+/// entry (d, c) of the row's own nx-wide block; Djj = D(j, j)
+SFB_LIE_HD inline double dyn_own(double w, double h, double alpha, double Djj, double dfx, bool diagonal)
+{
+  double acc = (w * h) * dfx;
+  if (diagonal) acc += dyn_coef(w, alpha, Djj);
+  return acc;
+}
+SFB_LIE_HD inline double dyn_du(double w, double h, double dfu) { return (w * h) * dfu; }
+
+/// What position p of a mesh_dyn row (node j of an interval of K points) holds: kind 0 t0, 1 tf, 2 another node k's
+/// single entry (idx = k), 3 the own block (idx = c), 4 u (idx = c).  2 + K + nx + nu positions, columns ascending.
+SFB_LIE_HD inline void dyn_decode(int p, int j, int K, int nx, int & kind, int & idx)
+{
+  if (p < 2) { kind = p; idx = 0; return; }
+  const int q = p - 2;
+  if (q < j) { kind = 2; idx = q; }
+  else if (q < j + nx) { kind = 3; idx = q - j; }
+  else if (q < nx + K) { kind = 2; idx = q - nx + 1; }
+  else { kind = 4; idx = q - nx - K; }
+}
+
+// ---- patterns (host).  rowptr [rows + 1], colind [nnz]; NULL arrays: only the count is returned ----
+inline int64_t eval_pattern(int64_t N, int nx, int nu, int nf, int32_t * rowptr, int32_t * colind)
+{
+  const int64_t per = 2 + nx + nu, rows = N * nf;
+  if (rowptr && colind) {
+    for (int64_t r = 0; r <= rows; ++r) rowptr[r] = (int32_t)(r * per);
+    for (int64_t r = 0; r < rows; ++r) {
+      const int64_t i = r / nf;
+      int32_t * c     = colind + r * per;
+      *c++ = 0; *c++ = 1;
+      for (int k = 0; k < nx; ++k) *c++ = (int32_t)(2 + i * nx + k);
+      for (int k = 0; k < nu; ++k) *c++ = (int32_t)(2 + (N + 1) * nx + i * nu + k);
+    }
+  }
+  return rows * per;
+}
+inline int64_t dyn_pattern(int nivals, const int32_t * K, int nx, int nu, int32_t * rowptr, int32_t * colind)
+{
+  int64_t N = 0, nnz = 0;
+  for (int s = 0; s < nivals; ++s) N += K[s], nnz += (int64_t)K[s] * nx * (2 + K[s] + nx + nu);
+  if (rowptr && colind) {
+    int64_t M = 0, e = 0, row = 0;
+    for (int s = 0; s < nivals; ++s) {
+      for (int j = 0; j < K[s]; ++j)
+        for (int d = 0; d < nx; ++d) {
+          rowptr[row++] = (int32_t)e;
+          for (int p = 0; p < 2 + K[s] + nx + nu; ++p) {
+            int kind, idx;
+            dyn_decode(p, j, K[s], nx, kind, idx);
+            colind[e++] = (int32_t)(kind < 2 ? kind : kind == 2 ? 2 + (M + idx) * nx + d : kind == 3 ? 2 + (M + j) * nx + idx : 2 + (N + 1) * nx + (M + j) * nu + idx);
+          }
+        }
+      M += K[s];
+    }
+    rowptr[row] = (int32_t)e;
+  }
+  return nnz;
+}
+/// the upper triangle shared by the three functions' d2F (:159-175): column t0 {t0}, tf {t0, tf}, component j of x_i
+/// {t0, tf, x_i0 .. x_ij}, component j of u_i {t0, tf, x_i, u_i0 .. u_ij}; the columns of x_N are empty
+inline void d2_pattern(int64_t N, int nx, int nu, MeshCsc & H)
+{
+  const int64_t nv = 2 + nx * (N + 1) + nu * N;
+  H.rows = H.cols = (int32_t)nv;
+  H.colptr.assign((size_t)nv + 1, 0);
+  H.rowind.clear();
+  for (int64_t c = 0; c < nv; ++c) {
+    if (c < 2) {
+      for (int64_t r = 0; r <= c; ++r) H.rowind.push_back((int32_t)r);
+    } else if (c < 2 + nx * N) {
+      const int64_t i = (c - 2) / nx, j = (c - 2) % nx;
+      H.rowind.push_back(0); H.rowind.push_back(1);
+      for (int64_t r = 0; r <= j; ++r) H.rowind.push_back((int32_t)(2 + i * nx + r));
+    } else if (c >= 2 + nx * (N + 1)) {
+      const int64_t i = (c - 2 - nx * (N + 1)) / nu, j = (c - 2 - nx * (N + 1)) % nu;
+      H.rowind.push_back(0); H.rowind.push_back(1);
+      for (int64_t r = 0; r < nx; ++r) H.rowind.push_back((int32_t)(2 + i * nx + r));
+      for (int64_t r = 0; r <= j; ++r) H.rowind.push_back((int32_t)(2 + nx * (N + 1) + i * nu + r));
+    }
+    H.colptr[(size_t)c + 1] = (int32_t)H.rowind.size();
+  }
+  H.val.assign(H.rowind.size(), 0.0);
+}
+
+}  // namespace meshfn
+
+namespace detail {
+
+inline double meshfn_fd_step() { return std::sqrt(std::numeric_limits<double>::epsilon()); }
+
+/// The integrand's value, Jacobian J (nf x (1 + nx + nu), columns t | x | u) and Hessians H ((1 + nx + nu) x nf (1 + nx + nu),
+/// side by side) at one node.  Analytic: f.jacobian(t, x, u, J), f.hessian(t, x, u, H).  Numerical: forward differences
+/// with step sqrt(eps) on the group (x (+) h e_c); second derivatives by differences of differences at step eps^(1/4).
+template<uint8_t Deriv, diff::Type DT, class Fn, class X, class U>
+struct MeshModelEval {
+  static constexpr int nx = X::Dof, nu = U::Dof, nv = 1 + nx + nu;
+  using R                 = std::decay_t<std::invoke_result_t<Fn &, double, const X &, const U &>>;
+  static constexpr int nf = (int)std::tuple_size_v<R>;
+  using JMat              = Mat<nf, nv>;
+  using HMat              = Mat<nv, nf * nv>;
+  static constexpr bool has_jacobian = requires(Fn & f, const X & x, const U & u, JMat & J) { f.jacobian(0.0, x, u, J); };
+  static constexpr bool has_hessian  = requires(Fn & f, const X & x, const U & u, HMat & H) { f.hessian(0.0, x, u, H); };
+  static_assert(DT != diff::Type::Analytic || Deriv < 1 || has_jacobian, "diff::Type::Analytic: the integrand needs jacobian(t, x, u, J)");
+  static_assert(DT != diff::Type::Analytic || Deriv < 2 || has_hessian, "diff::Type::Analytic: the integrand needs hessian(t, x, u, H)");
+
+  R f{};
+  std::conditional_t<(Deriv >= 1), JMat, char> J{};
+  std::conditional_t<(Deriv >= 2), HMat, char> H{};
+
+  static R shifted(Fn & fn, double t, const X & x, const U & u, int a, double da, int b, double db)
+  {
+    typename X::Tangent ex{};
+    typename U::Tangent eu{};
+    const auto bump = [&](int z, double d) {
+      if (z == 0) t += d;
+      else if (z <= nx) ex[z - 1] += d;
+      else eu[z - 1 - nx] += d;
+    };
+    bump(a, da);
+    if (b >= 0) bump(b, db);
+    return fn(t, rplus(x, ex), rplus(u, eu));
+  }
+
+  void operator()(Fn & fn, double t, const X & x, const U & u)
+  {
+    f = fn(t, x, u);
+    if constexpr (Deriv >= 1) {
+      if constexpr (DT != diff::Type::Numerical && has_jacobian) {
+        fn.jacobian(t, x, u, J);
+      } else {
+        const double h = meshfn_fd_step();
+        for (int a = 0; a < nv; ++a) {
+          const R fa = shifted(fn, t, x, u, a, h, -1, 0.0);
+          for (int r = 0; r < nf; ++r) J(r, a) = (fa[r] - f[r]) / h;
+        }
+      }
+    }
+    if constexpr (Deriv >= 2) {
+      if constexpr (DT != diff::Type::Numerical && has_hessian) {
+        fn.hessian(t, x, u, H);
+      } else {
+        const double h = std::sqrt(meshfn_fd_step());
+        for (int a = 0; a < nv; ++a)
+          for (int b = a; b < nv; ++b) {
+            const R pp = shifted(fn, t, x, u, a, h, b, h), pm = shifted(fn, t, x, u, a, h, b, -h);
+            const R mp = shifted(fn, t, x, u, a, -h, b, h), mm = shifted(fn, t, x, u, a, -h, b, -h);
+            for (int r = 0; r < nf; ++r) H(a, r * nv + b) = H(b, r * nv + a) = ((pp[r] - pm[r]) - (mp[r] - mm[r])) / (4 * h * h);
+          }
+      }
+    }
+  }
+};
+
+/// what node i adds to d2F (eval :208-242 with timescaled = false; integrate :368-415 and dyn :568-615 with true)
+template<int nx, int nu, int nf>
+void meshfn_d2_node(MeshCsc & H2, std::size_t N, std::size_t i, const double * lam, double w, double h, double tau, bool timescaled,
+                    const Mat<nf, 1 + nx + nu> & J, const Mat<1 + nx + nu, nf *(1 + nx + nu)> & H)
+{
+  constexpr int nv  = 1 + nx + nu;
+  const double mtau = 1. - tau;
+  const int x_d = (int)(2 + i * nx), u_d = (int)(2 + (N + 1) * nx + i * nu), u_base = (int)(2 + (N + 1) * nx);
+  const auto add = [&](int r, int c, double v) {
+    const int pos = r < 2 ? r : r < u_base ? 2 + (r - x_d) : 2 + nx + (r - u_d);
+    H2.val[(std::size_t)H2.colptr[c] + pos] += v;
+  };
+  for (int j = 0; j < nf; ++j) {
+    const double wl = w * lam[j], s = timescaled ? wl * h : wl;
+    const auto h2   = [&](int a, int b) { return H(a, j * nv + b); };
+    add(0, 0, (s * mtau * mtau) * h2(0, 0));
+    if (timescaled) add(0, 0, (-wl * 2 * mtau) * J(j, 0));
+    add(0, 1, (s * mtau * tau) * h2(0, 0));
+    if (timescaled) add(0, 1, (wl * (1. - 2 * tau)) * J(j, 0));
+    add(1, 1, (s * tau * tau) * h2(0, 0));
+    if (timescaled) add(1, 1, (wl * 2 * tau) * J(j, 0));
+    for (int c = 0; c < nx + nu; ++c) {
+      const int col = c < nx ? x_d + c : u_d + (c - nx);
+      add(0, col, (s * mtau) * h2(0, 1 + c));
+      if (timescaled) add(0, col, (-wl) * J(j, 1 + c));
+      add(1, col, (s * tau) * h2(0, 1 + c));
+      if (timescaled) add(1, col, wl * J(j, 1 + c));
+    }
+    for (int c = 0; c < nx; ++c)
+      for (int r = 0; r <= c; ++r) add(x_d + r, x_d + c, s * h2(1 + r, 1 + c));
+    for (int c = 0; c < nu; ++c) {
+      for (int r = 0; r < nx; ++r) add(x_d + r, u_d + c, s * h2(1 + r, 1 + nx + c));
+      for (int r = 0; r <= c; ++r) add(u_d + r, u_d + c, s * h2(1 + nx + r, 1 + nx + c));
+    }
+  }
+}
+
+template<class XS>
+using meshfn_value_t = std::decay_t<decltype(*std::begin(std::declval<XS &>()))>;
+
+template<class T>
+struct is_rn : std::false_type {};
+template<int N>
+struct is_rn<Rn<N>> : std::true_type {};
+
+}  // namespace detail
+
+/// [f(t_i, x_i, u_i)]_i over the N collocation nodes, t_i = t0 + (tf - t0) tau_i, each scaled by its quadrature weight
+/// when `scale` (:114-246).  Row (node i, output r) of dF holds t0, tf, the nx columns of x_i and the nu columns of u_i.
+template<uint8_t Deriv, diff::Type DT = diff::Type::Default, class M, class Fn, class XS, class US>
+  requires(Deriv <= 2)
+void mesh_eval(MeshValue<Deriv> & out, const M & m, Fn & f, const double t0, const double tf, XS && xs, US && us, bool scale = false)
+{
+  using X = detail::meshfn_value_t<XS>;
+  using U = detail::meshfn_value_t<US>;
+  using E = detail::MeshModelEval<Deriv, DT, Fn, X, U>;
+  constexpr int nx = E::nx, nu = E::nu, nf = E::nf;
+  static_assert(Deriv < 2 || (detail::is_rn<X>::value && detail::is_rn<U>::value), "Deriv == 2 needs Rn state and input");
+  const std::size_t N = m.N_colloc();
+  if (!out.allocated) {
+    out.F.assign(N * nf, 0.0);
+    if constexpr (Deriv >= 1) {
+      out.dF.rows = (int32_t)(N * nf);
+      out.dF.cols = (int32_t)(2 + nx * (N + 1) + nu * N);
+      const int64_t nnz = meshfn::eval_pattern((int64_t)N, nx, nu, nf, nullptr, nullptr);
+      out.dF.rowptr.assign(N * nf + 1, 0);
+      out.dF.colind.assign((std::size_t)nnz, 0);
+      out.dF.val.assign((std::size_t)nnz, 0.0);
+      meshfn::eval_pattern((int64_t)N, nx, nu, nf, out.dF.rowptr.data(), out.dF.colind.data());
+    }
+    if constexpr (Deriv >= 2) meshfn::d2_pattern((int64_t)N, nx, nu, out.d2F);
+    out.allocated = true;
+  }
+  set_zero(out);
+  const std::vector<double> taus = m.all_nodes(), wts = m.all_weights();
+  auto xit = std::begin(xs);
+  auto uit = std::begin(us);
+  E ev;
+  for (std::size_t i = 0; i < N; ++i, ++xit, ++uit) {
+    const double tau = taus[i], w = scale ? wts[i] : 1.;
+    ev(f, t0 + (tf - t0) * tau, *xit, *uit);
+    for (int r = 0; r < nf; ++r) out.F[i * nf + r] = meshfn::eval_F(w, ev.f[r]);
+    if constexpr (Deriv >= 1) {
+      for (int r = 0; r < nf; ++r) {
+        double * v = out.dF.val.data() + out.dF.rowptr[i * nf + r];
+        v[0]       = meshfn::eval_dt0(w, tau, ev.J(r, 0));
+        v[1]       = meshfn::eval_dtf(w, tau, ev.J(r, 0));
+        for (int c = 0; c < nx + nu; ++c) v[2 + c] = meshfn::eval_dz(w, ev.J(r, 1 + c));
+      }
+    }
+    if constexpr (Deriv >= 2) detail::meshfn_d2_node<nx, nu, nf>(out.d2F, N, i, out.lambda.data() + i * nf, w, 1.0, tau, false, ev.J, ev.H);
+  }
+}
+
+/// (tf - t0) sum_i w_i f(t_i, x_i, u_i) (:273-419).  dF is a dense nf x numVars row block; its last-state columns are zero.
+template<uint8_t Deriv, diff::Type DT = diff::Type::Default, class M, class Fn, class XS, class US>
+  requires(Deriv <= 2)
+void mesh_integrate(MeshValue<Deriv> & out, const M & m, Fn & f, const double t0, const double tf, XS && xs, US && us)
+{
+  using X = detail::meshfn_value_t<XS>;
+  using U = detail::meshfn_value_t<US>;
+  using E = detail::MeshModelEval<Deriv, DT, Fn, X, U>;
+  constexpr int nx = E::nx, nu = E::nu, nf = E::nf;
+  static_assert(Deriv < 2 || (detail::is_rn<X>::value && detail::is_rn<U>::value), "Deriv == 2 needs Rn state and input");
+  const std::size_t N = m.N_colloc(), nv = 2 + nx * (N + 1) + nu * N;
+  if (!out.allocated) {
+    out.F.assign(nf, 0.0);
+    if constexpr (Deriv >= 1) {
+      out.dF.rows = nf;
+      out.dF.cols = (int32_t)nv;
+      out.dF.rowptr.resize(nf + 1);
+      out.dF.colind.resize(nf * nv);
+      out.dF.val.assign(nf * nv, 0.0);
+      for (int r = 0; r <= nf; ++r) out.dF.rowptr[r] = (int32_t)(r * nv);
+      for (std::size_t e = 0; e < nf * nv; ++e) out.dF.colind[e] = (int32_t)(e % nv);
+    }
+    if constexpr (Deriv >= 2) meshfn::d2_pattern((int64_t)N, nx, nu, out.d2F);
+    out.allocated = true;
+  }
+  set_zero(out);
+  const std::vector<double> taus = m.all_nodes(), wts = m.all_weights();
+  const double h = tf - t0;
+  auto xit = std::begin(xs);
+  auto uit = std::begin(us);
+  E ev;
+  for (std::size_t i = 0; i < N; ++i, ++xit, ++uit) {
+    const double tau = taus[i], w = wts[i];
+    ev(f, t0 + (tf - t0) * tau, *xit, *uit);
+    for (int r = 0; r < nf; ++r) meshfn::integrate_F_add(out.F[r], w, h, ev.f[r]);
+    if constexpr (Deriv >= 1) {
+      for (int r = 0; r < nf; ++r) {
+        double * v = out.dF.val.data() + r * nv;
+        meshfn::integrate_dt0_add(v[0], w, h, tau, ev.f[r], ev.J(r, 0));
+        meshfn::integrate_dtf_add(v[1], w, h, tau, ev.f[r], ev.J(r, 0));
+        for (int c = 0; c < nx; ++c) v[2 + i * nx + c] = meshfn::integrate_dz(w, h, ev.J(r, 1 + c));
+        for (int c = 0; c < nu; ++c) v[2 + (N + 1) * nx + i * nu + c] = meshfn::integrate_dz(w, h, ev.J(r, 1 + nx + c));
+      }
+    }
+    if constexpr (Deriv >= 2) detail::meshfn_d2_node<nx, nu, nf>(out.d2F, N, i, out.lambda.data(), w, h, tau, true, ev.J, ev.H);
+  }
+}
+
+/// The collocation defects w_i ((tf - t0) f(t_i, x_i, u_i) - sum_k D(k, j) x_{M + k}), interval by interval (:450-665).
+/// Row (node M_s + j of interval s, component d) of dF holds t0, tf, one entry per node k = 0 .. K_s of the interval
+/// (component d of x_{M_s + k}; for k == j the whole nx-wide block) and the nu columns of u_i: 2 + K_s + nx + nu entries.
+template<uint8_t Deriv, diff::Type DT = diff::Type::Default, class M, class Fn, class XS, class US>
+  requires(Deriv <= 2)
+void mesh_dyn(MeshValue<Deriv> & out, const M & m, Fn & f, const double t0, const double tf, XS && xs, US && us)
+{
+  using X = detail::meshfn_value_t<XS>;
+  using U = detail::meshfn_value_t<US>;
+  using E = detail::MeshModelEval<Deriv, DT, Fn, X, U>;
+  constexpr int nx = E::nx, nu = E::nu, nf = E::nf;
+  static_assert(nx == nf, "Output dimension must be same as state dimension");
+  static_assert(detail::is_rn<X>::value, "mesh_dyn: the defect is linear in the node states and needs a vector state (Rn)");
+  static_assert(Deriv < 2 || detail::is_rn<U>::value, "Deriv == 2 needs Rn state and input");
+  const std::size_t N = m.N_colloc(), S = m.N_ivals();
+  if (!out.allocated) {
+    out.F.assign(N * nx, 0.0);
+    if constexpr (Deriv >= 1) {
+      std::vector<int32_t> K(S);
+      for (std::size_t s = 0; s < S; ++s) K[s] = (int32_t)m.N_colloc_ival(s);
+      const int64_t nnz = meshfn::dyn_pattern((int)S, K.data(), nx, nu, nullptr, nullptr);
+      out.dF.rows       = (int32_t)(N * nx);
+      out.dF.cols       = (int32_t)(2 + nx * (N + 1) + nu * N);
+      out.dF.rowptr.assign(N * nx + 1, 0);
+      out.dF.colind.assign((std::size_t)nnz, 0);
+      out.dF.val.assign((std::size_t)nnz, 0.0);
+      meshfn::dyn_pattern((int)S, K.data(), nx, nu, out.dF.rowptr.data(), out.dF.colind.data());
+    }
+    if constexpr (Deriv >= 2) meshfn::d2_pattern((int64_t)N, nx, nu, out.d2F);
+    out.allocated = true;
+  }
+  set_zero(out);
+  const std::vector<double> taus = m.all_nodes(), wts = m.all_weights();
+  const double h = tf - t0;
+  auto xit = std::begin(xs);
+  auto uit = std::begin(us);
+  E ev;
+  std::size_t M0 = 0;
+  for (std::size_t s = 0; s < S; ++s) {
+    const int K             = (int)m.N_colloc_ival(s);
+    const auto [alpha, Dus] = m.interval_diffmat_unscaled(s);
+    // component d of the interval's K + 1 node states is read at xk[k * nx + d]
+    double xk[(detail::kMeshMaxDegree + 1) * (nx > 0 ? nx : 1)];
+    {
+      auto xj = xit;
+      for (int k = 0; k <= K; ++k, ++xj)
+        for (int d = 0; d < nx; ++d) xk[k * nx + d] = (*xj).v[d];
+    }
+    for (int j = 0; j < K; ++j, ++xit, ++uit) {
+      const std::size_t i = M0 + j;
+      const double tau = taus[i], w = wts[i];
+      const double * Dcol = Dus.a.data() + (std::size_t)j * (K + 1);
+      ev(f, t0 + (tf - t0) * tau, *xit, *uit);
+      for (int d = 0; d < nx; ++d) out.F[i * nx + d] = meshfn::dyn_F(K, w, h, alpha, Dcol, ev.f[d], xk + d, nx);
+      if constexpr (Deriv >= 1) {
+        for (int d = 0; d < nx; ++d) {
+          double * v = out.dF.val.data() + out.dF.rowptr[i * nx + d];
+          for (int p = 0; p < 2 + K + nx + nu; ++p) {
+            int kind, idx;
+            meshfn::dyn_decode(p, j, K, nx, kind, idx);
+            v[p] = kind == 0   ? meshfn::dyn_dt0(w, h, tau, ev.f[d], ev.J(d, 0))
+                   : kind == 1 ? meshfn::dyn_dtf(w, h, tau, ev.f[d], ev.J(d, 0))
+                   : kind == 2 ? meshfn::dyn_coef(w, alpha, Dcol[idx])
+                   : kind == 3 ? meshfn::dyn_own(w, h, alpha, Dcol[j], ev.J(d, 1 + idx), idx == d)
+                               : meshfn::dyn_du(w, h, ev.J(d, 1 + nx + idx));
+          }
+        }
+      }
+      if constexpr (Deriv >= 2) detail::meshfn_d2_node<nx, nu, nf>(out.d2F, N, i, out.lambda.data() + i * nx, w, h, tau, true, ev.J, ev.H);
+    }
+    M0 += K;
+  }
+}
+
+}  // namespace smooth_feedback_amd

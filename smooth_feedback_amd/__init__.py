@@ -15,8 +15,10 @@ from .ekf import (ekf_predict_batch_device, ekf_predict_batch_host, ekf_predict_
 from .pid import (PIDGroup, pid_rollout_batch_device, pid_rollout_batch_host, pid_rollout_spline_batch_host,  # noqa: F401
                   pid_step_batch_device, pid_step_batch_host)
 from .spline import spline_eval_batch_host, spline_fit_cubic_batch_host  # noqa: F401
-from .mesh import (PHMesh, mesh_dyn_error_batch_device, mesh_dyn_error_batch_host, mesh_resample_batch_device,  # noqa: F401
-                   mesh_resample_batch_host)
+from .mesh import (PHMesh, mesh_dyn_batch, mesh_dyn_batch_device, mesh_dyn_batch_host, mesh_dyn_error_batch_device,  # noqa: F401
+                   mesh_dyn_error_batch_host, mesh_dyn_pattern, mesh_eval_batch, mesh_eval_batch_device, mesh_eval_batch_host,
+                   mesh_eval_pattern, mesh_integrate_batch, mesh_integrate_batch_device, mesh_integrate_batch_host,
+                   mesh_resample_batch_device, mesh_resample_batch_host)
 from .mpc import LIE_RN, LIE_SE2, LIE_SE3, LIE_SO3, MPCLayout, MPCSwarm  # noqa: F401
 
 __version__ = "0.1.0"

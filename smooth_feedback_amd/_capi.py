@@ -148,6 +148,14 @@ def _load():
     L.sfb_mesh_resample_batch.argtypes = L.sfb_mesh_resample_batch_host.argtypes + [vp]
     L.sfb_mesh_dyn_error_batch_host.argtypes = [mesh, i64, i32, dp, dp, dp, dp]
     L.sfb_mesh_dyn_error_batch.argtypes = L.sfb_mesh_dyn_error_batch_host.argtypes + [vp]
+    L.sfb_mesh_eval_pattern.argtypes = [mesh, i32, i32, i32, vp, vp, C.POINTER(C.c_int64)]
+    L.sfb_mesh_dyn_pattern.argtypes = [mesh, i32, i32, vp, vp, C.POINTER(C.c_int64)]
+    L.sfb_mesh_eval_batch_host.argtypes = [mesh, i64, i32, i32, i32, i32] + [dp] * 6
+    L.sfb_mesh_eval_batch.argtypes = L.sfb_mesh_eval_batch_host.argtypes + [vp]
+    L.sfb_mesh_integrate_batch_host.argtypes = [mesh, i64, i32, i32, i32] + [dp] * 6
+    L.sfb_mesh_integrate_batch.argtypes = L.sfb_mesh_integrate_batch_host.argtypes + [vp]
+    L.sfb_mesh_dyn_batch_host.argtypes = [mesh, i64, i32, i32] + [dp] * 7
+    L.sfb_mesh_dyn_batch.argtypes = L.sfb_mesh_dyn_batch_host.argtypes + [vp]
     lay = C.POINTER(SfbMPCLayout)
     L.sfb_mpc_record_doubles.argtypes = [lay, i32]
     L.sfb_mpc_record_doubles.restype = i64

@@ -1,4 +1,5 @@
-// C-ABI for the batched ph-mesh path (include/sfb.h): resampling onto the degree-raised mesh, dynamics-error estimate.
+// C-ABI for the batched ph-mesh path (include/sfb.h): resampling onto the degree-raised mesh, dynamics-error estimate,
+// and the functions over the mesh (eval, integrate, dyn) with first derivatives and their sparsity patterns.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -10,6 +11,7 @@
 
 #include "../../include/sfb.h"
 #include "../../include/smooth_feedback_amd/mesh.hpp"
+#include "../../include/smooth_feedback_amd/mesh_function.hpp"
 #include "capi_common.h"
 #include "mesh_kernel.h"
 
@@ -75,10 +77,22 @@ struct MeshEntry {
   sfb::DeviceBlock blk;
   sfb::MeshDevice dev;
 };
+// what the mesh-function kernels read, per (mesh, nx, nu): nodes, weights, differentiation matrices and mesh_dyn's
+// entry -> row table; kept and dropped by the same rule as the interval lists
+struct MeshFnKey {
+  MeshKey mesh;
+  int32_t nx, nu;
+  bool operator<(const MeshFnKey &o) const { return std::tie(nx, nu, mesh) < std::tie(o.nx, o.nu, o.mesh); }
+};
+struct MeshFnEntry {
+  sfb::DeviceBlock blk;
+  sfb::MeshFnDevice dev;
+};
 struct MeshCache {
   std::mutex mu;
   std::map<int, sfb::DeviceBlock> tables;
   std::map<MeshKey, MeshEntry> meshes;
+  std::map<MeshFnKey, MeshFnEntry> fns;
 };
 MeshCache &cache()
 {
@@ -160,9 +174,205 @@ sfb_status with_device_mesh(const sfb_mesh *mesh, Launch &&launch)
   return launch(out);
 }
 
+// launch(m) with the device tables of (mesh, nx, nu), under the cache's lock
+template<class Launch>
+sfb_status with_device_meshfn(const sfb_mesh *mesh, int32_t nx, int32_t nu, Launch &&launch)
+{
+  int device = 0;
+  hipError_t e = hipGetDevice(&device);
+  if (e != hipSuccess) return sfb::hip_fail(e, "hipGetDevice");
+  MeshCache &c = cache();
+  std::lock_guard<std::mutex> lock(c.mu);
+  MeshFnKey key{MeshKey{device, std::vector<int32_t>(mesh->K, mesh->K + mesh->nivals), std::vector<uint64_t>(mesh->nivals)}, nx, nu};
+  std::memcpy(key.mesh.tau0.data(), mesh->tau0, sizeof(double) * mesh->nivals);
+  auto it = c.fns.find(key);
+  if (it == c.fns.end()) {
+    size_t here = 0;
+    for (const auto &m : c.fns) here += m.first.mesh.device == device ? 1 : 0;
+    if (here >= kMeshesKept) {
+      if ((e = hipDeviceSynchronize()) != hipSuccess) return sfb::hip_fail(e, "hipDeviceSynchronize");
+      for (auto m = c.fns.begin(); m != c.fns.end();) m = m->first.mesh.device == device ? c.fns.erase(m) : std::next(m);
+    }
+    const int32_t n = mesh->nivals;
+    std::vector<sfb::MeshFnIval> iv(n);
+    std::vector<int32_t> node_ival;
+    std::vector<double> tau, w, D;
+    int32_t N = 0;
+    for (int32_t s = 0; s < n; ++s) {  // the expressions of Mesh::interval_nodes / interval_weights / interval_diffmat_unscaled
+      const L::detail::LgrTable &T = L::detail::lgr_table(mesh->K[s]);
+      const double tau0 = mesh->tau0[s], tauf = s + 1 < n ? mesh->tau0[s + 1] : 1.0, al = (tauf - tau0) / 2;
+      iv[s] = sfb::MeshFnIval{mesh->K[s], N, (int32_t)D.size(), 0, 2. / (tauf - tau0)};
+      for (int32_t j = 0; j < mesh->K[s]; ++j) {
+        tau.push_back(tau0 + al * (T.tau[j] + 1));
+        w.push_back(al * T.w[j]);
+        node_ival.push_back(s);
+      }
+      D.insert(D.end(), T.Dus.a.begin(), T.Dus.a.end());
+      N += mesh->K[s];
+    }
+    const int64_t nnz = L::meshfn::dyn_pattern(n, mesh->K, nx, nu, nullptr, nullptr);
+    std::vector<int32_t> rowptr((size_t)N * nx + 1, 0), colind((size_t)nnz), entry_row((size_t)nnz);
+    L::meshfn::dyn_pattern(n, mesh->K, nx, nu, rowptr.data(), colind.data());
+    for (int32_t r = 0; r < N * nx; ++r)
+      for (int32_t q = rowptr[r]; q < rowptr[r + 1]; ++q) entry_row[q] = r;
+    sfb::Staging st;
+    sfb::MeshFnIval *div;
+    int32_t *dni, *drp, *der;
+    double *dtau, *dw, *dD;
+    st.add(&div, (size_t)n, sfb::Staging::In, iv.data());
+    st.add(&dtau, tau.size(), sfb::Staging::In, tau.data());
+    st.add(&dw, w.size(), sfb::Staging::In, w.data());
+    st.add(&dD, D.size(), sfb::Staging::In, D.data());
+    st.add(&dni, node_ival.size(), sfb::Staging::In, node_ival.data());
+    st.add(&drp, rowptr.size(), sfb::Staging::In, rowptr.data());
+    st.add(&der, entry_row.size(), sfb::Staging::In, entry_row.data());
+    MeshFnEntry ent;
+    const sfb_status rc = sfb::stage_per_call(st, ent.blk);
+    if (rc != SFB_OK) return rc;
+    if ((e = st.upload()) != hipSuccess) return sfb::hip_fail(e, "mesh function tables upload");
+    ent.dev = sfb::MeshFnDevice{n, N, nx, nu, nnz, div, dni, dtau, dw, dD, drp, der};
+    it      = c.fns.emplace(std::move(key), std::move(ent)).first;
+  }
+  return launch(it->second.dev);
+}
+
+// what the three mesh-function entries refuse, in this order: the mesh, the batch, negative sizes, an index range the
+// 32-bit patterns cannot hold, a derivative input without its output (or the reverse), a NULL array with work to do
+sfb_status meshfn_check(const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, int32_t nf, const double *t0, const double *tf, bool needs_X,
+                        const double *X, const double *F, const double *dF, double *out_F, double *out_dF)
+{
+  const sfb_status st = mesh_check(mesh, batch);
+  if (st != SFB_OK) return st;
+  if (nx < 0) return sfb::fail(SFB_ERR_INVALID_ARG, "nx < 0");
+  if (nu < 0) return sfb::fail(SFB_ERR_INVALID_ARG, "nu < 0");
+  if (nf < 0) return sfb::fail(SFB_ERR_INVALID_ARG, "nf < 0");
+  const int64_t N = mesh_nodes(mesh), nv = 2 + (int64_t)nx * (N + 1) + (int64_t)nu * N;
+  if (nv > 0x7fffffff || N * nf * (2 + (int64_t)sfb::kMeshMaxK + nx + nu) > 0x7fffffff || (int64_t)nf * (nv + 1) > 0x7fffffff)
+    return sfb::fail(SFB_ERR_INVALID_ARG, "mesh function: more variables or entries than 32-bit indices hold");
+  if ((dF == nullptr) != (out_dF == nullptr)) return sfb::fail(SFB_ERR_INVALID_ARG, "dF and the derivative output: both or neither");
+  if (batch > 0 && nf > 0 && (!t0 || !tf || !F || !out_F || (needs_X && !X))) return sfb::fail(SFB_ERR_INVALID_ARG, "NULL array");
+  return SFB_OK;
+}
+
+sfb_status pattern_check(const sfb_mesh *mesh, int32_t nx, int32_t nu, int32_t nf, int32_t *rowptr, int32_t *colind, int64_t *nnz)
+{
+  const sfb_status st = mesh_check(mesh, 0);
+  if (st != SFB_OK) return st;
+  if (nx < 0) return sfb::fail(SFB_ERR_INVALID_ARG, "nx < 0");
+  if (nu < 0) return sfb::fail(SFB_ERR_INVALID_ARG, "nu < 0");
+  if (nf < 0) return sfb::fail(SFB_ERR_INVALID_ARG, "nf < 0");
+  const int64_t N = mesh_nodes(mesh), nv = 2 + (int64_t)nx * (N + 1) + (int64_t)nu * N;
+  if (nv > 0x7fffffff || N * nf * (2 + (int64_t)sfb::kMeshMaxK + nx + nu) > 0x7fffffff)
+    return sfb::fail(SFB_ERR_INVALID_ARG, "mesh function: more variables or entries than 32-bit indices hold");
+  if ((rowptr == nullptr) != (colind == nullptr)) return sfb::fail(SFB_ERR_INVALID_ARG, "rowptr and colind: both or neither");
+  if (!rowptr && !nnz) return sfb::fail(SFB_ERR_INVALID_ARG, "NULL array");
+  return SFB_OK;
+}
+
+enum MeshFn { kEval, kIntegrate, kDyn };
+
+sfb_status meshfn_device(MeshFn fn, const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, int32_t nf, int scale, const double *t0,
+                         const double *tf, const double *X, const double *F, const double *dF, double *out_F, double *out_dF, void *stream)
+{
+  sfb_status st = meshfn_check(mesh, batch, nx, nu, nf, t0, tf, fn == kDyn, X, F, dF, out_F, out_dF);
+  if (st != SFB_OK) return st;
+  st = sfb::require_device();
+  if (st != SFB_OK) return st;
+  if (batch == 0 || nf == 0) return SFB_OK;
+  return with_device_meshfn(mesh, nx, nu, [&](const sfb::MeshFnDevice &m) {
+    sfb::MeshFnArgs a{};
+    a.m = m; a.batch = batch; a.nf = nf; a.scale = scale ? 1 : 0; a.t0 = t0; a.tf = tf; a.X = X; a.F = F; a.dF = dF; a.out_F = out_F; a.out_dF = out_dF;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const hipError_t e  = fn == kEval ? sfb::mesh_eval_launch(a, s) : fn == kIntegrate ? sfb::mesh_integrate_launch(a, s) : sfb::mesh_dyn_launch(a, s);
+    return e != hipSuccess ? sfb::hip_fail(e, "mesh function kernel launch") : SFB_OK;
+  });
+}
+
+sfb_status meshfn_host(MeshFn fn, const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, int32_t nf, int scale, const double *t0,
+                       const double *tf, const double *X, const double *F, const double *dF, double *out_F, double *out_dF)
+{
+  sfb_status st = meshfn_check(mesh, batch, nx, nu, nf, t0, tf, fn == kDyn, X, F, dF, out_F, out_dF);
+  if (st != SFB_OK) return st;
+  st = sfb::require_device();
+  if (st != SFB_OK) return st;
+  if (batch == 0 || nf == 0) return SFB_OK;
+  const size_t B = (size_t)batch, N = (size_t)mesh_nodes(mesh), nz = 1 + (size_t)nx + (size_t)nu, nv = 2 + (size_t)nx * (N + 1) + (size_t)nu * N;
+  const size_t rows = fn == kIntegrate ? (size_t)nf : N * (size_t)nf;
+  const size_t dcount = fn == kIntegrate ? (size_t)nf * nv
+                        : fn == kEval    ? N * (size_t)nf * (2 + (size_t)nx + (size_t)nu)
+                                         : (size_t)L::meshfn::dyn_pattern(mesh->nivals, mesh->K, nx, nu, nullptr, nullptr);
+  using S = sfb::Staging;
+  S s;
+  double *d0, *d1, *dX = nullptr, *dFv, *ddF = nullptr, *doF, *dodF = nullptr;
+  s.add(&d0, B, S::In, t0); s.add(&d1, B, S::In, tf);
+  if (fn == kDyn) s.add(&dX, B * (N + 1) * (size_t)nx, S::In, X);
+  s.add(&dFv, B * N * (size_t)nf, S::In, F);
+  if (dF) s.add(&ddF, B * N * (size_t)nf * nz, S::In, dF);
+  s.add(&doF, B * rows, S::Out, out_F);
+  if (dF) s.add(&dodF, B * dcount, S::Out, out_dF);
+  sfb::DeviceBlock blk;
+  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
+  hipError_t e = s.upload();
+  if (e != hipSuccess) return sfb::hip_fail(e, "mesh function upload");
+  st = meshfn_device(fn, mesh, batch, nx, nu, nf, scale, d0, d1, dX, dFv, ddF, doF, dodF, nullptr);
+  if (st != SFB_OK) return st;
+  if ((e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
+  if (e != hipSuccess) return sfb::hip_fail(e, "mesh function download");
+  return SFB_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+sfb_status sfb_mesh_eval_pattern(const sfb_mesh *mesh, int32_t nx, int32_t nu, int32_t nf, int32_t *rowptr, int32_t *colind, int64_t *nnz)
+{
+  const sfb_status st = pattern_check(mesh, nx, nu, nf, rowptr, colind, nnz);
+  if (st != SFB_OK) return st;
+  const int64_t n = L::meshfn::eval_pattern(mesh_nodes(mesh), nx, nu, nf, rowptr, colind);
+  if (nnz) *nnz = n;
+  return SFB_OK;
+}
+
+sfb_status sfb_mesh_dyn_pattern(const sfb_mesh *mesh, int32_t nx, int32_t nu, int32_t *rowptr, int32_t *colind, int64_t *nnz)
+{
+  const sfb_status st = pattern_check(mesh, nx, nu, nx, rowptr, colind, nnz);
+  if (st != SFB_OK) return st;
+  const int64_t n = L::meshfn::dyn_pattern(mesh->nivals, mesh->K, nx, nu, rowptr, colind);
+  if (nnz) *nnz = n;
+  return SFB_OK;
+}
+
+sfb_status sfb_mesh_eval_batch(const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, int32_t nf, int scale, const double *t0, const double *tf,
+                               const double *F, const double *dF, double *out_F, double *out_dF_val, void *stream)
+{
+  return meshfn_device(kEval, mesh, batch, nx, nu, nf, scale, t0, tf, nullptr, F, dF, out_F, out_dF_val, stream);
+}
+sfb_status sfb_mesh_integrate_batch(const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, int32_t nf, const double *t0, const double *tf,
+                                    const double *F, const double *dF, double *out_F, double *out_dF, void *stream)
+{
+  return meshfn_device(kIntegrate, mesh, batch, nx, nu, nf, 0, t0, tf, nullptr, F, dF, out_F, out_dF, stream);
+}
+sfb_status sfb_mesh_dyn_batch(const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, const double *t0, const double *tf, const double *X,
+                              const double *F, const double *dF, double *out_F, double *out_dF_val, void *stream)
+{
+  return meshfn_device(kDyn, mesh, batch, nx, nu, nx, 0, t0, tf, X, F, dF, out_F, out_dF_val, stream);
+}
+sfb_status sfb_mesh_eval_batch_host(const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, int32_t nf, int scale, const double *t0,
+                                    const double *tf, const double *F, const double *dF, double *out_F, double *out_dF_val)
+{
+  return meshfn_host(kEval, mesh, batch, nx, nu, nf, scale, t0, tf, nullptr, F, dF, out_F, out_dF_val);
+}
+sfb_status sfb_mesh_integrate_batch_host(const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, int32_t nf, const double *t0, const double *tf,
+                                         const double *F, const double *dF, double *out_F, double *out_dF)
+{
+  return meshfn_host(kIntegrate, mesh, batch, nx, nu, nf, 0, t0, tf, nullptr, F, dF, out_F, out_dF);
+}
+sfb_status sfb_mesh_dyn_batch_host(const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, const double *t0, const double *tf, const double *X,
+                                   const double *F, const double *dF, double *out_F, double *out_dF_val)
+{
+  return meshfn_host(kDyn, mesh, batch, nx, nu, nx, 0, t0, tf, X, F, dF, out_F, out_dF_val);
+}
 
 sfb_status sfb_mesh_resample_batch(const sfb_mesh *mesh, int64_t batch, int32_t dim, int extend, const double *vals, double *out, void *stream)
 {

@@ -11,9 +11,19 @@
 // with its column of the integration matrix (dyn_error_point of dyn_error.hpp, the function the host estimate calls;
 // the F and X_0 reads are LDS broadcasts), and the maxima are taken across the 16 slots with cross-lane moves.  Lane 0
 // of the slot group writes the interval's error.  Plain loads and stores.
+//
+// mesh_eval / mesh_integrate / mesh_dyn (include/sfb.h: sfb_mesh_eval_batch, ...; model-free: the caller's model values
+// F [batch][N][nf] and Jacobians dF [batch][N][nf][1 + nx + nu] come in): one lane per output double, the entry index
+// fastest and the agent slowest, so a wave stores 512 contiguous bytes.  Every entry is one call of the law of
+// mesh_function.hpp (namespace meshfn), the functions the host front calls.  The CSR values of mesh_eval have rows of one
+// length and are decoded by division; those of mesh_dyn go entry -> row through the per-(mesh, nx, nu) table
+// dyn_entry_row (4 bytes per entry, shared by every agent: cache resident) and row -> position through dyn_rowptr, and
+// read the row's own block of dF contiguously.  mesh_integrate's t0, tf and F lanes loop over the nodes in node order
+// (the host's order of summation); its x and u lanes do one product.  No LDS, plain loads and stores.
 #include "mesh_kernel.h"
 
 #include "../../include/smooth_feedback_amd/dyn_error.hpp"
+#include "../../include/smooth_feedback_amd/mesh_function.hpp"
 
 namespace sfb {
 
@@ -91,7 +101,163 @@ __global__ void __launch_bounds__(64) mesh_dyn_error_kernel(const MeshDynErrorAr
   if (live && slot == 0) a.errs[pair] = L::dyn_error_combine(e2, x2, bad);
 }
 
+namespace MF = smooth_feedback_amd::meshfn;
+
+// lane t -> (agent, entry of that agent), by a 32-bit division when both fit (wave-uniform); at the benchmark shape the
+// kernels measured the same with the 64-bit division alone
+__device__ inline void agent_entry(const int64_t t, const int64_t per, int64_t &b, int &e)
+{
+  if (((uint64_t)t | (uint64_t)per) >> 32 == 0) {
+    const uint32_t q = (uint32_t)t / (uint32_t)per;
+    b = q;
+    e = (int)((uint32_t)t - q * (uint32_t)per);
+  } else {
+    b = t / per;
+    e = (int)(t - b * per);
+  }
+}
+
+__global__ void __launch_bounds__(256) mesh_eval_F_kernel(const MeshFnArgs a)
+{
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int per   = a.m.N * a.nf;
+  if (t >= a.batch * per) return;
+  int64_t b;
+  int e;
+  agent_entry(t, per, b, e);
+  a.out_F[t] = MF::eval_F(a.scale ? a.m.w[e / a.nf] : 1., a.F[t]);
+}
+
+__global__ void __launch_bounds__(256) mesh_eval_dF_kernel(const MeshFnArgs a)
+{
+  const int per   = 2 + a.m.nx + a.m.nu, rows = a.m.N * a.nf;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= a.batch * rows * per) return;
+  int64_t b;
+  int e;
+  agent_entry(t, (int64_t)rows * per, b, e);
+  const int row = e / per, p = e - row * per;  // (node, output) and the position in its row
+  const int i   = row / a.nf;
+  const double w = a.scale ? a.m.w[i] : 1., tau = a.m.tau[i];
+  const double *df = a.dF + (b * rows + row) * (per - 1);
+  a.out_dF[t] = p == 0 ? MF::eval_dt0(w, tau, df[0]) : p == 1 ? MF::eval_dtf(w, tau, df[0]) : MF::eval_dz(w, df[p - 1]);
+}
+
+__global__ void __launch_bounds__(256) mesh_integrate_kernel(const MeshFnArgs a)
+{
+  const int nx = a.m.nx, nu = a.m.nu, nf = a.nf, N = a.m.N, nz = 1 + nx + nu;
+  const int64_t nv  = 2 + (int64_t)nx * (N + 1) + (int64_t)nu * N;
+  const int64_t per = a.dF ? nf * (nv + 1) : nf;  // per agent: nf values, then the nf x nv derivative block
+  const int64_t t   = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= a.batch * per) return;
+  int64_t b;
+  int q;
+  agent_entry(t, per, b, q);
+  const double h  = a.tf[b] - a.t0[b];
+  const double *Fb = a.F + b * N * nf;
+  if (q < nf) {
+    double acc = 0.0;
+    for (int i = 0; i < N; ++i) MF::integrate_F_add(acc, a.m.w[i], h, Fb[(int64_t)i * nf + q]);
+    a.out_F[b * nf + q] = acc;
+    return;
+  }
+  const int e = q - nf;
+  const int r = e / (int)nv;
+  const int64_t c = e - r * (int)nv;
+  const double *dfb = a.dF + (b * N * nf + r) * nz;  // node i's row r at dfb + i nf nz
+  double v = 0.0;
+  if (c < 2) {
+    for (int i = 0; i < N; ++i) {
+      const double f = Fb[(int64_t)i * nf + r], dft = dfb[(int64_t)i * nf * nz];
+      if (c == 0) MF::integrate_dt0_add(v, a.m.w[i], h, a.m.tau[i], f, dft);
+      else MF::integrate_dtf_add(v, a.m.w[i], h, a.m.tau[i], f, dft);
+    }
+  } else if (c < 2 + (int64_t)nx * N) {
+    const int i = (int)((c - 2) / nx), k = (int)((c - 2) - (int64_t)i * nx);
+    v           = MF::integrate_dz(a.m.w[i], h, dfb[(int64_t)i * nf * nz + 1 + k]);
+  } else if (c >= 2 + (int64_t)nx * (N + 1)) {
+    const int64_t cu = c - 2 - (int64_t)nx * (N + 1);
+    const int i = (int)(cu / nu), k = (int)(cu - (int64_t)i * nu);
+    v           = MF::integrate_dz(a.m.w[i], h, dfb[(int64_t)i * nf * nz + 1 + nx + k]);
+  }  // (the columns of x_N stay zero)
+  a.out_dF[b * nf * nv + e] = v;
+}
+
+__global__ void __launch_bounds__(256) mesh_dyn_F_kernel(const MeshFnArgs a)
+{
+  const int nx = a.m.nx, N = a.m.N;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= a.batch * N * nx) return;
+  int64_t b;
+  int e;
+  agent_entry(t, (int64_t)N * nx, b, e);
+  const int i = e / nx, d = e - i * nx;
+  const MeshFnIval iv = a.m.ivals[a.m.node_ival[i]];
+  const int j         = i - iv.M;
+  const double *x     = a.X + (b * (N + 1) + iv.M) * nx + d;
+  a.out_F[t] = MF::dyn_F(iv.K, a.m.w[i], a.tf[b] - a.t0[b], iv.alpha, a.m.D + iv.Doff + j * (iv.K + 1), a.F[t], x, nx);
+}
+
+__global__ void __launch_bounds__(256) mesh_dyn_dF_kernel(const MeshFnArgs a)
+{
+  const int nx = a.m.nx, nu = a.m.nu, N = a.m.N, nz = 1 + nx + nu;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= a.batch * a.m.dyn_nnz) return;
+  int64_t b;
+  int e;
+  agent_entry(t, a.m.dyn_nnz, b, e);
+  const int row   = a.m.dyn_entry_row[e];
+  const int p     = e - a.m.dyn_rowptr[row];
+  const int i = row / nx, d = row - i * nx;
+  const MeshFnIval iv = a.m.ivals[a.m.node_ival[i]];
+  const int j         = i - iv.M;
+  int kind, idx;
+  MF::dyn_decode(p, j, iv.K, nx, kind, idx);
+  const double w = a.m.w[i], tau = a.m.tau[i], h = a.tf[b] - a.t0[b];
+  const double *Dcol = a.m.D + iv.Doff + j * (iv.K + 1);
+  const int64_t fr   = (b * N + i) * nx + d;
+  const double *df   = a.dF + fr * nz;
+  double v;
+  if (kind == 0) v = MF::dyn_dt0(w, h, tau, a.F[fr], df[0]);
+  else if (kind == 1) v = MF::dyn_dtf(w, h, tau, a.F[fr], df[0]);
+  else if (kind == 2) v = MF::dyn_coef(w, iv.alpha, Dcol[idx]);
+  else if (kind == 3) v = MF::dyn_own(w, h, iv.alpha, Dcol[j], df[1 + idx], idx == d);
+  else v = MF::dyn_du(w, h, df[1 + nx + idx]);
+  a.out_dF[t] = v;
+}
+
+template<class Kern>
+hipError_t lane_launch(Kern kern, const int64_t total, const MeshFnArgs &a, hipStream_t stream)
+{
+  if (total <= 0) return hipSuccess;
+  const int64_t blocks = (total + 255) / 256;
+  if (blocks > 0x7fffffff) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
 }  // namespace
+
+hipError_t mesh_eval_launch(const MeshFnArgs &a, hipStream_t stream)
+{
+  const int64_t rows = a.batch * a.m.N * a.nf;
+  const hipError_t e = lane_launch(mesh_eval_F_kernel, rows, a, stream);
+  if (e != hipSuccess || !a.dF) return e;
+  return lane_launch(mesh_eval_dF_kernel, rows * (2 + a.m.nx + a.m.nu), a, stream);
+}
+
+hipError_t mesh_integrate_launch(const MeshFnArgs &a, hipStream_t stream)
+{
+  const int64_t nv = 2 + (int64_t)a.m.nx * (a.m.N + 1) + (int64_t)a.m.nu * a.m.N;
+  return lane_launch(mesh_integrate_kernel, a.batch * (a.dF ? a.nf * (nv + 1) : a.nf), a, stream);
+}
+
+hipError_t mesh_dyn_launch(const MeshFnArgs &a, hipStream_t stream)
+{
+  const hipError_t e = lane_launch(mesh_dyn_F_kernel, a.batch * a.m.N * a.m.nx, a, stream);
+  if (e != hipSuccess || !a.dF) return e;
+  return lane_launch(mesh_dyn_dF_kernel, a.batch * a.m.dyn_nnz, a, stream);
+}
 
 hipError_t mesh_resample_launch(const MeshResampleArgs &a, hipStream_t stream)
 {

@@ -1,5 +1,5 @@
-// Batched ph-mesh kernels (mesh.hip): resampling of node values onto the degree-raised mesh and the collocation
-// dynamics-error estimate.  Launch arguments; the tables are built on the host by capi_mesh.hip from mesh.hpp.
+// Batched ph-mesh kernels (mesh.hip): resampling of node values onto the degree-raised mesh, the collocation
+// dynamics-error estimate, and the functions over the mesh (eval, integrate, dyn) with their first derivatives.  Launch arguments; the tables are built on the host by capi_mesh.hip from mesh.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -47,5 +47,36 @@ struct MeshDynErrorArgs {
 
 hipError_t mesh_resample_launch(const MeshResampleArgs &a, hipStream_t stream);
 hipError_t mesh_dyn_error_launch(const MeshDynErrorArgs &a, hipStream_t stream);
+
+// ---- functions over the mesh with first derivatives (mesh_function.hpp: mesh_eval, mesh_integrate, mesh_dyn) ----
+// one interval, as these kernels see it
+struct MeshFnIval {
+  int32_t K;     // collocation points
+  int32_t M;     // index of its first node
+  int32_t Doff;  // its (K + 1) x K unscaled differentiation matrix starts at D + Doff: D(k, j) at [k + j (K + 1)]
+  int32_t pad;
+  double alpha;  // 2 / (tauf - tau0)
+};
+// what one (mesh, nx, nu) needs on the device; built on the host by capi_mesh.hip and cached with the interval lists
+struct MeshFnDevice {
+  int32_t nivals, N, nx, nu;
+  int64_t dyn_nnz;
+  const MeshFnIval *ivals;       // [nivals]
+  const int32_t *node_ival;      // [N] interval of every node
+  const double *tau, *w;         // [N] nodes on [0, 1] and quadrature weights
+  const double *D;
+  const int32_t *dyn_rowptr;     // [N nx + 1] CSR row starts of mesh_dyn's dF
+  const int32_t *dyn_entry_row;  // [dyn_nnz] the decode table: row (node nx + component) of every entry
+};
+struct MeshFnArgs {
+  MeshFnDevice m;
+  int64_t batch;
+  int32_t nf, scale;
+  const double *t0, *tf, *X, *F, *dF;  // dF NULL: values only
+  double *out_F, *out_dF;
+};
+hipError_t mesh_eval_launch(const MeshFnArgs &a, hipStream_t stream);
+hipError_t mesh_integrate_launch(const MeshFnArgs &a, hipStream_t stream);
+hipError_t mesh_dyn_launch(const MeshFnArgs &a, hipStream_t stream);
 
 }  // namespace sfb
