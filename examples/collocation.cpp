@@ -15,6 +15,7 @@
 #include <smooth/feedback/mpc.hpp>
 
 #include "lie_eval.h"
+#include "ocp_nlp_harness.h"
 #include "rigid_body_model.h"
 #include "vehicle_model.h"
 
@@ -379,6 +380,152 @@ int sfbx_meshfn_host(int kmin, int kmax, int n, int k, int nops, const int32_t *
     default: return -5;
     }
   });
+}
+
+// OCPNLP of a problem given as term tables (ocp_nlp_harness.h) on the script's mesh.  The harness carries one mesh type per
+// shape: dims (1, 0, 0, 0, 0) on Mesh<1, 2>, (2, 1, 1, 4, 6) on Mesh<3, 3>, (3, 2, 2, 1, 3) on Mesh<3, 6>, (3, 2, 1, 3, 2) on Mesh<13, 13>.
+int sfbx_ocp_nlp_host(int kmin, int kmax, int n, int k, int nops, const int32_t * ops, const int32_t * dims, const int32_t * nterms,
+                      const int32_t * terms, const double * coef, const double * crl, const double * cru, const double * cel, const double * ceu,
+                      const double * x, const double * lambda, int order, int numerical, int calls, int32_t * sizes, double * f, double * df, double * g,
+                      int32_t * rowptr, int32_t * colind, double * dg, int32_t * hcolptr, int32_t * hrowind, double * d2f, double * d2g, double * xl,
+                      double * xu, double * gl, double * gu, double * ws, double * x_back, double * lambda_back)
+{
+  sfbx::OcpData d{};
+  for (int q = 0, at = 0; q < 5; ++q) {
+    d.tab[q] = sfbx::TermTable{nterms[q], terms + 7 * at, coef + at};
+    at += nterms[q];
+  }
+  d.crl = crl, d.cru = cru, d.cel = cel, d.ceu = ceu;
+  const sfbx::OcpNlpOut o{f, df, g, dg, d2f, d2g, xl, xu, gl, gu, ws, x_back, lambda_back, rowptr, colind, hcolptr, hrowind, sizes};
+  using T = sf::diff::Type;
+  try {
+#define SFBX_NLP(KMIN, KMAX, NX, NU, NQ, NCR, NCE) \
+  if (kmin == KMIN && kmax == KMAX && dims[0] == NX && dims[1] == NU && dims[2] == NQ && dims[3] == NCR && dims[4] == NCE) { \
+    const auto mesh = run_script<sf::Mesh<KMIN, KMAX>>(n, k, nops, ops, nullptr); \
+    return numerical ? sfbx::ocp_nlp_run<NX, NU, NQ, NCR, NCE, T::Numerical>(mesh, d, x, lambda, order, calls, o) \
+                     : sfbx::ocp_nlp_run<NX, NU, NQ, NCR, NCE, T::Analytic>(mesh, d, x, lambda, order, calls, o); \
+  }
+    SFBX_NLP(1, 2, 1, 0, 0, 0, 0) SFBX_NLP(3, 3, 2, 1, 1, 4, 6) SFBX_NLP(3, 6, 3, 2, 2, 1, 3) SFBX_NLP(13, 13, 3, 2, 1, 3, 2)
+#undef SFBX_NLP
+  } catch (const std::exception & e) {
+    std::fprintf(stderr, "collocation harness: %s\n", e.what());
+    return -2;
+  }
+  return -1;  // no such (mesh type, dims)
+}
+
+// the scenario of the reference's tests/test_ocp_to_nlp.cpp as caller code against <smooth/feedback/ocp_to_nlp.hpp>: the
+// problem written as lambdas in an OCP<...>, random x and lambda, and df, dg, d2f, d2g against differences of f, g and
+// lambda' g at the reference's tolerances (1e-4 first, 1e-3 second derivatives, relative in the Frobenius norm as
+// isApprox is); returns 0, or the number of the first expectation that fails
+int sfbx_test_ocp_to_nlp_api(void)
+{
+  namespace F = smooth::feedback;
+  using X = F::Rn<2>;
+  using U = F::Rn<1>;
+  const auto theta = [](double tf, const X & x0, const X & xf, const F::Vec<1> & q) {
+    const double a = x0.v[0] * xf.v[0], b = x0.v[1] * xf.v[1];
+    return (tf - 2) * (tf - 2) + a * a + b * b + xf.v[0] * xf.v[0] + xf.v[1] * xf.v[1] + q[0];
+  };
+  const auto f  = [](double t, const X & x, const U & u) { return F::Vec<2>{x.v[1] + t, x.v[0] * u.v[0] * u.v[0]}; };
+  const auto g  = [](double t, const X & x, const U & u) { return F::Vec<1>{t + t * (x.v[0] * x.v[0] + x.v[1] * x.v[1]) + u.v[0] * u.v[0]}; };
+  const auto cr = [](double t, const X & x, const U & u) { return F::Vec<4>{t, t * x.v[0] * u.v[0], t * x.v[1] * u.v[0], u.v[0] * u.v[0]}; };
+  const auto ce = [](double tf, const X & x0, const X & xf, const F::Vec<1> & q) {
+    return F::Vec<6>{tf, x0.v[0] * xf.v[0], x0.v[1] * xf.v[1], xf.v[0], xf.v[1], q[0] * q[0]};
+  };
+  const F::Vec<4> crl{-1, -1, -1, -1}, cru{1, 1, 1, 1};
+  const F::Vec<6> cel{-1, -1, -1, -1, -1, -1}, ceu{1, 1, 1, 1, 1, 1};
+  const auto ocp = F::make_ocp<X, U>(theta, f, g, cr, crl, cru, ce, cel, ceu);
+  F::Mesh<3, 3> mesh;
+  mesh.refine_ph(0, 4);
+  mesh.refine_ph(0, 4);
+  auto nlp = F::ocp_to_nlp(ocp, mesh);
+  static_assert(F::HessianNLP<decltype(nlp)>);
+  const std::size_t n = nlp.n(), m = nlp.m();
+  if (n != 31 || m != 61) return 1;
+  std::vector<double> x(n), lambda(m);
+  uint64_t state = 5;
+  const auto draw = [&]() {
+    state = state * 6364136223846793005ull + 1442695040888963407ull;
+    return (double)(state >> 11) / 4503599627370496.0 - 1.0;  // [-1, 1)
+  };
+  for (double & v : x) v = draw();
+  for (double & v : lambda) v = draw();
+  // the same problem as tables with closed-form derivatives
+  static const int32_t terms[][7] = {
+    {0, 2, 1, 0, 0, 0, 0}, {0, 0, 1, 0, 0, 0, 0}, {1, 1, 1, 3, 2, 0, 0},                                                    // f
+    {0, 0, 1, 0, 0, 0, 0}, {0, 0, 1, 1, 2, 0, 0}, {0, 0, 1, 2, 2, 0, 0}, {0, 3, 2, 0, 0, 0, 0},                              // g
+    {0, 0, 1, 0, 0, 0, 0}, {1, 0, 1, 1, 1, 3, 1}, {2, 0, 1, 2, 1, 3, 1}, {3, 3, 2, 0, 0, 0, 0},                              // cr
+    {0, 0, 2, 0, 0, 0, 0}, {0, 0, 1, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0}, {0, 1, 2, 3, 2, 0, 0}, {0, 2, 2, 4, 2, 0, 0},
+    {0, 3, 2, 0, 0, 0, 0}, {0, 4, 2, 0, 0, 0, 0}, {0, 5, 1, 0, 0, 0, 0},                                                    // theta
+    {0, 0, 1, 0, 0, 0, 0}, {1, 1, 1, 3, 1, 0, 0}, {2, 2, 1, 4, 1, 0, 0}, {3, 3, 1, 0, 0, 0, 0}, {4, 4, 1, 0, 0, 0, 0}, {5, 5, 2, 0, 0, 0, 0}};  // ce
+  static const double coef[25] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, -4, 4, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
+  sfbx::TermOcp<2, 1, 1, 4, 6> tocp{};
+  tocp.f.tab = {3, terms[0], coef}, tocp.g.tab = {4, terms[3], coef + 3}, tocp.cr.tab = {4, terms[7], coef + 7};
+  tocp.theta.tab = {8, terms[11], coef + 11}, tocp.ce.tab = {6, terms[19], coef + 19};
+  tocp.crl = crl, tocp.cru = cru, tocp.cel = cel, tocp.ceu = ceu;
+  auto tnlp = F::ocp_to_nlp<F::diff::Type::Analytic>(tocp, mesh);
+  // the lambdas and the tables are one problem
+  if (std::fabs(nlp.f(x) - tnlp.f(x)) > 1e-12) return 2;
+  {
+    const std::vector<double> a = nlp.g(x), b = tnlp.g(x);
+    for (std::size_t i = 0; i < m; ++i)
+      if (std::fabs(a[i] - b[i]) > 1e-12) return 3;
+    if (nlp.gl() != tnlp.gl() || nlp.gu() != tnlp.gu() || nlp.xl() != tnlp.xl()) return 4;
+  }
+  // differences of f, g, lambda' g (central)
+  const auto lg = [&](auto & p, const std::vector<double> & xx) {
+    const std::vector<double> & gv = p.g(xx);
+    double s = 0;
+    for (std::size_t i = 0; i < m; ++i) s += lambda[i] * gv[i];
+    return s;
+  };
+  const auto approx = [](const std::vector<double> & a, const std::vector<double> & b, double tol) {
+    double d = 0, na = 0, nb = 0;
+    for (std::size_t i = 0; i < a.size(); ++i) d += (a[i] - b[i]) * (a[i] - b[i]), na += a[i] * a[i], nb += b[i] * b[i];
+    return std::sqrt(d) <= tol * std::sqrt(std::min(na, nb));
+  };
+  const double h1 = 1e-6, h2 = 1e-4;
+  std::vector<double> df_num(n), dg_num(m * n), d2f_num(n * n), d2g_num(n * n);
+  for (std::size_t c = 0; c < n; ++c) {
+    std::vector<double> xp = x, xm = x;
+    xp[c] += h1, xm[c] -= h1;
+    df_num[c] = (tnlp.f(xp) - tnlp.f(xm)) / (2 * h1);
+    const std::vector<double> gp = tnlp.g(xp), gm = tnlp.g(xm);
+    for (std::size_t r = 0; r < m; ++r) dg_num[r * n + c] = (gp[r] - gm[r]) / (2 * h1);
+    for (std::size_t b = c; b < n; ++b) {
+      std::vector<double> pp = x, pm = x, mp = x, mm = x;
+      pp[c] += h2, pp[b] += h2, pm[c] += h2, pm[b] -= h2, mp[c] -= h2, mp[b] += h2, mm[c] -= h2, mm[b] -= h2;
+      d2f_num[c * n + b] = d2f_num[b * n + c] = ((tnlp.f(pp) - tnlp.f(pm)) - (tnlp.f(mp) - tnlp.f(mm))) / (4 * h2 * h2);
+      d2g_num[c * n + b] = d2g_num[b * n + c] = ((lg(tnlp, pp) - lg(tnlp, pm)) - (lg(tnlp, mp) - lg(tnlp, mm))) / (4 * h2 * h2);
+    }
+  }
+  const auto dense_csr = [&](const F::MeshCsr & A) {
+    std::vector<double> out((std::size_t)A.rows * n, 0.0);
+    for (int r = 0; r < A.rows; ++r)
+      for (int p = A.rowptr[r]; p < A.rowptr[r + 1]; ++p) out[(std::size_t)r * n + A.colind[p]] = A.val[p];
+    return out;
+  };
+  const auto dense_sym = [&](const F::MeshCsc & H) {
+    std::vector<double> out(n * n, 0.0);
+    for (int c = 0; c < H.cols; ++c)
+      for (int p = H.colptr[c]; p < H.colptr[c + 1]; ++p) out[(std::size_t)H.rowind[p] * n + c] = out[(std::size_t)c * n + H.rowind[p]] = H.val[p];
+    return out;
+  };
+  int at = 5;
+  for (int pass = 0; pass < 2; ++pass) {  // the tables' closed forms, then the lambdas' differences
+    const auto run = [&](auto & p) {
+      if (!approx(dense_csr(p.df_dx(x)), df_num, 1e-4)) return 0;
+      if (!approx(dense_csr(p.dg_dx(x)), dg_num, 1e-4)) return 1;
+      if (!approx(dense_sym(p.d2f_dx2(x)), d2f_num, 1e-3)) return 2;
+      if (!approx(dense_sym(p.d2g_dx2(x, lambda)), d2g_num, 1e-3)) return 3;
+      return 4;
+    };
+    const int ok = pass == 0 ? run(tnlp) : run(nlp);
+    if (ok != 4) return at + ok;
+    at += 4;
+  }
+  return 0;
 }
 
 // the two trajectory scenarios of the reference's tests/test_collocation_mesh_function.cpp (:522-628) as caller code;

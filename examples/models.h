@@ -217,6 +217,20 @@ int sfbx_meshfn_host(int kmin, int kmax, int n, int k, int nops, const int32_t *
 /* the reference's two trajectory scenarios of mesh_function (tests/test_collocation_mesh_function.cpp:522-628) as caller code
  * against <smooth/feedback/collocation/mesh_function.hpp>: 0, or the number of the first expectation that fails */
 int sfbx_test_mesh_function_api(void);
+/* OCPNLP (include/smooth_feedback_amd/ocp_to_nlp.hpp) of a problem given as three-factor term tables (rows r, a, ka, b, kb,
+ * c, kc; nterms[5] and the rows of f, g, cr, theta, ce one after the other) on the script's mesh, at x and lambda, orders
+ * 0 .. order, `calls` times; then nlpsol_to_ocpsol and ocpsol_to_nlpsol there and back (x_back, lambda_back).  Out: sizes = n,
+ * m, nnz of dg, nnz of the Hessians, 1 when no output array moved between the calls; df dense; dg as CSR; d2f, d2g over one
+ * CSC pattern.  NULL outputs are skipped.  -1: the harness does not carry this (mesh type, dims). */
+int sfbx_ocp_nlp_host(int kmin, int kmax, int n, int k, int nops, const int32_t *ops, const int32_t *dims, const int32_t *nterms,
+                      const int32_t *terms, const double *coef, const double *crl, const double *cru, const double *cel,
+                      const double *ceu, const double *x, const double *lambda, int order, int numerical, int calls, int32_t *sizes,
+                      double *f, double *df, double *g, int32_t *rowptr, int32_t *colind, double *dg, int32_t *hcolptr,
+                      int32_t *hrowind, double *d2f, double *d2g, double *xl, double *xu, double *gl, double *gu, double *ws,
+                      double *x_back, double *lambda_back);
+/* the scenario of the reference's tests/test_ocp_to_nlp.cpp as caller code against <smooth/feedback/ocp_to_nlp.hpp>: 0, or the
+ * number of the first expectation that fails */
+int sfbx_test_ocp_to_nlp_api(void);
 
 #ifdef __cplusplus
 }

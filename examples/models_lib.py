@@ -639,3 +639,50 @@ def meshfn_host(spec, ops, opdata, fn, deriv, shape, terms, coef, t0, tf, xs, us
 
 def test_mesh_function_api():
     return lib().sfbx_test_mesh_function_api()
+
+
+def ocp_nlp_host(spec, ops, dims, tables, bounds, x, lam=None, order=1, numerical=False, calls=1):
+    """detail::OCPNLP of ocp_to_nlp.hpp on the script's mesh for a problem given as three-factor term tables (sfbx_ocp_nlp_host):
+    tables maps "terms.f" / "coef.f" (and g, cr, theta, ce) to (nterms, 7) rows and coefficients, bounds = (crl, cru, cel, ceu).
+    Orders 0 .. order at x (n,) and lam (m,), `calls` times.  Returns dict n, m, stable, f, g, xl, xu, gl, gu, w_scaling, x_back,
+    lambda_back (nlpsol_to_ocpsol, then ocpsol_to_nlpsol), with order >= 1 df (n,), rowptr, colind, dg, with order 2 hcolptr,
+    hrowind, d2f, d2g.  LookupError for a (mesh type, dims) the harness does not carry."""
+    args, keep = _script_args(spec, ops, None)
+    dims = np.ascontiguousarray(dims, dtype=np.int32)
+    nx, nu, nq, ncr, nce = [int(v) for v in dims]
+    names = ("f", "g", "cr", "theta", "ce")
+    nterms = np.array([len(tables["coef." + k]) for k in names], dtype=np.int32)
+    terms = np.ascontiguousarray(np.concatenate([np.asarray(tables["terms." + k], dtype=np.int32).reshape(-1, 7) for k in names]), dtype=np.int32)
+    coef = np.ascontiguousarray(np.concatenate([np.asarray(tables["coef." + k], dtype=np.float64) for k in names]))
+    crl, cru, cel, ceu = [np.ascontiguousarray(np.concatenate([np.asarray(b, dtype=np.float64).ravel(), [0.0]])) for b in bounds]
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    n = len(x)
+    N = (n - 1 - nq - nx) // (nx + nu)
+    m = nx * N + nq + ncr * N + nce
+    lam = np.ascontiguousarray(lam if lam is not None else np.zeros(m), dtype=np.float64)
+    nnz_cap = m * (2 + 14 + nx + nu) + nq * (nx + nu) * N + nce * (1 + nq + 2 * nx)
+    h_cap = n * (2 + nx + nu + nq + 2 * nx)
+    sizes = np.zeros(5, np.int32)
+    f, ws = np.zeros(1), np.zeros(1)
+    df, g, xl, xu, gl, gu, xb, lb = np.zeros(n), np.zeros(m), np.zeros(n), np.zeros(n), np.zeros(m), np.zeros(m), np.zeros(n), np.zeros(m)
+    rowptr, colind, dg = np.zeros(m + 1, np.int32), np.zeros(nnz_cap, np.int32), np.zeros(nnz_cap)
+    hcolptr, hrowind, d2f, d2g = np.zeros(n + 1, np.int32), np.zeros(h_cap, np.int32), np.zeros(h_cap), np.zeros(h_cap)
+    rc = lib().sfbx_ocp_nlp_host(*args[:6], _p(dims), _p(nterms), _p(terms), _p(coef), _p(crl), _p(cru), _p(cel), _p(ceu), _p(x), _p(lam), int(order),
+                                 1 if numerical else 0, int(calls), _p(sizes), _p(f), _p(df), _p(g), _p(rowptr), _p(colind), _p(dg), _p(hcolptr),
+                                 _p(hrowind), _p(d2f), _p(d2g), _p(xl), _p(xu), _p(gl), _p(gu), _p(ws), _p(xb), _p(lb))
+    if rc == -1:
+        raise LookupError("sfbx_ocp_nlp_host: %d" % rc)
+    assert rc == 0, rc
+    assert (int(sizes[0]), int(sizes[1])) == (n, m), (sizes, n, m)
+    nnz, hnnz = int(sizes[2]), int(sizes[3])
+    out = {"n": n, "m": m, "stable": bool(sizes[4]), "f": float(f[0]), "g": g, "xl": xl, "xu": xu, "gl": gl, "gu": gu, "w_scaling": float(ws[0]),
+           "x_back": xb, "lambda_back": lb}
+    if order >= 1:
+        out.update(df=df, rowptr=rowptr, colind=colind[:nnz].copy(), dg=dg[:nnz].copy())
+    if order >= 2:
+        out.update(hcolptr=hcolptr, hrowind=hrowind[:hnnz].copy(), d2f=d2f[:hnnz].copy(), d2g=d2g[:hnnz].copy())
+    return out
+
+
+def test_ocp_to_nlp_api():
+    return lib().sfbx_test_ocp_to_nlp_api()

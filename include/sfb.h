@@ -780,6 +780,49 @@ sfb_status sfb_mesh_dyn_batch_host(const sfb_mesh *mesh, int64_t batch, int32_t 
                                    const double *tf, const double *X, const double *F, const double *dF, double *out_F,
                                    double *out_dF_val);
 
+/* ------------------------------------------------------------------------------------------
+ * The collocation NLP of an optimal control problem over a mesh (include/smooth_feedback_amd/ocp_to_nlp.hpp:
+ * ocp_to_nlp; reference ocp_to_nlp.hpp).  t0 = 0.  Variables [tf | q (nq) | x_0 .. x_N | u_0 .. u_{N-1}],
+ * n = 1 + nq + nx (N + 1) + nu N; constraints [dyn nx N | integrals nq | running ncr N | end nce].  With
+ * ws = 1 / max(1e-6, max_i w_i):
+ *   g = [ws mesh_dyn.F | ws (mesh_integrate.F - q) | ws mesh_eval(cr, scaled by the weights).F | ce(tf, x_0, x_N, q)]
+ * and dg_dx comes as values dg_val [batch][nnz] over ONE CSR pattern per (mesh, dims), columns ascending, every
+ * reserved entry stored:
+ *   dyn row (node M_s + j, component d): tf, one entry per other node of the interval, the own nx-wide block, u_i;
+ *   integral r: tf, q_r (the value -ws), x_0 .. x_{N-1}, u_0 .. u_{N-1};   running (node i, r): tf, x_i, u_i;
+ *   end r: tf, q, x_0, x_N (unscaled).
+ * Model-free like the entries above: the model arrives at the N nodes (times tf tau_i) as F [batch][N][nf] and
+ * dF [batch][N][nf][1 + nx + nu] for f (nf = nx), g (nf = nq) and cr (nf = ncr), the end constraint as ce [batch][nce] and
+ * dce [batch][nce][1 + 2 nx + nq], columns (tf | x0 | xf | q).  x [batch][n] holds each agent's own tf, q, X, U.  One
+ * fused launch writes every output double once.  The four Jacobian inputs NULL together with dg_val NULL: values only.
+ * A segment of length zero takes NULL arrays.  nx >= 1, the other dims >= 0.
+ * Errors: the mesh, batch < 0, the dims, sizes beyond 32-bit indices, Jacobian inputs without dg_val or the reverse
+ * (or only some of the Jacobian inputs that have work), a NULL array with work to do; then SFB_ERR_NO_DEVICE for
+ * the compute entries.  batch == 0 writes nothing and returns SFB_OK with or without a device.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct sfb_ocp_dims {
+  int32_t nx, nu, nq, ncr, nce;
+} sfb_ocp_dims;
+/* var_beg: where tf, q, x, u start and n; con_beg: where the four constraint segments start and m.  Host only. */
+sfb_status sfb_ocp_nlp_structure(const sfb_mesh *mesh, const sfb_ocp_dims *dims, int64_t var_beg[5], int64_t con_beg[5]);
+/* rowptr [m + 1], colind [nnz].  Both arrays NULL: only *nnz is set.  Host only. */
+sfb_status sfb_ocp_nlp_pattern(const sfb_mesh *mesh, const sfb_ocp_dims *dims, int32_t *rowptr, int32_t *colind,
+                               int64_t *nnz);
+/* xl, xu [n]: -inf / +inf except tf >= 0; gl, gu [m]: zero for dyn and integrals, ws w_i crl / cru per node, cel / ceu.
+ * crl, cru [ncr], cel, ceu [nce].  Any output may be NULL.  Host only. */
+sfb_status sfb_ocp_nlp_bounds(const sfb_mesh *mesh, const sfb_ocp_dims *dims, const double *crl, const double *cru,
+                              const double *cel, const double *ceu, double *xl, double *xu, double *gl, double *gu,
+                              double *w_scaling);
+sfb_status sfb_ocp_nlp_batch(const sfb_mesh *mesh, const sfb_ocp_dims *dims, int64_t batch, const double *x,
+                             const double *Ff, const double *dFf, const double *Fg, const double *dFg, const double *Fcr,
+                             const double *dFcr, const double *ce, const double *dce, double *g, double *dg_val,
+                             void *stream);
+/* Host-pointer variant (stages through device memory, synchronous). */
+sfb_status sfb_ocp_nlp_batch_host(const sfb_mesh *mesh, const sfb_ocp_dims *dims, int64_t batch, const double *x,
+                                  const double *Ff, const double *dFf, const double *Fg, const double *dFg,
+                                  const double *Fcr, const double *dFcr, const double *ce, const double *dce, double *g,
+                                  double *dg_val);
+
 /*
  * Synthetic workload of the reference benchmark: random_qp(m, n, density, rng)
  * (benchmarks/bench_types.hpp:19-41) drawn `batch` times from ONE std::default_random_engine

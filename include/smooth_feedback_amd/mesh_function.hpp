@@ -200,6 +200,224 @@ inline void d2_pattern(int64_t N, int nx, int nu, MeshCsc & H)
   H.val.assign(H.rowind.size(), 0.0);
 }
 
+// ---- the collocation NLP of an OCP over a mesh (ocp_to_nlp.hpp; sfb_ocp_nlp_* of the C-ABI) ----
+// Variables [tf | q (nq) | x_0 .. x_N | u_0 .. u_{N-1}] (t0 = 0), constraints [dyn nx N | integrals nq | running ncr N | end nce].
+struct OcpDims {
+  int32_t nx, nu, nq, ncr, nce;
+};
+
+// what the NLP adds to the laws above: the mesh-weight scaling ws, ws (I - q), the -ws of the integral rows' q entry, and
+// the end constraint, which passes through unscaled
+SFB_LIE_HD inline double nlp_scaled(double ws, double v) { return ws * v; }
+SFB_LIE_HD inline double nlp_integral(double ws, double I, double q) { return ws * (I - q); }
+SFB_LIE_HD inline double nlp_minus_identity(double ws) { return -ws; }
+SFB_LIE_HD inline double nlp_end(double v) { return v; }
+
+/// var_beg (tf, q, x, u, n) and con_beg (dyn, integrals, running, end, m)
+inline void ocp_nlp_structure(int64_t N, const OcpDims & d, int64_t var_beg[5], int64_t con_beg[5])
+{
+  const int64_t vl[4] = {1, d.nq, (int64_t)d.nx * (N + 1), (int64_t)d.nu * N};
+  const int64_t cl[4] = {(int64_t)d.nx * N, d.nq, (int64_t)d.ncr * N, d.nce};
+  var_beg[0] = con_beg[0] = 0;
+  for (int k = 0; k < 4; ++k) var_beg[k + 1] = var_beg[k] + vl[k], con_beg[k + 1] = con_beg[k] + cl[k];
+}
+
+/// One output double of the NLP (a row of g, or an entry of dg_dx's pattern), decoded once per (mesh, dims): what it is,
+/// the node whose weight / time it uses, where its source double sits within one agent's input, and where its mesh
+/// coefficient sits in the table of differentiation matrices ((K + 1) x K per interval, one after the other).
+struct OcpNlpItem {
+  int32_t kind, node, src, aux;
+};
+enum OcpNlpKind : int32_t {
+  kNlpGDyn,     // g, dyn row: src = i nx + d (in Ff), aux = column j of D
+  kNlpGInt,     // g, integral r: src = r
+  kNlpGCr,      // g, running: src = i ncr + r (in Fcr)
+  kNlpGCe,      // g, end: src = r (in ce)
+  kNlpDynTf,    // src = i nx + d (Ff; the time derivative is dFf[src nz])
+  kNlpDynCoef,  // aux = D(k, j)
+  kNlpDynOwn,   // src in dFf, aux = D(j, j)
+  kNlpDynOwnDiag,
+  kNlpDynDu,    // src in dFf
+  kNlpIntTf,    // src = r: a sum over the nodes in node order
+  kNlpIntQ,
+  kNlpIntDz,    // src in dFg
+  kNlpCrTf,     // src = i ncr + r (the time derivative is dFcr[src nz])
+  kNlpCrDz,     // src in dFcr
+  kNlpCeD,      // src in dce
+};
+
+/// CSR pattern of dg_dx (columns ascending, every reserved entry stored) and, with `items`, the decode records: the m
+/// rows of g first, then the nnz entries.  NULL arrays: only the count is returned.
+///   dyn row (node M + j, d): tf | per node k of the interval its component d, the own node the whole block | u_i
+///   integral r: tf | q_r | x_0 .. x_{N-1} | u;   running (i, r): tf | x_i | u_i;   end r: tf | q | x_0 | x_N
+inline int64_t ocp_nlp_pattern(int nivals, const int32_t * K, const OcpDims & dm, int32_t * rowptr, int32_t * colind, OcpNlpItem * items)
+{
+  const int nx = dm.nx, nu = dm.nu, nq = dm.nq, ncr = dm.ncr, nce = dm.nce, nz = 1 + nx + nu, ne = 1 + 2 * nx + nq;
+  int64_t N = 0, nnz = 0;
+  for (int s = 0; s < nivals; ++s) N += K[s], nnz += (int64_t)K[s] * nx * (1 + K[s] + nx + nu);
+  nnz += (int64_t)nq * (2 + (int64_t)(nx + nu) * N) + (int64_t)ncr * N * (1 + nx + nu) + (int64_t)nce * (1 + nq + 2 * nx);
+  const bool pat = rowptr && colind;
+  if (!pat && !items) return nnz;
+  const int64_t qv = 1, xv = 1 + nq, uv = xv + (int64_t)nx * (N + 1), m = (int64_t)nx * N + nq + (int64_t)ncr * N + nce;
+  int64_t e = 0, row = 0;
+  OcpNlpItem * gi = items, * di = items ? items + m : nullptr;
+  const auto put = [&](int64_t col, int32_t kind, int64_t node, int64_t src, int64_t aux) {
+    if (pat) colind[e] = (int32_t)col;
+    if (di) di[e] = OcpNlpItem{kind, (int32_t)node, (int32_t)src, (int32_t)aux};
+    ++e;
+  };
+  const auto begin_row = [&](int32_t kind, int64_t node, int64_t src, int64_t aux) {
+    if (pat) rowptr[row] = (int32_t)e;
+    if (gi) gi[row] = OcpNlpItem{kind, (int32_t)node, (int32_t)src, (int32_t)aux};
+    ++row;
+  };
+  int64_t M = 0, Doff = 0;
+  for (int s = 0; s < nivals; ++s) {
+    const int Ks = K[s];
+    for (int j = 0; j < Ks; ++j)
+      for (int d = 0; d < nx; ++d) {
+        const int64_t i = M + j, fr = i * nx + d, Dcol = Doff + (int64_t)j * (Ks + 1);
+        begin_row(kNlpGDyn, i, fr, Dcol);
+        put(0, kNlpDynTf, i, fr, 0);
+        for (int k = 0; k <= Ks; ++k) {
+          if (k != j) put(xv + (M + k) * nx + d, kNlpDynCoef, i, 0, Dcol + k);
+          else
+            for (int c = 0; c < nx; ++c) put(xv + i * nx + c, c == d ? kNlpDynOwnDiag : kNlpDynOwn, i, fr * nz + 1 + c, Dcol + j);
+        }
+        for (int c = 0; c < nu; ++c) put(uv + i * nu + c, kNlpDynDu, i, fr * nz + 1 + nx + c, 0);
+      }
+    M += Ks;
+    Doff += (int64_t)(Ks + 1) * Ks;
+  }
+  for (int r = 0; r < nq; ++r) {
+    begin_row(kNlpGInt, 0, r, 0);
+    put(0, kNlpIntTf, 0, r, 0);
+    put(qv + r, kNlpIntQ, 0, 0, 0);
+    for (int64_t i = 0; i < N; ++i)
+      for (int c = 0; c < nx; ++c) put(xv + i * nx + c, kNlpIntDz, i, (i * nq + r) * nz + 1 + c, 0);
+    for (int64_t i = 0; i < N; ++i)
+      for (int c = 0; c < nu; ++c) put(uv + i * nu + c, kNlpIntDz, i, (i * nq + r) * nz + 1 + nx + c, 0);
+  }
+  for (int64_t i = 0; i < N; ++i)
+    for (int r = 0; r < ncr; ++r) {
+      const int64_t fr = i * ncr + r;
+      begin_row(kNlpGCr, i, fr, 0);
+      put(0, kNlpCrTf, i, fr, 0);
+      for (int c = 0; c < nx; ++c) put(xv + i * nx + c, kNlpCrDz, i, fr * nz + 1 + c, 0);
+      for (int c = 0; c < nu; ++c) put(uv + i * nu + c, kNlpCrDz, i, fr * nz + 1 + nx + c, 0);
+    }
+  for (int r = 0; r < nce; ++r) {  // dce's columns are (tf | x0 | xf | q)
+    begin_row(kNlpGCe, 0, r, 0);
+    put(0, kNlpCeD, 0, (int64_t)r * ne, 0);
+    for (int c = 0; c < nq; ++c) put(qv + c, kNlpCeD, 0, (int64_t)r * ne + 1 + 2 * nx + c, 0);
+    for (int c = 0; c < nx; ++c) put(xv + c, kNlpCeD, 0, (int64_t)r * ne + 1 + c, 0);
+    for (int c = 0; c < nx; ++c) put(xv + N * nx + c, kNlpCeD, 0, (int64_t)r * ne + 1 + nx + c, 0);
+  }
+  if (pat) rowptr[row] = (int32_t)e;
+  return nnz;
+}
+
+/// per node: its time on [0, 1], quadrature weight, and its interval's 2 / length, point count and first node
+struct OcpNlpNode {
+  double tau, w, alpha;
+  int32_t K, M;
+};
+/// what every agent of one (mesh, dims) shares
+struct OcpNlpTables {
+  OcpDims d;
+  int32_t N;
+  int64_t m, nnz;
+  double ws;
+  const OcpNlpNode * nodes;  // [N]
+  const double * D;          // the unscaled differentiation matrices, D(k, j) of an interval at [k + j (K + 1)]
+  const OcpNlpItem * items;  // [m + nnz]
+};
+/// one agent's arrays: x [n]; the model at the N nodes, F [N][nf] and dF [N][nf][1 + nx + nu] for f, g, cr; ce [nce], dce [nce][1 + 2 nx + nq]
+struct OcpNlpAgent {
+  const double *x, *Ff, *dFf, *Fg, *dFg, *Fcr, *dFcr, *ce, *dce;
+};
+/// an item with everything that does not depend on the agent looked up
+struct OcpNlpLane {
+  int32_t kind, src, K, xoff;  // xoff: component d of x_M within x (kNlpGDyn)
+  double tau, w, alpha, Dv;
+  const double * Dcol;
+};
+SFB_LIE_HD inline double ocp_nlp_w_scaling(double max_weight) { return 1. / (max_weight > 1e-6 ? max_weight : 1e-6); }
+
+SFB_LIE_HD inline OcpNlpLane ocp_nlp_decode(const OcpNlpTables & T, const OcpNlpItem it)
+{
+  const OcpNlpNode nd = T.N > 0 ? T.nodes[it.node] : OcpNlpNode{};
+  OcpNlpLane L{it.kind, it.src, nd.K, 0, nd.tau, nd.w, nd.alpha, 0.0, T.D + it.aux};
+  if (it.kind == kNlpGDyn) L.xoff = 1 + T.d.nq + nd.M * T.d.nx + it.src % T.d.nx;
+  if (it.kind == kNlpDynCoef || it.kind == kNlpDynOwn || it.kind == kNlpDynOwnDiag) L.Dv = T.D[it.aux];
+  return L;
+}
+
+/// the value of one item for one agent: the laws above, then the multiplication by ws.  t0 = 0, so h = tf.
+SFB_LIE_HD inline double ocp_nlp_value(const OcpNlpTables & T, const OcpNlpLane & L, const OcpNlpAgent & a)
+{
+  const int nx = T.d.nx, nq = T.d.nq, nz = 1 + nx + T.d.nu;
+  const double ws = T.ws, tf = a.x[0], h = tf - 0.0;
+  switch (L.kind) {
+  case kNlpGDyn: return nlp_scaled(ws, dyn_F(L.K, L.w, h, L.alpha, L.Dcol, a.Ff[L.src], a.x + L.xoff, nx));
+  case kNlpGInt: {
+    double acc = 0.0;
+    for (int i = 0; i < T.N; ++i) integrate_F_add(acc, T.nodes[i].w, h, a.Fg[(int64_t)i * nq + L.src]);
+    return nlp_integral(ws, acc, a.x[1 + L.src]);
+  }
+  case kNlpGCr: return nlp_scaled(ws, eval_F(L.w, a.Fcr[L.src]));
+  case kNlpGCe: return nlp_end(a.ce[L.src]);
+  case kNlpDynTf: return nlp_scaled(ws, dyn_dtf(L.w, h, L.tau, a.Ff[L.src], a.dFf[(int64_t)L.src * nz]));
+  case kNlpDynCoef: return nlp_scaled(ws, dyn_coef(L.w, L.alpha, L.Dv));
+  case kNlpDynOwn: return nlp_scaled(ws, dyn_own(L.w, h, L.alpha, L.Dv, a.dFf[L.src], false));
+  case kNlpDynOwnDiag: return nlp_scaled(ws, dyn_own(L.w, h, L.alpha, L.Dv, a.dFf[L.src], true));
+  case kNlpDynDu: return nlp_scaled(ws, dyn_du(L.w, h, a.dFf[L.src]));
+  case kNlpIntTf: {
+    double acc = 0.0;
+    for (int i = 0; i < T.N; ++i) {
+      const int64_t fr = (int64_t)i * nq + L.src;
+      integrate_dtf_add(acc, T.nodes[i].w, h, T.nodes[i].tau, a.Fg[fr], a.dFg[fr * nz]);
+    }
+    return nlp_scaled(ws, acc);
+  }
+  case kNlpIntQ: return nlp_minus_identity(ws);
+  case kNlpIntDz: return nlp_scaled(ws, integrate_dz(L.w, h, a.dFg[L.src]));
+  case kNlpCrTf: return nlp_scaled(ws, eval_dtf(L.w, L.tau, a.dFcr[(int64_t)L.src * nz]));
+  case kNlpCrDz: return nlp_scaled(ws, eval_dz(L.w, a.dFcr[L.src]));
+  default: return nlp_end(a.dce[L.src]);
+  }
+}
+
+/// one agent on the host: g [m] and, with dg, the CSR values [nnz] (the loop the fused kernel spreads over lanes)
+inline void ocp_nlp_assemble(const OcpNlpTables & T, const OcpNlpAgent & a, double * g, double * dg)
+{
+  for (int64_t it = 0; it < T.m; ++it) g[it] = ocp_nlp_value(T, ocp_nlp_decode(T, T.items[it]), a);
+  if (dg)
+    for (int64_t e = 0; e < T.nnz; ++e) dg[e] = ocp_nlp_value(T, ocp_nlp_decode(T, T.items[T.m + e]), a);
+}
+
+/// xl, xu [n]: free except tf >= 0; gl, gu [m]: zero for dyn and integrals, ws w_i crl / cru per node, cel / ceu.  NULL outputs are skipped.
+inline void ocp_nlp_bounds(const OcpDims & d, int64_t N, const OcpNlpNode * nodes, double ws, const double * crl, const double * cru,
+                           const double * cel, const double * ceu, double * xl, double * xu, double * gl, double * gu)
+{
+  int64_t vb[5], cb[5];
+  ocp_nlp_structure(N, d, vb, cb);
+  const double inf = std::numeric_limits<double>::infinity();
+  for (int64_t k = 0; k < vb[4]; ++k) {
+    if (xl) xl[k] = k == 0 ? 0.0 : -inf;
+    if (xu) xu[k] = inf;
+  }
+  for (int side = 0; side < 2; ++side) {
+    double * out = side ? gu : gl;
+    const double *cr = side ? cru : crl, *ce = side ? ceu : cel;
+    if (!out) continue;
+    for (int64_t k = 0; k < cb[2]; ++k) out[k] = 0.0;
+    for (int64_t i = 0; i < N; ++i)
+      for (int r = 0; r < d.ncr; ++r) out[cb[2] + i * d.ncr + r] = (ws * nodes[i].w) * cr[r];
+    for (int r = 0; r < d.nce; ++r) out[cb[3] + r] = ce[r];
+  }
+}
+
 }  // namespace meshfn
 
 namespace detail {

@@ -64,6 +64,12 @@ class SfbMesh(C.Structure):
     _fields_ = [("nivals", C.c_int32), ("K", C.c_void_p), ("tau0", C.c_void_p)]
 
 
+class SfbOcpDims(C.Structure):
+    """sfb_ocp_dims (include/sfb.h)."""
+
+    _fields_ = [("nx", C.c_int32), ("nu", C.c_int32), ("nq", C.c_int32), ("ncr", C.c_int32), ("nce", C.c_int32)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -156,6 +162,12 @@ def _load():
     L.sfb_mesh_integrate_batch.argtypes = L.sfb_mesh_integrate_batch_host.argtypes + [vp]
     L.sfb_mesh_dyn_batch_host.argtypes = [mesh, i64, i32, i32] + [dp] * 7
     L.sfb_mesh_dyn_batch.argtypes = L.sfb_mesh_dyn_batch_host.argtypes + [vp]
+    dims = C.POINTER(SfbOcpDims)
+    L.sfb_ocp_nlp_structure.argtypes = [mesh, dims, vp, vp]
+    L.sfb_ocp_nlp_pattern.argtypes = [mesh, dims, vp, vp, C.POINTER(C.c_int64)]
+    L.sfb_ocp_nlp_bounds.argtypes = [mesh, dims] + [dp] * 8 + [C.POINTER(C.c_double)]
+    L.sfb_ocp_nlp_batch_host.argtypes = [mesh, dims, i64] + [dp] * 11
+    L.sfb_ocp_nlp_batch.argtypes = L.sfb_ocp_nlp_batch_host.argtypes + [vp]
     lay = C.POINTER(SfbMPCLayout)
     L.sfb_mpc_record_doubles.argtypes = [lay, i32]
     L.sfb_mpc_record_doubles.restype = i64

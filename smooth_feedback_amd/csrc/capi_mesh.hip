@@ -1,7 +1,9 @@
 // C-ABI for the batched ph-mesh path (include/sfb.h): resampling onto the degree-raised mesh, dynamics-error estimate,
-// and the functions over the mesh (eval, integrate, dyn) with first derivatives and their sparsity patterns.
+// the functions over the mesh (eval, integrate, dyn) with first derivatives and their sparsity patterns, and the
+// collocation NLP of an OCP over the mesh (structure, pattern, bounds, fused batched g / dg_dx).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -88,11 +90,26 @@ struct MeshFnEntry {
   sfb::DeviceBlock blk;
   sfb::MeshFnDevice dev;
 };
+// what the fused NLP kernel reads, per (mesh, dims): the node table, the differentiation matrices and one decode record
+// per output double; kept and dropped by the same rule
+struct OcpNlpKey {
+  MeshKey mesh;
+  int32_t d[5];
+  bool operator<(const OcpNlpKey &o) const
+  {
+    return std::lexicographical_compare(d, d + 5, o.d, o.d + 5) || (std::equal(d, d + 5, o.d) && mesh < o.mesh);
+  }
+};
+struct OcpNlpEntry {
+  sfb::DeviceBlock blk;
+  L::meshfn::OcpNlpTables dev;
+};
 struct MeshCache {
   std::mutex mu;
   std::map<int, sfb::DeviceBlock> tables;
   std::map<MeshKey, MeshEntry> meshes;
   std::map<MeshFnKey, MeshFnEntry> fns;
+  std::map<OcpNlpKey, OcpNlpEntry> nlps;
 };
 MeshCache &cache()
 {
@@ -236,6 +253,109 @@ sfb_status with_device_meshfn(const sfb_mesh *mesh, int32_t nx, int32_t nu, Laun
   return launch(it->second.dev);
 }
 
+// nodes, weights, interval constants and differentiation matrices of a mesh as the NLP law reads them (the expressions
+// of Mesh::interval_nodes / interval_weights / interval_diffmat_unscaled); returns ws
+double ocp_nlp_host_tables(const sfb_mesh *mesh, std::vector<L::meshfn::OcpNlpNode> &nodes, std::vector<double> &D)
+{
+  const int32_t n = mesh->nivals;
+  int32_t N = 0;
+  double wmax = 0.0;
+  for (int32_t s = 0; s < n; ++s) {
+    const L::detail::LgrTable &T = L::detail::lgr_table(mesh->K[s]);
+    const double tau0 = mesh->tau0[s], tauf = s + 1 < n ? mesh->tau0[s + 1] : 1.0, al = (tauf - tau0) / 2;
+    for (int32_t j = 0; j < mesh->K[s]; ++j) {
+      nodes.push_back(L::meshfn::OcpNlpNode{tau0 + al * (T.tau[j] + 1), al * T.w[j], 2. / (tauf - tau0), mesh->K[s], N});
+      wmax = std::max(wmax, nodes.back().w);
+    }
+    D.insert(D.end(), T.Dus.a.begin(), T.Dus.a.end());
+    N += mesh->K[s];
+  }
+  return L::meshfn::ocp_nlp_w_scaling(wmax);
+}
+
+L::meshfn::OcpDims to_dims(const sfb_ocp_dims *d) { return L::meshfn::OcpDims{d->nx, d->nu, d->nq, d->ncr, d->nce}; }
+
+// what every sfb_ocp_nlp_* entry refuses first: the mesh, the batch, the dims, sizes beyond 32-bit indices
+sfb_status ocp_dims_check(const sfb_mesh *mesh, int64_t batch, const sfb_ocp_dims *d)
+{
+  const sfb_status st = mesh_check(mesh, batch);
+  if (st != SFB_OK) return st;
+  if (!d) return sfb::fail(SFB_ERR_INVALID_ARG, "NULL dims");
+  if (d->nx < 1) return sfb::fail(SFB_ERR_INVALID_ARG, "dims: nx < 1");
+  if (d->nu < 0 || d->nq < 0 || d->ncr < 0 || d->nce < 0) return sfb::fail(SFB_ERR_INVALID_ARG, "dims: nu, nq, ncr or nce < 0");
+  const int64_t N = mesh_nodes(mesh), nz = 1 + (int64_t)d->nx + d->nu;
+  int64_t vb[5], cb[5];
+  L::meshfn::ocp_nlp_structure(N, to_dims(d), vb, cb);
+  const int64_t widest = std::max<int64_t>({d->nx, d->nq, d->ncr});
+  const int64_t row_max = std::max<int64_t>({2 + sfb::kMeshMaxK + nz, 2 + (nz - 1) * N, 1 + (int64_t)d->nq + 2 * (int64_t)d->nx});
+  if (vb[4] > 0x7fffffff || cb[4] > 0x7fffffff || cb[4] * row_max > 0x7fffffff || N * widest * nz > 0x7fffffff ||
+      (int64_t)d->nce * (1 + 2 * (int64_t)d->nx + d->nq) > 0x7fffffff)
+    return sfb::fail(SFB_ERR_INVALID_ARG, "ocp nlp: more variables, constraints or entries than 32-bit indices hold");
+  return SFB_OK;
+}
+
+sfb_status ocp_nlp_check(const sfb_mesh *mesh, const sfb_ocp_dims *d, int64_t batch, const double *x, const double *Ff, const double *dFf,
+                         const double *Fg, const double *dFg, const double *Fcr, const double *dFcr, const double *ce, const double *dce,
+                         double *g, double *dg_val)
+{
+  const sfb_status st = ocp_dims_check(mesh, batch, d);
+  if (st != SFB_OK) return st;
+  const bool want = dg_val != nullptr;
+  if ((dFf != nullptr) != want || (d->nq > 0 && (dFg != nullptr) != want) || (d->ncr > 0 && (dFcr != nullptr) != want) ||
+      (d->nce > 0 && (dce != nullptr) != want))
+    return sfb::fail(SFB_ERR_INVALID_ARG, "the Jacobian inputs and dg_val: all or none");
+  if (batch > 0 && (!x || !Ff || !g || (d->nq > 0 && !Fg) || (d->ncr > 0 && !Fcr) || (d->nce > 0 && !ce)))
+    return sfb::fail(SFB_ERR_INVALID_ARG, "NULL array");
+  return SFB_OK;
+}
+
+// launch(T) with the device tables of (mesh, dims), under the cache's lock
+template<class Launch>
+sfb_status with_device_ocpnlp(const sfb_mesh *mesh, const sfb_ocp_dims *d, Launch &&launch)
+{
+  namespace MF = L::meshfn;
+  int device = 0;
+  hipError_t e = hipGetDevice(&device);
+  if (e != hipSuccess) return sfb::hip_fail(e, "hipGetDevice");
+  MeshCache &c = cache();
+  std::lock_guard<std::mutex> lock(c.mu);
+  OcpNlpKey key{MeshKey{device, std::vector<int32_t>(mesh->K, mesh->K + mesh->nivals), std::vector<uint64_t>(mesh->nivals)},
+                {d->nx, d->nu, d->nq, d->ncr, d->nce}};
+  std::memcpy(key.mesh.tau0.data(), mesh->tau0, sizeof(double) * mesh->nivals);
+  auto it = c.nlps.find(key);
+  if (it == c.nlps.end()) {
+    size_t here = 0;
+    for (const auto &m : c.nlps) here += m.first.mesh.device == device ? 1 : 0;
+    if (here >= kMeshesKept) {
+      if ((e = hipDeviceSynchronize()) != hipSuccess) return sfb::hip_fail(e, "hipDeviceSynchronize");
+      for (auto m = c.nlps.begin(); m != c.nlps.end();) m = m->first.mesh.device == device ? c.nlps.erase(m) : std::next(m);
+    }
+    std::vector<MF::OcpNlpNode> nodes;
+    std::vector<double> D;
+    const double ws    = ocp_nlp_host_tables(mesh, nodes, D);
+    const MF::OcpDims dm = to_dims(d);
+    int64_t vb[5], cb[5];
+    MF::ocp_nlp_structure((int64_t)nodes.size(), dm, vb, cb);
+    const int64_t nnz = MF::ocp_nlp_pattern(mesh->nivals, mesh->K, dm, nullptr, nullptr, nullptr);
+    std::vector<MF::OcpNlpItem> items((size_t)(cb[4] + nnz));
+    MF::ocp_nlp_pattern(mesh->nivals, mesh->K, dm, nullptr, nullptr, items.data());
+    sfb::Staging st;
+    MF::OcpNlpNode *dn;
+    double *dD;
+    MF::OcpNlpItem *di;
+    st.add(&dn, nodes.size(), sfb::Staging::In, nodes.data());
+    st.add(&dD, D.size(), sfb::Staging::In, D.data());
+    st.add(&di, items.size(), sfb::Staging::In, items.data());
+    OcpNlpEntry ent;
+    const sfb_status rc = sfb::stage_per_call(st, ent.blk);
+    if (rc != SFB_OK) return rc;
+    if ((e = st.upload()) != hipSuccess) return sfb::hip_fail(e, "ocp nlp tables upload");
+    ent.dev = MF::OcpNlpTables{dm, (int32_t)nodes.size(), cb[4], nnz, ws, dn, dD, di};
+    it      = c.nlps.emplace(std::move(key), std::move(ent)).first;
+  }
+  return launch(it->second.dev);
+}
+
 // what the three mesh-function entries refuse, in this order: the mesh, the batch, negative sizes, an index range the
 // 32-bit patterns cannot hold, a derivative input without its output (or the reverse), a NULL array with work to do
 sfb_status meshfn_check(const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, int32_t nf, const double *t0, const double *tf, bool needs_X,
@@ -372,6 +492,102 @@ sfb_status sfb_mesh_dyn_batch_host(const sfb_mesh *mesh, int64_t batch, int32_t 
                                    const double *F, const double *dF, double *out_F, double *out_dF_val)
 {
   return meshfn_host(kDyn, mesh, batch, nx, nu, nx, 0, t0, tf, X, F, dF, out_F, out_dF_val);
+}
+
+sfb_status sfb_ocp_nlp_structure(const sfb_mesh *mesh, const sfb_ocp_dims *dims, int64_t var_beg[5], int64_t con_beg[5])
+{
+  const sfb_status st = ocp_dims_check(mesh, 0, dims);
+  if (st != SFB_OK) return st;
+  if (!var_beg || !con_beg) return sfb::fail(SFB_ERR_INVALID_ARG, "NULL array");
+  L::meshfn::ocp_nlp_structure(mesh_nodes(mesh), to_dims(dims), var_beg, con_beg);
+  return SFB_OK;
+}
+
+sfb_status sfb_ocp_nlp_pattern(const sfb_mesh *mesh, const sfb_ocp_dims *dims, int32_t *rowptr, int32_t *colind, int64_t *nnz)
+{
+  const sfb_status st = ocp_dims_check(mesh, 0, dims);
+  if (st != SFB_OK) return st;
+  if ((rowptr == nullptr) != (colind == nullptr)) return sfb::fail(SFB_ERR_INVALID_ARG, "rowptr and colind: both or neither");
+  if (!rowptr && !nnz) return sfb::fail(SFB_ERR_INVALID_ARG, "NULL array");
+  const int64_t n = L::meshfn::ocp_nlp_pattern(mesh->nivals, mesh->K, to_dims(dims), rowptr, colind, nullptr);
+  if (nnz) *nnz = n;
+  return SFB_OK;
+}
+
+sfb_status sfb_ocp_nlp_bounds(const sfb_mesh *mesh, const sfb_ocp_dims *dims, const double *crl, const double *cru, const double *cel,
+                              const double *ceu, double *xl, double *xu, double *gl, double *gu, double *w_scaling)
+{
+  const sfb_status st = ocp_dims_check(mesh, 0, dims);
+  if (st != SFB_OK) return st;
+  if (((gl || gu) && ((dims->ncr > 0 && (!crl || !cru)) || (dims->nce > 0 && (!cel || !ceu)))))
+    return sfb::fail(SFB_ERR_INVALID_ARG, "NULL array");
+  std::vector<L::meshfn::OcpNlpNode> nodes;
+  std::vector<double> D;
+  const double ws = ocp_nlp_host_tables(mesh, nodes, D);
+  int64_t vb[5], cb[5];
+  L::meshfn::ocp_nlp_structure((int64_t)nodes.size(), to_dims(dims), vb, cb);
+  if (w_scaling) *w_scaling = ws;
+  L::meshfn::ocp_nlp_bounds(to_dims(dims), (int64_t)nodes.size(), nodes.data(), ws, crl, cru, cel, ceu, xl, xu, gl, gu);
+  return SFB_OK;
+}
+
+sfb_status sfb_ocp_nlp_batch(const sfb_mesh *mesh, const sfb_ocp_dims *dims, int64_t batch, const double *x, const double *Ff, const double *dFf,
+                             const double *Fg, const double *dFg, const double *Fcr, const double *dFcr, const double *ce, const double *dce,
+                             double *g, double *dg_val, void *stream)
+{
+  sfb_status st = ocp_nlp_check(mesh, dims, batch, x, Ff, dFf, Fg, dFg, Fcr, dFcr, ce, dce, g, dg_val);
+  if (st != SFB_OK) return st;
+  if (batch == 0) return SFB_OK;  // nothing to write: no device is asked for
+  st = sfb::require_device();
+  if (st != SFB_OK) return st;
+  return with_device_ocpnlp(mesh, dims, [&](const L::meshfn::OcpNlpTables &T) {
+    int64_t vb[5], cb[5];
+    L::meshfn::ocp_nlp_structure(T.N, T.d, vb, cb);
+    sfb::OcpNlpArgs a{};
+    a.T = T; a.batch = batch; a.n = vb[4]; a.x = x; a.Ff = Ff; a.dFf = dFf; a.Fg = Fg; a.dFg = dFg; a.Fcr = Fcr; a.dFcr = dFcr; a.ce = ce; a.dce = dce;
+    a.g = g; a.dg = dg_val;
+    const hipError_t e = sfb::ocp_nlp_launch(a, static_cast<hipStream_t>(stream));
+    return e != hipSuccess ? sfb::hip_fail(e, "ocp_nlp_kernel launch") : SFB_OK;
+  });
+}
+
+sfb_status sfb_ocp_nlp_batch_host(const sfb_mesh *mesh, const sfb_ocp_dims *dims, int64_t batch, const double *x, const double *Ff, const double *dFf,
+                                  const double *Fg, const double *dFg, const double *Fcr, const double *dFcr, const double *ce, const double *dce,
+                                  double *g, double *dg_val)
+{
+  sfb_status st = ocp_nlp_check(mesh, dims, batch, x, Ff, dFf, Fg, dFg, Fcr, dFcr, ce, dce, g, dg_val);
+  if (st != SFB_OK) return st;
+  if (batch == 0) return SFB_OK;  // nothing to write: no device is asked for
+  st = sfb::require_device();
+  if (st != SFB_OK) return st;
+  const size_t B = (size_t)batch, N = (size_t)mesh_nodes(mesh), nx = (size_t)dims->nx, nq = (size_t)dims->nq, ncr = (size_t)dims->ncr,
+               nce = (size_t)dims->nce, nz = 1 + nx + (size_t)dims->nu, ne = 1 + 2 * nx + nq;
+  int64_t vb[5], cb[5];
+  L::meshfn::ocp_nlp_structure((int64_t)N, to_dims(dims), vb, cb);
+  const size_t nnz = (size_t)L::meshfn::ocp_nlp_pattern(mesh->nivals, mesh->K, to_dims(dims), nullptr, nullptr, nullptr);
+  using S = sfb::Staging;
+  S s;
+  double *dx, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr, *d4 = nullptr, *d5 = nullptr, *d6 = nullptr, *d7 = nullptr, *d8 = nullptr, *dg, *ddg = nullptr;
+  s.add(&dx, B * (size_t)vb[4], S::In, x);
+  s.add(&d1, B * N * nx, S::In, Ff);
+  if (dg_val) s.add(&d2, B * N * nx * nz, S::In, dFf);
+  if (nq) s.add(&d3, B * N * nq, S::In, Fg);
+  if (nq && dg_val) s.add(&d4, B * N * nq * nz, S::In, dFg);
+  if (ncr) s.add(&d5, B * N * ncr, S::In, Fcr);
+  if (ncr && dg_val) s.add(&d6, B * N * ncr * nz, S::In, dFcr);
+  if (nce) s.add(&d7, B * nce, S::In, ce);
+  if (nce && dg_val) s.add(&d8, B * nce * ne, S::In, dce);
+  s.add(&dg, B * (size_t)cb[4], S::Out, g);
+  if (dg_val) s.add(&ddg, B * nnz, S::Out, dg_val);
+  sfb::DeviceBlock blk;
+  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
+  hipError_t e = s.upload();
+  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_ocp_nlp_batch_host upload");
+  st = sfb_ocp_nlp_batch(mesh, dims, batch, dx, d1, d2, d3, d4, d5, d6, d7, d8, dg, ddg, nullptr);
+  if (st != SFB_OK) return st;
+  if ((e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
+  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_ocp_nlp_batch_host");
+  return SFB_OK;
 }
 
 sfb_status sfb_mesh_resample_batch(const sfb_mesh *mesh, int64_t batch, int32_t dim, int extend, const double *vals, double *out, void *stream)

@@ -20,7 +20,18 @@
 // dyn_entry_row (4 bytes per entry, shared by every agent: cache resident) and row -> position through dyn_rowptr, and
 // read the row's own block of dF contiguously.  mesh_integrate's t0, tf and F lanes loop over the nodes in node order
 // (the host's order of summation); its x and u lanes do one product.  No LDS, plain loads and stores.
+//
+// ocp_nlp (include/sfb.h: sfb_ocp_nlp_batch): g and the CSR values of dg_dx of the collocation NLP in one launch, every
+// output double written once and no t0 entry computed.  The outputs of one agent are m + nnz items (the rows of g, then
+// the entries of the pattern); the host builds one 16-byte decode record per item, once per (mesh, dims).  A lane takes
+// one item, decodes it once (record -> node table -> mesh coefficient) and then walks kNlpAgents agents with it; the
+// lanes of a wave hold consecutive items, so every store instruction of a wave writes 512 contiguous bytes of one
+// agent.  Every value is meshfn::ocp_nlp_value, the function the host front calls.
 #include "mesh_kernel.h"
+
+#include <cstdlib>
+
+#include "knobs.h"
 
 #include "../../include/smooth_feedback_amd/dyn_error.hpp"
 #include "../../include/smooth_feedback_amd/mesh_function.hpp"
@@ -226,6 +237,29 @@ __global__ void __launch_bounds__(256) mesh_dyn_dF_kernel(const MeshFnArgs a)
   a.out_dF[t] = v;
 }
 
+constexpr int kNlpAgents = 8;  // agents a lane walks with one decoded item (the knob SFB_NLP_AGENTS overrides it for A/B runs)
+
+__global__ void __launch_bounds__(256) ocp_nlp_kernel(const OcpNlpArgs a)
+{
+  const MF::OcpNlpTables &T = a.T;
+  const int64_t m = T.m, items = a.dg ? m + T.nnz : m;
+  const int64_t b0 = (int64_t)blockIdx.x * a.agents;
+  const int64_t b1 = b0 + a.agents < a.batch ? b0 + a.agents : a.batch;
+  const int64_t N = T.N, nz = 1 + T.d.nx + T.d.nu;
+  const int64_t sFf = N * T.d.nx, sFg = N * T.d.nq, sFcr = N * T.d.ncr, sdce = (int64_t)T.d.nce * (1 + 2 * T.d.nx + T.d.nq);
+  for (int64_t it = (int64_t)blockIdx.y * 256 + threadIdx.x; it < items; it += (int64_t)gridDim.y * 256) {
+    const MF::OcpNlpLane L = MF::ocp_nlp_decode(T, T.items[it]);
+    const bool row = it < m;
+    double *out    = row ? a.g + b0 * m + it : a.dg + b0 * T.nnz + (it - m);
+    const int64_t so = row ? m : T.nnz;
+    for (int64_t b = b0; b < b1; ++b, out += so) {
+      const MF::OcpNlpAgent ag{a.x + b * a.n, a.Ff + b * sFf, a.dFf + b * sFf * nz, a.Fg + b * sFg, a.dFg + b * sFg * nz,
+                               a.Fcr + b * sFcr, a.dFcr + b * sFcr * nz, a.ce + b * T.d.nce, a.dce + b * sdce};
+      *out = MF::ocp_nlp_value(T, L, ag);
+    }
+  }
+}
+
 template<class Kern>
 hipError_t lane_launch(Kern kern, const int64_t total, const MeshFnArgs &a, hipStream_t stream)
 {
@@ -257,6 +291,22 @@ hipError_t mesh_dyn_launch(const MeshFnArgs &a, hipStream_t stream)
   const hipError_t e = lane_launch(mesh_dyn_F_kernel, a.batch * a.m.N * a.m.nx, a, stream);
   if (e != hipSuccess || !a.dF) return e;
   return lane_launch(mesh_dyn_dF_kernel, a.batch * a.m.dyn_nnz, a, stream);
+}
+
+hipError_t ocp_nlp_launch(const OcpNlpArgs &args, hipStream_t stream)
+{
+  OcpNlpArgs a = args;
+  a.agents     = kNlpAgents;
+  if (const char *k = knob("SFB_NLP_AGENTS")) {
+    const int v = std::atoi(k);
+    if (v >= 1 && v <= 1024) a.agents = v;
+  }
+  const int64_t items = a.dg ? a.T.m + a.T.nnz : a.T.m;
+  if (a.batch <= 0 || items <= 0) return hipSuccess;
+  const int64_t groups = (a.batch + a.agents - 1) / a.agents, chunks = (items + 255) / 256;
+  if (groups > 0x7fffffff) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ocp_nlp_kernel, dim3((unsigned)groups, (unsigned)(chunks < 65535 ? chunks : 65535)), dim3(256), 0, stream, a);
+  return hipGetLastError();
 }
 
 hipError_t mesh_resample_launch(const MeshResampleArgs &a, hipStream_t stream)

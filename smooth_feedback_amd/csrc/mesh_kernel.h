@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "../../include/smooth_feedback_amd/mesh_function.hpp"
+
 namespace sfb {
 
 constexpr int kMeshMaxK   = 13;  // K + 1 <= 14 raised collocation points
@@ -78,5 +80,15 @@ struct MeshFnArgs {
 hipError_t mesh_eval_launch(const MeshFnArgs &a, hipStream_t stream);
 hipError_t mesh_integrate_launch(const MeshFnArgs &a, hipStream_t stream);
 hipError_t mesh_dyn_launch(const MeshFnArgs &a, hipStream_t stream);
+
+// ---- the collocation NLP of an OCP (ocp_to_nlp.hpp): g [batch][m] and the CSR values of dg_dx [batch][nnz], fused ----
+struct OcpNlpArgs {
+  smooth_feedback_amd::meshfn::OcpNlpTables T;  // device pointers: nodes, D and the decode records of one (mesh, dims)
+  int64_t batch, n;
+  int32_t agents;  // agents a lane walks with one decoded item (set by the launch)
+  const double *x, *Ff, *dFf, *Fg, *dFg, *Fcr, *dFcr, *ce, *dce;  // the Jacobians NULL: values only
+  double *g, *dg;
+};
+hipError_t ocp_nlp_launch(const OcpNlpArgs &a, hipStream_t stream);
 
 }  // namespace sfb

@@ -8,7 +8,12 @@ integrate and compare (mesh_dyn_error_batch_*).
 Functions over the mesh with first derivatives (mesh_function.hpp; sfb_mesh_eval_batch, sfb_mesh_integrate_batch,
 sfb_mesh_dyn_batch): the caller's model values F (B, N, nf) and Jacobians dF (B, N, nf, 1 + nx + nu), columns (t | x | u), go
 in; values and, for eval and dyn, the CSR values of the derivative in the order of mesh_eval_pattern / mesh_dyn_pattern come
-out (variables [t0 | tf | x_0 .. x_N | u_0 .. u_{N-1}])."""
+out (variables [t0 | tf | x_0 .. x_N | u_0 .. u_{N-1}]).
+
+The collocation NLP of an optimal control problem over the mesh (ocp_to_nlp.hpp; sfb_ocp_nlp_*): dims = (nx, nu, nq, ncr, nce),
+variables [tf | q | x_0 .. x_N | u_0 .. u_{N-1}] with t0 = 0, constraints [dyn | integrals | running | end].  The model at the
+nodes (times tf tau_i) for f, g and cr and the end constraint with its Jacobian go in; g (B, m) and the CSR values of dg_dx
+(B, nnz) in the order of ocp_nlp_pattern come out of one fused launch."""
 import ctypes as C
 
 import numpy as np
@@ -228,3 +233,100 @@ def mesh_dyn_batch(mesh, nu, t0, tf, X, F, dF=None):
     out_dF = torch.empty((B, len(mesh_dyn_pattern(m, nx, nu)[1])), dtype=torch.float64, device=F.device) if dF is not None else None
     _tensor_call(lambda mm, *a, stream: mesh_dyn_batch_device(mm, B, nx, nu, *a, stream=stream), m, [t0, tf, X, F, dF], [out_F, out_dF])
     return out_F, out_dF
+
+
+def _dims(dims):
+    d = [int(v) for v in dims]
+    if len(d) != 5:
+        raise ValueError("dims: expected (nx, nu, nq, ncr, nce), got %r" % (dims,))
+    return _capi.SfbOcpDims(*d)
+
+
+def ocp_nlp_structure(mesh, dims):
+    """(var_beg (5,), con_beg (5,)): where tf, q, x, u start and n; where the constraint segments start and m
+    (sfb_ocp_nlp_structure; host only)"""
+    m, d = _mesh(mesh), _dims(dims)
+    vb, cb = np.zeros(5, np.int64), np.zeros(5, np.int64)
+    _capi.check(_capi.lib.sfb_ocp_nlp_structure(C.byref(m.c), C.byref(d), _ptr(vb), _ptr(cb)))
+    return vb, cb
+
+
+def ocp_nlp_pattern(mesh, dims):
+    """(rowptr (m + 1,), colind (nnz,)) of dg_dx (sfb_ocp_nlp_pattern; host only)"""
+    m, d = _mesh(mesh), _dims(dims)
+    nnz = C.c_int64()
+    _capi.check(_capi.lib.sfb_ocp_nlp_pattern(C.byref(m.c), C.byref(d), None, None, C.byref(nnz)))
+    rowptr, colind = np.zeros(int(ocp_nlp_structure(m, dims)[1][4]) + 1, np.int32), np.zeros(nnz.value, np.int32)
+    _capi.check(_capi.lib.sfb_ocp_nlp_pattern(C.byref(m.c), C.byref(d), _ptr(rowptr), _ptr(colind), C.byref(nnz)))
+    return rowptr, colind
+
+
+def ocp_nlp_bounds(mesh, dims, crl, cru, cel, ceu):
+    """-> (xl, xu, gl, gu, w_scaling) (sfb_ocp_nlp_bounds; host only)"""
+    m, d = _mesh(mesh), _dims(dims)
+    vb, cb = ocp_nlp_structure(m, dims)
+    arr = [np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (crl, cru, cel, ceu)]
+    for a, want, name in zip(arr, (d.ncr, d.ncr, d.nce, d.nce), ("crl", "cru", "cel", "ceu")):
+        if len(a) != want:
+            raise ValueError("%s: expected %d values, got %d" % (name, want, len(a)))
+    xl, xu, gl, gu = np.zeros(vb[4]), np.zeros(vb[4]), np.zeros(cb[4]), np.zeros(cb[4])
+    ws = C.c_double()
+    _capi.check(_capi.lib.sfb_ocp_nlp_bounds(C.byref(m.c), C.byref(d), *[_ptr(a) if len(a) else None for a in arr], _ptr(xl), _ptr(xu),
+                                             _ptr(gl) if len(gl) else None, _ptr(gu) if len(gu) else None, C.byref(ws)))
+    return xl, xu, gl, gu, ws.value
+
+
+def _ocp_nlp_shapes(m, d, B):
+    nz, N = 1 + d.nx + d.nu, m.N
+    return [(B, N, d.nx), (B, N, d.nx, nz), (B, N, d.nq), (B, N, d.nq, nz), (B, N, d.ncr), (B, N, d.ncr, nz), (B, d.nce), (B, d.nce, 1 + 2 * d.nx + d.nq)]
+
+
+def ocp_nlp_batch_host(mesh, dims, x, Ff, dFf, Fg, dFg, Fcr, dFcr, ce, dce):
+    """x (B, n); Ff (B, N, nx), Fg (B, N, nq), Fcr (B, N, ncr) and their Jacobians (B, N, nf, 1 + nx + nu); ce (B, nce),
+    dce (B, nce, 1 + 2 nx + nq).  The four Jacobians None: values only.  -> g (B, m) and the CSR values (B, nnz) or None
+    (sfb_ocp_nlp_batch_host)"""
+    m, d = _mesh(mesh), _dims(dims)
+    vb, cb = ocp_nlp_structure(m, dims)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] != vb[4]:
+        raise ValueError("x: expected shape (B, %d), got %r" % (vb[4], x.shape))
+    B = len(x)
+    jac = [dFf, dFg, dFcr, dce]
+    if any(a is None for a in jac) and not all(a is None for a in jac):
+        raise ValueError("the Jacobians dFf, dFg, dFcr, dce: all or none")
+    deriv = dFf is not None
+    arrays = []
+    for k, (a, shape) in enumerate(zip([Ff, dFf, Fg, dFg, Fcr, dFcr, ce, dce], _ocp_nlp_shapes(m, d, B))):
+        if k % 2 == 1 and not deriv:
+            arrays.append(None)
+            continue
+        a = np.ascontiguousarray(a, dtype=np.float64) if a is not None else np.zeros(shape)
+        if a.shape != shape:
+            raise ValueError("input %d: expected shape %r, got %r" % (k, shape, a.shape))
+        arrays.append(a)
+    g = np.zeros((B, cb[4]))
+    dg = np.zeros((B, len(ocp_nlp_pattern(m, dims)[1]))) if deriv else None
+    ptr = lambda a: _ptr(a) if a is not None and a.size else None                   # noqa: E731
+    _capi.check(_capi.lib.sfb_ocp_nlp_batch_host(C.byref(m.c), C.byref(d), B, _ptr(x), *[ptr(a) for a in arrays], ptr(g), ptr(dg)))
+    return g, dg
+
+
+def ocp_nlp_batch_device(mesh, dims, B, dx, dFf, ddFf, dFg, ddFg, dFcr, ddFcr, dce, ddce, dg, ddg, stream=0):
+    """sfb_ocp_nlp_batch on device pointers (ints; the Jacobians and ddg 0: values only), asynchronous on `stream`."""
+    m, d = _mesh(mesh), _dims(dims)
+    _capi.check(_capi.lib.sfb_ocp_nlp_batch(C.byref(m.c), C.byref(d), int(B), dx or None, dFf or None, ddFf or None, dFg or None, ddFg or None,
+                                            dFcr or None, ddFcr or None, dce or None, ddce or None, dg or None, ddg or None, stream or None))
+
+
+def ocp_nlp_batch(mesh, dims, x, Ff, dFf, Fg, dFg, Fcr, dFcr, ce, dce):
+    """ocp_nlp_batch_host on torch tensors of the device, on the current stream (a segment of length zero: None)"""
+    import torch
+    m, d = _mesh(mesh), _dims(dims)
+    vb, cb = ocp_nlp_structure(m, dims)
+    B = x.shape[0]
+    deriv = dFf is not None
+    g = torch.empty((B, int(cb[4])), dtype=torch.float64, device=x.device)
+    dg = torch.empty((B, len(ocp_nlp_pattern(m, dims)[1])), dtype=torch.float64, device=x.device) if deriv else None
+    tensors = [x] + [t if t is not None and t.numel() else None for t in (Ff, dFf, Fg, dFg, Fcr, dFcr, ce, dce)]
+    _tensor_call(lambda mm, *a, stream: ocp_nlp_batch_device(mm, dims, B, *a, stream=stream), m, tensors, [g, dg])
+    return g, dg
