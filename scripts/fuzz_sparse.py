@@ -14,6 +14,7 @@ if __name__ == "__main__":
         print("debug knobs:", sfb.debug_set_from(os.environ["KNOBS"]))
     N = int(os.environ.get("N", 200)); seed0 = int(os.environ.get("SEED", 1))
     bad = 0
+    regimes = {}
     for it in range(N):
         rng = np.random.default_rng(10**6 + seed0 + it)
         n = int(rng.integers(2, 40)); m = int(rng.integers(2, 60)); B = int(rng.integers(1, int(os.environ.get("BMAX", 24))))
@@ -31,6 +32,11 @@ if __name__ == "__main__":
             viol = rng.random(B) < 0.2
             Ax = np.where(keep[None, :] | viol[:, None], Ax, 0.0)
         plan = sfb.SparseQPPlan(n, m, Pp, Pi, Ap, Aj, ordering=int(rng.integers(0, 2)), keep=keep)
+        # regime of the plan as far as nnzL and k tell (sparse_plan.cpp; tests/sparse_plan_check.cpp prints the full tuple): while the
+        # whole factor and its three constants fit kLdsSmall = 1536 doubles, the unit engine runs on exactly that, rounded up to 64
+        whole = plan.nnzL + n + m + 3
+        cls = "units, lds %4d (whole factor on chip)" % (-(-whole // 64) * 64) if whole <= 1536 else "lds >= 1536 (engine not determined by nnzL and k)"
+        regimes[cls] = regimes.get(cls, 0) + 1
         warm = rng.random() < 0.3
         wx = rng.uniform(-1, 1, (B, n)) if warm else None; wy = rng.uniform(-1, 1, (B, m)) if warm else None
         r = plan.solve_batch_host(Px, q, Ax, l, u, prm, warm_x=wx, warm_y=wy)
@@ -50,3 +56,5 @@ if __name__ == "__main__":
             print("MISMATCH seed", seed0 + it, "n", n, "m", m, "B", B, "pruned", keep is not None, prm, "warm", warm)
             if bad >= 5: break
     print("fuzz sparse: %d configurations, %d mismatching" % (it + 1, bad))
+    for cls in sorted(regimes):
+        print("fuzz sparse: %4d configurations with %s" % (regimes[cls], cls))

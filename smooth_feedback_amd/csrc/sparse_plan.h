@@ -40,8 +40,9 @@ struct SparsePlanHost {
   //   xidx[q]  : (tgt | piv << 16) * idx_scale   (padding: both = k, a scratch slot of the LDS vector);
   //              idx_scale = 8 (byte offsets) when (k+1)*8 < 65536, else 1
   // Storage: unit u, lane l, slot s at [(u * 64 + l) * 2 + s] (one 16-byte value load and one 8-byte index
-  // load per lane and unit); the c slots of a step occupy the leading ceil(c/2) lanes (slot e: lane e % lanes, slot e / lanes).  Unit counts are multiples of kSweepPad and the arrays carry kSweepPad extra
-  // all-padding units so the kernel prefetches branch-free.
+  // load per lane and unit); the c slots of a step occupy the leading ceil(c/2) lanes (natural placement -- slot e: lane e % lanes, slot e / lanes; the bank-aware placement may
+  // put a slot anywhere in those lanes).  Unit counts are multiples of 8 (the kernel's prefetch block) and the arrays carry kSweepPad
+  // extra all-padding units so the kernel prefetches branch-free.
   static constexpr int kSweepPad = 16;
   //   xmask[u] : 64 - (leading lanes of unit u's value load that carry slots);
   //              [full0, full1) : run of completely filled units (multiples of 8), loaded unmasked
@@ -76,8 +77,12 @@ struct SparsePlanHost {
   std::vector<int32_t> f2s;
   // LDS-RESIDENT SUBTREES (sparse_plan.cpp): the columns are cut into segments, each either a subtree whose
   // accumulators fit the item's LDS ("lds": factorised on chip) or a run of top columns (accumulators in HBM).
-  //   seg[10 s ..] = {first supernode, last + 1, first column, last + 1, lds, nL, accN = nL + columns,
-  //                  first K entry, last + 1, first L entry}; LDS layout of a segment: [L entries | D | sink | zero | panel scratch]
+  //   seg[kSegStride s ..] = {first supernode (unit engine: first unit), last + 1, first column, last + 1, lds (1 = closed subtree
+  //                  on chip, 0 = open run of top columns), nL, accN = nL + columns, first K entry, last + 1, first L entry,
+  //                  nout = outside accumulators, omap0 = start of their map in uomap (both 0 for the supernodal engine)};
+  //                  twelve fields, all read by the kernel.  (nL, accN and the first L entry are 0 in the top segments of the
+  //                  supernodal engine, which does not use them.)
+  //                  LDS layout of a segment, supernodal engine: [L entries | D | sink | zero | panel scratch]
   //   pmapL  : LDS offsets of the panel entries (parallel to pmap; 0 outside LDS segments)
   //   rsplit[s] : first HBM step of supernode s's trailing schedule; steps [rptr[s], rsplit[s]) target LDS offsets
   //   KmapL  : LDS offset of every K entry of an LDS segment;  KdescT / KmapT (nnzKT entries, padded): the K
