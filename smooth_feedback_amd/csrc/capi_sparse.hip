@@ -66,7 +66,7 @@ sfb_status upload_plan(const sfb::SparsePlanHost &h, const std::vector<int32_t> 
                                         &h.Kp, &h.Ki, &h.Kdesc, &h.Lp, &h.Li, &h.Rp, &h.Rk, &h.Rpos, &h.Rlen,
                                         &h.fmap, &h.fidx, &h.bmap, &h.bidx, &h.Kmap, &h.rptr, &h.rtgt, &h.rab, &h.snptr, &h.snR, &h.poff, &h.pmap, &h.fmask, &h.bmask,
                                         &h.f2s, &h.seg, &h.pmapL, &h.rsplit, &h.KmapL, &h.KdescT, &h.KmapT, &h.ztop, &h.ustream, &h.utype, &h.uomap,
-                                        Aorig ? Aorig : &none, Amasked ? Amasked : &none};
+                                        &h.ftpos, Aorig ? Aorig : &none, Amasked ? Amasked : &none};
   constexpr int NA = sizeof(arrs) / sizeof(arrs[0]);
   size_t off[NA + 1];
   off[0] = 0;
@@ -88,8 +88,8 @@ sfb_status upload_plan(const sfb::SparsePlanHost &h, const std::vector<int32_t> 
                             &d.Kp, &d.Ki, &d.Kdesc, &d.Lp, &d.Li, &d.Rp, &d.Rk, &d.Rpos, &d.Rlen,
                             &d.fmap, &d.fidx, &d.bmap, &d.bidx, &d.Kmap, &d.rptr, &d.rtgt, &d.rab, &d.snptr, &d.snR, &d.poff, &d.pmap, &d.fmask, &d.bmask,
                             &d.f2s, &d.seg, &d.pmapL, &d.rsplit, &d.KmapL, &d.KdescT, &d.KmapT, &d.ztop, &d.ustream, &d.utype, &d.uomap,
-                            &d.Aorig, &d.Amasked};
-  d.funits = h.funits; d.bunits = h.bunits; d.ffull0 = h.ffull0; d.ffull1 = h.ffull1; d.bfull0 = h.bfull0; d.bfull1 = h.bfull1; d.idx_scale = h.idx_scale; d.rsteps = h.rsteps; d.maxcol = h.maxcol; d.nsn = h.nsn; d.lds_doubles = h.lds_doubles; d.nseg = h.nseg; d.nnzKT = h.nnzKT; d.nztop = h.nztop; d.units = h.units; d.nunits = h.nunits;
+                            &d.ftpos, &d.Aorig, &d.Amasked};
+  d.funits = h.funits; d.bunits = h.bunits; d.ftail0 = h.ftail0; d.ftail = h.ftail; d.ffull0 = h.ffull0; d.ffull1 = h.ffull1; d.bfull0 = h.bfull0; d.bfull1 = h.bfull1; d.idx_scale = h.idx_scale; d.rsteps = h.rsteps; d.maxcol = h.maxcol; d.nsn = h.nsn; d.lds_doubles = h.lds_doubles; d.nseg = h.nseg; d.nnzKT = h.nnzKT; d.nztop = h.nztop; d.units = h.units; d.nunits = h.nunits;
   for (int a = 0; a < NA; ++a) *ptrs[a] = dblob + off[a];
   d.nnzA_io = nnzA_io;
   d.nmasked = Amasked ? (int)Amasked->size() - 512 : 0;  // without the padding

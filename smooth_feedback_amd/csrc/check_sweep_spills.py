@@ -14,7 +14,9 @@ import re
 import sys
 
 lines = open(sys.argv[1]).read().split("\n")
-stream = [i for i, l in enumerate(lines) if re.search(r"global_load_dwordx4 .*off offset:\d+", l)]
+# (the steps of the register tail, marked `; lat tail` in their asm statements, belong to the sweeps as well: they run between the
+# forward and the backward sweep with the backward stream's head in flight and are longer than the gap below)
+stream = [i for i, l in enumerate(lines) if re.search(r"global_load_dwordx4 .*off offset:\d+|; lat tail", l)]
 if not stream:
     sys.exit("check_sweep_spills: no stream loads found (the sweeps changed?)")
 regions, start, prev = [], stream[0], stream[0]
@@ -94,12 +96,13 @@ for a, b in regions:
 # file by number: a[0 .. kAgprFree) are the compiler's, a[kAgprFree .. 255] the resident stream's (kAgprFree: a constant of
 # qp_sparse.hip, read from the source next to this script).  Every access to an AccVGPR >= kAgprFree has to be one of ours -- a
 # literal `v_accvgpr_read_b32 v, a[N]` of the prefix or a `global_load_dwordx4 a[N:M]` of the load -- and none of ours may name
-# one below it.
+# one below it.  The register tail of the forward sweep (kLatTail, lat_tail_load) takes its AccVGPR pairs from the top of the same
+# range with `global_load_dwordx2 a[N:M]` and reads them the same way.
 import os
 src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "qp_sparse.hip")).read()
 AGPR_FREE = int(re.search(r"constexpr int kAgprFree\s*=\s*(\d+)\s*;", src).group(1))
 NUM = r"(0x[0-9a-fA-F]+|\d+)"  # (the assembler prints a literal register number the way the operand was formed: a[64:0x43])
-ours = re.compile(r"v_accvgpr_read_b32 v\d+, a\[" + NUM + r"\]|global_load_dwordx4 a\[" + NUM + ":" + NUM + r"\]")
+ours = re.compile(r"v_accvgpr_read_b32 v\d+, a\[" + NUM + r"\]|global_load_dwordx[24] a\[" + NUM + ":" + NUM + r"\]")
 for i, l in enumerate(lines):
     code = l.split(";")[0]
     idx = [int(x, 0) for x in re.findall(r"\ba\[?" + NUM, code)] + [int(x, 0) for pr in re.findall(r"\ba\[" + NUM + ":" + NUM + r"\]", code) for x in pr]

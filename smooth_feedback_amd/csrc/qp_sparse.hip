@@ -1164,10 +1164,34 @@ constexpr int kLatRegRows = 12;
 // positions: the table {1 / rho of the three classes, rho of the three classes} (a class byte is an offset into it)
 __host__ __device__ constexpr size_t lat_lds_doubles(const int n, const int m)
 {
-  return (size_t)(((n + m + 2) + 1) & ~1) + n + 2 * (size_t)m + (n + m) + 8 + (2 * kLatRegRows * 64) / 4 + (kLatRegRows * 64) / 8 + 4;
+  const size_t lay = (size_t)(((n + m + 2) + 1) & ~1) + n + 2 * (size_t)m + (n + m) + 8 + (2 * kLatRegRows * 64) / 4 + (kLatRegRows * 64) / 8 + 4;
+  // rhs_from_regs reads the kLatRegRows padded rows of c q without a predicate: behind the work vector there are at least that many doubles
+  const size_t rows = (size_t)(((n + m + 2) + 1) & ~1) + kLatRegRows * 64;
+  return lay > rows ? lay : rows;
 }
-constexpr int kLatResident = (256 - kAgprFree) / 4;  // kAgprFree == 0: all 256 AccVGPRs = 64 KB of the 232 KB a headline item streams per iteration
-__device__ __forceinline__ bool lat_resident_ok(const SparsePlanDev &pl) { return uni(pl.funits) >= kLatResident + 16; }
+// REGISTER TAIL of the LAT forward sweep.  The forward schedule of a plan ends in ftail column units (sparse_plan.h): unit
+// funits - T + i holds the entries of column k - 1 - T + i only, and all that column still waits for is the pivot the unit before it
+// finished -- a write-then-read of one t[j] through LDS per unit, 60-80 ns each on the dependent chain of the wave.  The LAT form
+// takes the last T = min(kLatTail, ftail) of them out of the sweep: lane l keeps row k - 1 - kLatTail + l of the work vector in a
+// register, L(row of lane l, column of step s) sits in the AccVGPR pair a[kLatTailReg0 + 2 s .. + 1] of lane l (lat_tail_load, once
+// per item, from the forward sweep copy), and step s is a v_readlane of the pivot and one fma on the lanes that have an entry
+// (a lane without one keeps its value whatever the pivot is, like a padding slot).  Same operands, same order per row: same bits.
+// The AccVGPRs come out of the resident head of the stream (four per unit); 0: no register tail, the kernel of round 6.
+#ifndef SFB_LAT_TAIL
+#define SFB_LAT_TAIL 48
+#endif
+constexpr int kLatTail = SFB_LAT_TAIL;
+constexpr int kLatTailMax = 48;  // == SparsePlanHost::kSweepTailMax
+static_assert(kLatTail >= 0 && kLatTail <= kLatTailMax && kLatTail % 8 == 0, "the forward sweep ends on a block of 8 units; lanes 0 .. kLatTail");
+constexpr int kLatTailReg0 = 256 - 2 * kLatTail;
+constexpr int kLatResident = ((kLatTailReg0 - kAgprFree) / 4) & ~7;  // whole blocks; kAgprFree == 0, no tail: all 256 AccVGPRs = 64 KB of the 232 KB a headline item streams per iteration
+// units of the forward schedule the register tail takes (wave-uniform): the sweep in front of it keeps at least one block
+__device__ __forceinline__ int lat_tail_units(const SparsePlanDev &pl)
+{
+  const int ft = uni(pl.ftail);
+  return (kLatTail > 0 && uni(pl.idx_scale) == 8 && uni(pl.ftail0) >= 8) ? (ft < kLatTail ? ft : kLatTail) : 0;
+}
+__device__ __forceinline__ bool lat_resident_ok(const SparsePlanDev &pl, const int treg) { return uni(pl.funits) - treg >= kLatResident + 16; }
 __device__ __forceinline__ void lat_resident_load(const double *LxF, const int lane)
 {
   asm volatile("" ::: "a255");  // (the kernel's AccVGPR count)
@@ -1186,13 +1210,57 @@ __device__ __forceinline__ void lat_resident_load(const double *LxF, const int l
   });
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
+// the tail's L into the AccVGPRs; returns the lane's steps that have an entry (bit s: column k - 1 - kLatTail + s updates this lane's row)
+__device__ __forceinline__ unsigned long long lat_tail_load(const SparsePlanDev &pl, const double *LxF, const int lane, const int treg)
+{
+  asm volatile("" ::: "a255");
+  unsigned long long have = 0;
+  const int i0 = uni(pl.ftail) - kLatTail;  // the plan's tail unit of step 0 (negative: the plan's tail is shorter)
+  const int32_t *pos = pl.ftpos + (lane + i0);  // row of this lane among the plan's tail rows
+  auto for_steps = [&]<int... S>(std::integer_sequence<int, S...>, auto &&fn) { (fn(std::integral_constant<int, S>{}), ...); };
+  for_steps(std::make_integer_sequence<int, kLatTail>{}, [&]<int S>(std::integral_constant<int, S>) {
+    const bool on = S >= kLatTail - treg && lane > S && lane <= kLatTail;  // (on: unit i0 + S >= 0 and row lane + i0 > i0 + S)
+    const int q   = on ? pos[(i0 + S) * kWave] : -1;
+    const double *pv = LxF + (q >= 0 ? q : 0);
+    asm volatile("global_load_dwordx2 a[%1:%2], %0, off" : : "v"(pv), "n"(kLatTailReg0 + 2 * S), "n"(kLatTailReg0 + 2 * S + 1) : "memory");
+    if (q >= 0) have |= 1ull << S;
+  });
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  return have;
+}
 __device__ __forceinline__ void ldl_solve_lat(const SparsePlanDev &pl, const Ws &w, double *t, const int lane, const double *Dinv,
-                                              vdouble2 (&lx)[8], vint2 (&ix)[8], const bool pre, const bool next, const bool resident = false)
+                                              vdouble2 (&lx)[8], vint2 (&ix)[8], const bool pre, const bool next, const bool resident = false,
+                                              const int treg = 0, const unsigned long long tail_have = 0)
 {
   const int k = uni(pl.k);
-  if (resident) sweep_dev<8, true, false, false, true, kLatResident>(pl.fidx, uni(pl.funits), w.LxF, t, lane, pl.fmask, 0, 0, lx, ix, pl.bidx, w.LxB, pl.bmask);
-  else if (pre) sweep_dev<8, true, false, true, true>(pl.fidx, uni(pl.funits), w.LxF, t, lane, pl.fmask, 0, 0, lx, ix, pl.bidx, w.LxB, pl.bmask);
-  else sweep_dev<8, true, false, false, true>(pl.fidx, uni(pl.funits), w.LxF, t, lane, pl.fmask, 0, 0, lx, ix, pl.bidx, w.LxB, pl.bmask);
+  const int fu = uni(pl.funits) - treg;  // the register tail below takes the last treg units
+  if (resident) sweep_dev<8, true, false, false, true, kLatResident>(pl.fidx, fu, w.LxF, t, lane, pl.fmask, 0, 0, lx, ix, pl.bidx, w.LxB, pl.bmask);
+  else if (pre) sweep_dev<8, true, false, true, true>(pl.fidx, fu, w.LxF, t, lane, pl.fmask, 0, 0, lx, ix, pl.bidx, w.LxB, pl.bmask);
+  else sweep_dev<8, true, false, false, true>(pl.fidx, fu, w.LxF, t, lane, pl.fmask, 0, 0, lx, ix, pl.bidx, w.LxB, pl.bmask);
+  if constexpr (kLatTail > 0) {
+    if (treg > 0) {  // (the backward stream's head is in flight in lx / ix: LDS and registers only from here to the backward sweep)
+      double *const tl = t + (k - 1 - kLatTail) + lane;
+      const bool mine = lane >= kLatTail - treg && lane <= kLatTail;
+      double tr = mine ? *tl : 0.0;
+      auto for_steps = [&]<int... S>(std::integer_sequence<int, S...>, auto &&fn) { (fn(std::integral_constant<int, S>{}), ...); };
+      auto block = [&]<int B>(std::integral_constant<int, B>) {
+        if (8 * B + 8 > kLatTail - treg) {  // (treg is a multiple of 8: whole blocks; the steps in front of the tail have no entry anywhere)
+          for_steps(std::make_integer_sequence<int, 8>{}, [&]<int E>(std::integral_constant<int, E>) {
+            constexpr int S = 8 * B + E;
+            int l0, h0;
+            asm volatile("v_accvgpr_read_b32 %0, a[%2] ; lat tail (check_sweep_spills.py)\n\tv_accvgpr_read_b32 %1, a[%3]"
+                         : "=v"(l0), "=v"(h0)
+                         : "n"(kLatTailReg0 + 2 * S), "n"(kLatTailReg0 + 2 * S + 1));
+            const double piv = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(tr), S), __builtin_amdgcn_readlane(__double2loint(tr), S));
+            if ((tail_have >> S) & 1) tr = fma(-__hiloint2double(h0, l0), piv, tr);
+          });
+        }
+      };
+      for_steps(std::make_integer_sequence<int, kLatTail / 8>{}, block);
+      if (mine && lane > kLatTail - treg) *tl = tr;
+      wave_lds_fence();
+    }
+  }
   for (int j0 = lane; j0 < k; j0 += kWave * 8) {  // D^-1 (:458) from LDS
     double dv[8];
 #pragma unroll
@@ -2387,9 +2455,15 @@ __device__ __forceinline__ int sp_solve_item(const SparsePlanDev &pl, const Dens
   // LAT, round 5: the head of the forward stream resident in the wave's AccVGPRs for as long as it iterates on the item (the
   // launch runs at the fabric's read rate: what is on chip is not streamed)
   [[maybe_unused]] bool lat_resident = false;
+  [[maybe_unused]] int lat_treg = 0;                   // units of the forward schedule done in registers (ldl_solve_lat)
+  [[maybe_unused]] unsigned long long lat_have = 0;   // ... and the steps of them in which this lane's row has an entry
   if constexpr (LAT) {
-    lat_resident = iterates && uni(pl.idx_scale) == 8 && uni(pl.bunits) >= 8 && lat_resident_ok(pl);
+    if (iterates && uni(pl.funits) >= 8 && uni(pl.bunits) >= 8) lat_treg = lat_tail_units(pl);  // (the chained sweeps' condition, lat_chain below)
+    lat_resident = iterates && uni(pl.idx_scale) == 8 && uni(pl.bunits) >= 8 && lat_resident_ok(pl, lat_treg);
     if (lat_resident) lat_resident_load(w.LxF, lane);
+    if constexpr (kLatTail > 0) {
+      if (lat_treg > 0) lat_have = lat_tail_load(pl, w.LxF, lane, lat_treg);
+    }
   }
   auto vectors_home = [&] {  // LAT: x, z, y back to the workspace (polish, report, or the next wave that takes the item up)
     if constexpr (LAT) {
@@ -2506,7 +2580,7 @@ __device__ __forceinline__ int sp_solve_item(const SparsePlanDev &pl, const Dens
         // is NOT done: the compiler is free to copy loop-carried registers while their loads are in flight (wrong results).
         vdouble2 lat_lx[8];
         vint2 lat_ix[8];
-        ldl_solve_lat(pl, w, t, lane, vdinv, lat_lx, lat_ix, false, false, lat_resident);
+        ldl_solve_lat(pl, w, t, lane, vdinv, lat_lx, lat_ix, false, false, lat_resident, lat_treg, lat_have);
       } else {
         ldl_solve_dev<8>(pl, w, t, lane, lean, vdinv);
       }

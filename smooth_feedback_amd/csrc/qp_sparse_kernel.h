@@ -22,6 +22,8 @@ struct SparsePlanDev {
   const int32_t *fmap, *fidx, *bmap, *bidx;  // packed sweep schedules, see sparse_plan.h
   const int32_t *fmask, *bmask;              // lane-mask shifts of the units' value loads (one word per unit)
   int funits, bunits, idx_scale, ffull0, ffull1, bfull0, bfull1;
+  int ftail0, ftail;     // column tail of the forward schedule: units [ftail0, ftail0 + ftail) hold one column each (sparse_plan.h)
+  const int32_t *ftpos;  // [tail unit i][row r - (k - 1 - ftail)]: position of L(r, column of unit i) in the forward sweep copy, or -1
   const int32_t *Kmap, *rptr, *rtgt, *rab;   // right-looking factorisation schedule
   int rsteps, maxcol;
   const int32_t *snptr, *snR, *poff, *pmap;  // (relaxed) supernodes of the factorisation and their panel maps

@@ -937,7 +937,7 @@ bool build_sparse_plan(int n, int m, const int32_t *Pp, const int32_t *Pi, const
   if (k + 1 >= (1 << 16)) { *msg = "n+m too large for the packed sweep encoding (max 65534)"; return false; }
   o.idx_scale = ((k + 1) * 8 < (1 << 16)) ? 8 : 1;
   auto build = [&](bool forward, std::vector<int32_t> &xmap, std::vector<int32_t> &xidx, int &units,
-                   std::vector<int32_t> &xmask, int &full0, int &full1) {
+                   std::vector<int32_t> &xmask, int &full0, int &full1, int &tail0, int &ntail) {
     const int cap = 128;  // slots per dependent step
     // Critical-path list scheduling.  Slot = one entry of L, enumerated in the sequential sweep order.  It
     // depends on (a) the previous update of its target (per-target order = the sequential one) and (b) the
@@ -962,44 +962,78 @@ bool build_sparse_plan(int n, int m, const int32_t *Pp, const int32_t *Pi, const
       if (last_upd[tg] >= 0) { prev_same[q] = last_upd[tg]; next_same[last_upd[tg]] = q; }
       last_upd[tg] = q;
     }
-    // heights, reverse order (every dependant of a slot has a larger number)
-    std::vector<int32_t> height(ns, 1), colh(k, 0);
-    for (int q = ns - 1; q >= 0; --q) {
-      int h = 0;
-      if (next_same[q] >= 0) h = height[next_same[q]];
-      else h = std::max(h, (int)colh[sl[q].tgt]);  // last update of its target: the target's own slots wait for it
-      height[q] = h + 1;
-      colh[sl[q].piv] = std::max(colh[sl[q].piv], height[q]);
-    }
-    std::vector<int32_t> npred(ns, 0);
-    for (int q = 0; q < ns; ++q) npred[q] = (prev_same[q] >= 0 ? 1 : 0) + (last_upd[sl[q].piv] >= 0 ? 1 : 0);
-    std::vector<std::vector<std::array<int32_t, 3>>> slots;  // per step: (pos, tgt, piv)
-    std::vector<std::pair<int32_t, int32_t>> heap;          // (height, -slot): ready slots
-    std::vector<int32_t> arriving;                           // become ready for the NEXT step
-    for (int q = 0; q < ns; ++q)
-      if (npred[q] == 0) heap.emplace_back(height[q], -q);
-    std::make_heap(heap.begin(), heap.end());
-    int done = 0;
-    while (done < ns) {
-      slots.emplace_back();
-      arriving.clear();
-      for (int c = 0; c < cap && !heap.empty(); ++c) {
-        std::pop_heap(heap.begin(), heap.end());
-        const int q = -heap.back().second;
-        heap.pop_back();
-        slots.back().push_back({sl[q].pos, sl[q].tgt, sl[q].piv});
-        ++done;
-        if (next_same[q] >= 0) {
-          if (--npred[next_same[q]] == 0) arriving.push_back(next_same[q]);
-        } else {  // target final: release its own slots
-          const int tt = tof(sl[q].tgt);
-          for (int r = col_first[tt]; r < col_first[tt + 1]; ++r)
-            if (--npred[r] == 0) arriving.push_back(r);
+    using Steps = std::vector<std::vector<std::array<int32_t, 3>>>;  // per step: (pos, tgt, piv)
+    // the list scheduler over the slots whose pivot is processed before position `cut` (cut == k: all of them)
+    auto schedule = [&](const int cut) {
+      const int nsched = col_first[cut];
+      // heights among those slots, reverse order (every dependant of a slot has a larger number)
+      std::vector<int32_t> height(ns, 1), colh(k, 0);
+      for (int q = nsched - 1; q >= 0; --q) {
+        int h = 0;
+        if (next_same[q] >= 0) h = next_same[q] < nsched ? height[next_same[q]] : 0;
+        else h = std::max(h, (int)colh[sl[q].tgt]);  // last update of its target: the target's own slots wait for it
+        height[q] = h + 1;
+        colh[sl[q].piv] = std::max(colh[sl[q].piv], height[q]);
+      }
+      std::vector<int32_t> npred(ns, 0);
+      for (int q = 0; q < ns; ++q) npred[q] = (prev_same[q] >= 0 ? 1 : 0) + (last_upd[sl[q].piv] >= 0 ? 1 : 0);
+      Steps slots;
+      std::vector<std::pair<int32_t, int32_t>> heap;          // (height, -slot): ready slots
+      std::vector<int32_t> arriving;                           // become ready for the NEXT step
+      for (int q = 0; q < nsched; ++q)
+        if (npred[q] == 0) heap.emplace_back(height[q], -q);
+      std::make_heap(heap.begin(), heap.end());
+      int done = 0;
+      while (done < nsched) {
+        slots.emplace_back();
+        arriving.clear();
+        for (int c = 0; c < cap && !heap.empty(); ++c) {
+          std::pop_heap(heap.begin(), heap.end());
+          const int q = -heap.back().second;
+          heap.pop_back();
+          slots.back().push_back({sl[q].pos, sl[q].tgt, sl[q].piv});
+          ++done;
+          if (next_same[q] >= 0) {
+            if (--npred[next_same[q]] == 0 && next_same[q] < nsched) arriving.push_back(next_same[q]);
+          } else {  // target final: release its own slots
+            const int tt = tof(sl[q].tgt);
+            for (int r = col_first[tt]; r < col_first[tt + 1]; ++r)
+              if (--npred[r] == 0 && r < nsched) arriving.push_back(r);
+          }
+        }
+        for (int q : arriving) {
+          heap.emplace_back(height[q], -q);
+          std::push_heap(heap.begin(), heap.end());
         }
       }
-      for (int q : arriving) {
-        heap.emplace_back(height[q], -q);
-        std::push_heap(heap.begin(), heap.end());
+      return slots;
+    };
+    Steps slots = schedule(k);
+    // COLUMN TAIL of the forward sweep (sparse_plan.h): the last T columns that have entries, c0 .. k - 2, leave the list
+    // scheduler and get one unit each, in ascending order behind the body [columns < c0, padded to whole blocks of 8].  A trailing
+    // row then receives every body update before any tail update, and the tail updates in ascending column order: per target the
+    // order is the sequential one, as before.  T is a multiple of 8 (the sweep ends on a block); the layout is taken where it
+    // needs no more units than the list scheduler alone -- the chain-bound end of that schedule is one column per unit anyway,
+    // give or take a column split over two units and the padding of the last block.
+    tail0 = ntail = 0;
+    if (forward && o.idx_scale == 8) {
+      const int today = (((int)slots.size() + 7) / 8) * 8;
+      int best = today + 1, bestT = 0;
+      Steps body_best;
+      for (int T = 8; T <= SparsePlanHost::kSweepTailMax && T <= k - 1; T += 8) {
+        Steps body = schedule(k - 1 - T);
+        const int total = (((int)body.size() + 7) / 8) * 8 + T;
+        if (total <= best) { best = total; bestT = T; body_best = std::move(body); }  // (ties: the longer tail)
+      }
+      if (bestT > 0 && best <= today) {
+        slots = std::move(body_best);
+        slots.resize(((slots.size() + 7) / 8) * 8);  // empty units up to the block
+        tail0 = (int)slots.size();
+        ntail = bestT;
+        for (int j = k - 1 - bestT; j < k - 1; ++j) {
+          slots.emplace_back();
+          for (int q = col_first[j]; q < col_first[j + 1]; ++q) slots.back().push_back({sl[q].pos, sl[q].tgt, sl[q].piv});
+        }
       }
     }
     const int steps = (int)slots.size();
@@ -1056,8 +1090,16 @@ bool build_sparse_plan(int n, int m, const int32_t *Pp, const int32_t *Pi, const
       s = e;
     }
   };
-  build(true, o.fmap, o.fidx, o.funits, o.fmask, o.ffull0, o.ffull1);
-  build(false, o.bmap, o.bidx, o.bunits, o.bmask, o.bfull0, o.bfull1);
+  build(true, o.fmap, o.fidx, o.funits, o.fmask, o.ffull0, o.ffull1, o.ftail0, o.ftail);
+  // where the placer put the entries of the tail's columns: [tail unit i][row - c0] -> slot of the forward sweep copy
+  o.ftpos.assign((size_t)o.ftail * 64, -1);
+  for (int i = 0; i < o.ftail; ++i)
+    for (int s = 0; s < 128; ++s) {
+      const size_t q = (size_t)(o.ftail0 + i) * 128 + s;
+      if (o.fmap[q] >= 0) o.ftpos[(size_t)i * 64 + (((uint32_t)o.fidx[q] & 0xFFFFu) / o.idx_scale - (k - 1 - o.ftail))] = (int32_t)q;
+    }
+  int none0 = 0, none1 = 0;
+  build(false, o.bmap, o.bidx, o.bunits, o.bmask, o.bfull0, o.bfull1, none0, none1);
 
   return true;
 }

@@ -48,6 +48,18 @@ struct SparsePlanHost {
   //              [full0, full1) : run of completely filled units (multiples of 8), loaded unmasked
   std::vector<int32_t> fmap, fidx, bmap, bidx, fmask, bmask;
   int funits = 0, bunits = 0, idx_scale = 1, ffull0 = 0, ffull1 = 0, bfull0 = 0, bfull1 = 0;
+  // COLUMN TAIL of the forward sweep: the end of a forward schedule is bound by the chain through the last columns (the dense
+  // triangle of the root separator), one column per unit at best.  The planner says so outright: the forward schedule is
+  // [body | tail], the body being the list schedule of the entries of columns < c0 = k - 1 - ftail, padded to whole blocks of 8
+  // (ftail0 units), and tail unit ftail0 + i holding exactly the entries of column c0 + i (possibly none) -- ordinary units like
+  // any other, placed and masked alike.  ftail is a multiple of 8, at most kSweepTailMax; ftail0 = ftail = 0 where the layout
+  // would need more units than the list scheduler alone, and for plans in element indices.
+  static constexpr int kSweepTailMax = 48;
+  int ftail0 = 0, ftail = 0;
+  //   ftpos[i * 64 + (r - c0)] : slot (index into fmap / the forward sweep copy) of entry (r, c0 + i), or -1 -- the tail rows
+  //   c0 + 1 .. k - 1 are at most kSweepTailMax < 64.  A reader that keeps those rows in registers (the LAT form's register tail,
+  //   qp_sparse.hip) finds its operands with it wherever the bank-aware placement put them.
+  std::vector<int32_t> ftpos;
   // Right-looking, supernodal factorisation schedule.  Accumulators: [L values (nnzL) | D (k) | scratch | zero];
   // Kmap[p] = accumulator of KKT entry p.  When a column j is final it updates, for every pair of its rows
   // (r_a >= r_b), the accumulator of entry (r_a, r_b) [the diagonal D(r_b) when a == b]:
