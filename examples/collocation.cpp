@@ -414,6 +414,36 @@ int sfbx_ocp_nlp_host(int kmin, int kmax, int n, int k, int nops, const int32_t 
   return -1;  // no such (mesh type, dims)
 }
 
+// OCPNLP::d2l_dx2 of the same problems on the same (mesh type, dims) pairs
+int sfbx_ocp_nlp_hess_host(int kmin, int kmax, int n, int k, int nops, const int32_t * ops, const int32_t * dims, const int32_t * nterms,
+                           const int32_t * terms, const double * coef, const double * crl, const double * cru, const double * cel, const double * ceu,
+                           const double * x, const double * lambda, double sigma, int numerical, int calls, int32_t * sizes, int32_t * hcolptr,
+                           int32_t * hrowind, int32_t * hcolptr2, int32_t * hrowind2, double * d2l)
+{
+  sfbx::OcpData d{};
+  for (int q = 0, at = 0; q < 5; ++q) {
+    d.tab[q] = sfbx::TermTable{nterms[q], terms + 7 * at, coef + at};
+    at += nterms[q];
+  }
+  d.crl = crl, d.cru = cru, d.cel = cel, d.ceu = ceu;
+  const sfbx::OcpNlpHessOut o{sizes, hcolptr, hrowind, hcolptr2, hrowind2, d2l};
+  using T = sf::diff::Type;
+  try {
+#define SFBX_NLP(KMIN, KMAX, NX, NU, NQ, NCR, NCE) \
+  if (kmin == KMIN && kmax == KMAX && dims[0] == NX && dims[1] == NU && dims[2] == NQ && dims[3] == NCR && dims[4] == NCE) { \
+    const auto mesh = run_script<sf::Mesh<KMIN, KMAX>>(n, k, nops, ops, nullptr); \
+    return numerical ? sfbx::ocp_nlp_hess_run<NX, NU, NQ, NCR, NCE, T::Numerical>(mesh, d, x, lambda, sigma, calls, o) \
+                     : sfbx::ocp_nlp_hess_run<NX, NU, NQ, NCR, NCE, T::Analytic>(mesh, d, x, lambda, sigma, calls, o); \
+  }
+    SFBX_NLP(1, 2, 1, 0, 0, 0, 0) SFBX_NLP(3, 3, 2, 1, 1, 4, 6) SFBX_NLP(3, 6, 3, 2, 2, 1, 3) SFBX_NLP(13, 13, 3, 2, 1, 3, 2)
+#undef SFBX_NLP
+  } catch (const std::exception & e) {
+    std::fprintf(stderr, "collocation harness: %s\n", e.what());
+    return -2;
+  }
+  return -1;  // no such (mesh type, dims)
+}
+
 // the scenario of the reference's tests/test_ocp_to_nlp.cpp as caller code against <smooth/feedback/ocp_to_nlp.hpp>: the
 // problem written as lambdas in an OCP<...>, random x and lambda, and df, dg, d2f, d2g against differences of f, g and
 // lambda' g at the reference's tolerances (1e-4 first, 1e-3 second derivatives, relative in the Frobenius norm as

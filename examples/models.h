@@ -228,6 +228,13 @@ int sfbx_ocp_nlp_host(int kmin, int kmax, int n, int k, int nops, const int32_t 
                       double *f, double *df, double *g, int32_t *rowptr, int32_t *colind, double *dg, int32_t *hcolptr,
                       int32_t *hrowind, double *d2f, double *d2g, double *xl, double *xu, double *gl, double *gu, double *ws,
                       double *x_back, double *lambda_back);
+/* OCPNLP::d2l_dx2(x, sigma, lambda) of the same problems, `calls` times.  sizes [4]: n, m, nnz of the Hessian, 1 when the output
+ * array did not move between the calls; (hcolptr, hrowind): the pattern of the front's member; (hcolptr2, hrowind2): the pattern of
+ * meshfn::ocp_nlp_hess_pattern from the mesh's interval sizes; d2l: the values.  NULL outputs are skipped. */
+int sfbx_ocp_nlp_hess_host(int kmin, int kmax, int n, int k, int nops, const int32_t *ops, const int32_t *dims, const int32_t *nterms,
+                           const int32_t *terms, const double *coef, const double *crl, const double *cru, const double *cel,
+                           const double *ceu, const double *x, const double *lambda, double sigma, int numerical, int calls,
+                           int32_t *sizes, int32_t *hcolptr, int32_t *hrowind, int32_t *hcolptr2, int32_t *hrowind2, double *d2l);
 /* the scenario of the reference's tests/test_ocp_to_nlp.cpp as caller code against <smooth/feedback/ocp_to_nlp.hpp>: 0, or the
  * number of the first expectation that fails */
 int sfbx_test_ocp_to_nlp_api(void);

@@ -684,5 +684,38 @@ def ocp_nlp_host(spec, ops, dims, tables, bounds, x, lam=None, order=1, numerica
     return out
 
 
+def ocp_nlp_hess_host(spec, ops, dims, tables, bounds, x, lam, sigma, numerical=False, calls=1):
+    """OCPNLP::d2l_dx2(x, sigma, lam) of ocp_to_nlp.hpp on the script's mesh for a problem given as term tables, as ocp_nlp_host takes
+    it (sfbx_ocp_nlp_hess_host).  Returns dict n, m, stable, d2l (nnzH,), hcolptr, hrowind (the member's pattern) and hcolptr2, hrowind2
+    (meshfn::ocp_nlp_hess_pattern from the mesh's interval sizes).  LookupError for a (mesh type, dims) the harness does not carry."""
+    args, keep = _script_args(spec, ops, None)
+    dims = np.ascontiguousarray(dims, dtype=np.int32)
+    nx, nu, nq, ncr, nce = [int(v) for v in dims]
+    names = ("f", "g", "cr", "theta", "ce")
+    nterms = np.array([len(tables["coef." + k]) for k in names], dtype=np.int32)
+    terms = np.ascontiguousarray(np.concatenate([np.asarray(tables["terms." + k], dtype=np.int32).reshape(-1, 7) for k in names]), dtype=np.int32)
+    coef = np.ascontiguousarray(np.concatenate([np.asarray(tables["coef." + k], dtype=np.float64) for k in names]))
+    crl, cru, cel, ceu = [np.ascontiguousarray(np.concatenate([np.asarray(b, dtype=np.float64).ravel(), [0.0]])) for b in bounds]
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    n = len(x)
+    N = (n - 1 - nq - nx) // (nx + nu)
+    m = nx * N + nq + ncr * N + nce
+    lam = np.ascontiguousarray(lam, dtype=np.float64)
+    assert lam.shape == (m,), (lam.shape, m)
+    h_cap = n * (2 + nx + nu + nq + 2 * nx)
+    sizes = np.zeros(4, np.int32)
+    hcolptr, hrowind, hcolptr2, hrowind2, d2l = np.zeros(n + 1, np.int32), np.zeros(h_cap, np.int32), np.zeros(n + 1, np.int32), np.zeros(h_cap, np.int32), np.zeros(h_cap)
+    rc = lib().sfbx_ocp_nlp_hess_host(*args[:6], _p(dims), _p(nterms), _p(terms), _p(coef), _p(crl), _p(cru), _p(cel), _p(ceu), _p(x), _p(lam),
+                                      C.c_double(float(sigma)), 1 if numerical else 0, int(calls), _p(sizes), _p(hcolptr), _p(hrowind), _p(hcolptr2),
+                                      _p(hrowind2), _p(d2l))
+    if rc == -1:
+        raise LookupError("sfbx_ocp_nlp_hess_host: %d" % rc)
+    assert rc == 0, rc
+    assert (int(sizes[0]), int(sizes[1])) == (n, m), (sizes, n, m)
+    hnnz = int(sizes[2])
+    return {"n": n, "m": m, "stable": bool(sizes[3]), "d2l": d2l[:hnnz].copy(), "hcolptr": hcolptr, "hrowind": hrowind[:hnnz].copy(),
+            "hcolptr2": hcolptr2, "hrowind2": hrowind2[:hnnz].copy()}
+
+
 def test_ocp_to_nlp_api():
     return lib().sfbx_test_ocp_to_nlp_api()

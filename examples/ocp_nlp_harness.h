@@ -232,4 +232,44 @@ int ocp_nlp_run(const Mesh & mesh, const OcpData & d, const double * x, const do
   return 0;
 }
 
+/// d2l_dx2 of the data problem on `mesh` at (x, sigma, lambda), `calls` times: the pattern of the front's member, the
+/// pattern of meshfn::ocp_nlp_hess_pattern from the mesh's interval sizes (hcolptr2 / hrowind2), and the values.
+/// sizes: n, m, hnnz, 1 when the output array did not move between the calls.  Returns 0, or a negative code.
+struct OcpNlpHessOut {
+  int32_t *sizes, *hcolptr, *hrowind, *hcolptr2, *hrowind2;
+  double * d2l;
+};
+template<int NX, int NU, int NQ, int NCR, int NCE, sfn::diff::Type DT, class Mesh>
+int ocp_nlp_hess_run(const Mesh & mesh, const OcpData & d, const double * x, const double * lambda, double sigma, int calls, const OcpNlpHessOut & o)
+{
+  constexpr int nz = 1 + NX + NU, ne = 1 + 2 * NX + NQ;
+  if (!d.tab[0].valid(NX, nz) || !d.tab[1].valid(NQ, nz) || !d.tab[2].valid(NCR, nz) || !d.tab[3].valid(1, ne) || !d.tab[4].valid(NCE, ne)) return -9;
+  TermOcp<NX, NU, NQ, NCR, NCE> ocp{};
+  ocp.f.tab = d.tab[0], ocp.g.tab = d.tab[1], ocp.cr.tab = d.tab[2], ocp.theta.tab = d.tab[3], ocp.ce.tab = d.tab[4];
+  for (int r = 0; r < NCR; ++r) ocp.crl[r] = d.crl[r], ocp.cru[r] = d.cru[r];
+  for (int r = 0; r < NCE; ++r) ocp.cel[r] = d.cel[r], ocp.ceu[r] = d.ceu[r];
+  auto nlp = sfn::ocp_to_nlp<DT>(ocp, mesh);
+  const std::size_t n = nlp.n(), m = nlp.m();
+  const std::vector<double> xv(x, x + n), lv(lambda, lambda + m);
+  bool stable        = true;
+  const void * where = nullptr;
+  for (int c = 0; c < calls; ++c) {
+    const void * now = nlp.d2l_dx2(xv, sigma, lv).val.data();
+    if (c > 0 && now != where) stable = false;
+    where = now;
+  }
+  const sfn::MeshCsc & h = nlp.d2l_dx2(xv, sigma, lv);
+  if (o.hcolptr) std::copy(h.colptr.begin(), h.colptr.end(), o.hcolptr);
+  if (o.hrowind) std::copy(h.rowind.begin(), h.rowind.end(), o.hrowind);
+  if (o.d2l) std::copy(h.val.begin(), h.val.end(), o.d2l);
+  std::vector<int32_t> K(mesh.N_ivals());
+  for (std::size_t s = 0; s < K.size(); ++s) K[s] = (int32_t)mesh.N_colloc_ival(s);
+  const sfn::meshfn::OcpDims dm{NX, NU, NQ, NCR, NCE};
+  const int64_t nnz = sfn::meshfn::ocp_nlp_hess_pattern((int)K.size(), K.data(), dm, nullptr, nullptr, nullptr);
+  if (nnz != (int64_t)h.val.size() || nlp.hess_tables().nnz != nnz) return -8;
+  if (o.hcolptr2 && o.hrowind2) sfn::meshfn::ocp_nlp_hess_pattern((int)K.size(), K.data(), dm, o.hcolptr2, o.hrowind2, nullptr);
+  if (o.sizes) o.sizes[0] = (int32_t)n, o.sizes[1] = (int32_t)m, o.sizes[2] = (int32_t)nnz, o.sizes[3] = stable ? 1 : 0;
+  return 0;
+}
+
 }  // namespace sfbx

@@ -823,6 +823,45 @@ sfb_status sfb_ocp_nlp_batch_host(const sfb_mesh *mesh, const sfb_ocp_dims *dims
                                   const double *Fcr, const double *dFcr, const double *ce, const double *dce, double *g,
                                   double *dg_val);
 
+/* ------------------------------------------------------------------------------------------
+ * The Hessian of the Lagrangian of that NLP (OCPNLP::d2l_dx2 of ocp_to_nlp.hpp), the other half of each QP of a swarm
+ * SQP iteration:
+ *   H = sigma d2theta + ws (d2 dyn + d2 integrals + d2 running)(lambda) + sum_r lambda_ce[r] d2ce_r
+ * as values hess_val [batch][nnzH] over ONE upper-triangle CSC pattern per (mesh, dims), rows ascending within a column,
+ * every reserved entry stored -- the P_* form of a sparse QP plan, and the pattern of d2f_dx2 / d2g_dx2:
+ *   column tf {tf};  q_r {tf, q_0 .. q_r};  component j of x_0 {tf, q, x_00 .. x_0j};  of x_i {tf, x_i0 .. x_ij};
+ *   of x_N {tf, q, x_0, x_N0 .. x_Nj};  of u_i {tf, x_i, u_i0 .. u_ij}.
+ * The q-x0 and q-xf blocks of theta and ce sit at (q, x0) and (q, xf).
+ * Model-free, per agent (C order), with nz = 1 + nx + nu and ne = 1 + 2 nx + nq:
+ *   x [n], lambda [m], sigma (one double);
+ *   dFf [N][nx][nz], dFg [N][nq][nz], dFcr [N][ncr][nz]: the Jacobians sfb_ocp_nlp_batch takes (dFcr is accepted for
+ *     symmetry and not read: the running constraints are not time-scaled; it may be NULL);
+ *   HLf, HLg, HLcr [N][nz][nz]: the Hessian in (t, x, u) at node i of lambda_i . f, of lambda_q . g and of lambda_cr,i . cr,
+ *     that is the model Hessians CONTRACTED with that node's multipliers by the caller (the multipliers of the integral
+ *     rows are the same at every node).  Full square, row major; only r <= c is read.  Contracted because the
+ *     uncontracted [N][nx][nz][nz] is 9 GB for nx = 12, nu = 2 on 52 nodes at 8 192 agents, and a caller with automatic
+ *     differentiation gets the Hessian of lambda . f directly;
+ *   d2theta [ne][ne], and d2ce_l [ne][ne] = sum_r lambda_ce[r] d2ce_r, rows and columns (tf | x0 | xf | q); only the
+ *     part that is upper in the NLP's column order is read.
+ * A segment with nq, ncr or nce of zero takes NULL arrays.  One launch writes every output double once; every sum runs
+ * in one fixed order (nodes ascending; within a node f, g, cr; then theta, then ce), the order of the host front.
+ * Errors: the mesh, batch < 0, the dims, sizes beyond 32-bit indices, a NULL array with work to do; then
+ * SFB_ERR_NO_DEVICE for the compute entries.  batch == 0 writes nothing and returns SFB_OK with or without a device.
+ * ---------------------------------------------------------------------------------------- */
+/* colptr [n + 1], rowind [nnzH].  Both arrays NULL: only *nnz is set.  Host only. */
+sfb_status sfb_ocp_nlp_hess_pattern(const sfb_mesh *mesh, const sfb_ocp_dims *dims, int32_t *colptr, int32_t *rowind,
+                                    int64_t *nnz);
+/* Device pointers, asynchronous on `stream`. */
+sfb_status sfb_ocp_nlp_hess_batch(const sfb_mesh *mesh, const sfb_ocp_dims *dims, int64_t batch, const double *x,
+                                  const double *lambda, const double *sigma, const double *dFf, const double *HLf,
+                                  const double *dFg, const double *HLg, const double *dFcr, const double *HLcr,
+                                  const double *d2theta, const double *d2ce_l, double *hess_val, void *stream);
+/* Host-pointer variant (stages through device memory, synchronous). */
+sfb_status sfb_ocp_nlp_hess_batch_host(const sfb_mesh *mesh, const sfb_ocp_dims *dims, int64_t batch, const double *x,
+                                       const double *lambda, const double *sigma, const double *dFf, const double *HLf,
+                                       const double *dFg, const double *HLg, const double *dFcr, const double *HLcr,
+                                       const double *d2theta, const double *d2ce_l, double *hess_val);
+
 /*
  * Synthetic workload of the reference benchmark: random_qp(m, n, density, rng)
  * (benchmarks/bench_types.hpp:19-41) drawn `batch` times from ONE std::default_random_engine

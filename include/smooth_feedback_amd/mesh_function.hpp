@@ -5,7 +5,8 @@
 // One law: the arithmetic of every output entry of orders 0 and 1 is written once below (namespace meshfn, SFB_LIE_HD);
 // the host loops of this header and the batched kernels of smooth_feedback_amd/csrc/mesh.hip both call it, and both add
 // sums over nodes in node order.  The sparsity patterns are built once as well (meshfn::*_pattern: the host front, and
-// sfb_mesh_eval_pattern / sfb_mesh_dyn_pattern of the C-ABI).
+// sfb_mesh_eval_pattern / sfb_mesh_dyn_pattern of the C-ABI).  The same holds for the Lagrangian Hessian of the collocation
+// NLP (meshfn::ocp_nlp_hess_pattern / _value below): one law and one record builder for OCPNLP::d2l_dx2 and the kernel.
 //
 // dF is CSR in the form QuadraticProgramSparse::A_* has, d2F the upper triangle in CSC as P_*.  Derivatives with respect
 // to x and u are right-Jacobians.  mesh_eval and mesh_integrate take any state / input type of the Lie layer for
@@ -416,6 +417,194 @@ inline void ocp_nlp_bounds(const OcpDims & d, int64_t N, const OcpNlpNode * node
       for (int r = 0; r < d.ncr; ++r) out[cb[2] + i * d.ncr + r] = (ws * nodes[i].w) * cr[r];
     for (int r = 0; r < d.nce; ++r) out[cb[3] + r] = ce[r];
   }
+}
+
+// ---- the Hessian of the Lagrangian of that NLP (OCPNLP::d2l_dx2; sfb_ocp_nlp_hess_* of the C-ABI) ----
+//   H = sigma d2theta + ws (d2 dyn + d2 integrals + d2 running)(lambda) + sum_r lambda_ce[r] d2ce_r
+// as values over the upper-triangle CSC pattern d2f_dx2 / d2g_dx2 have (rows ascending in a column, every reserved entry
+// stored): the image of d2_pattern under the variable map without the t0 row and column, united with the
+// (tf | q | x_0 | x_N)^2 block; the q-x0 and q-xf blocks sit at (q, x0) and (q, xf).
+//
+// Model-free and CONTRACTED: per node the caller brings HL [nz][nz], the Hessian in z = (t | x | u) of lambda_i . f, of
+// lambda_q . g and of lambda_cr,i . cr (full square, row major, only r <= c read), and for the end d2theta [ne][ne] and
+// d2ce_l = sum_r lambda_ce[r] d2ce_r, columns (tf | x0 | xf | q).  The uncontracted [N][nx][nz][nz] would be 9 GB for the
+// MPC shape at 8 192 agents, and a caller with autodiff gets the Hessian of lambda . f directly.
+//
+// The node part restates detail::meshfn_d2_node on those contracted inputs: t0 is fixed, so of its lines only add(1, 1),
+// add(1, col) and the blocks apply; s = w h for dyn and the integrals (time-scaled), s = w for the running constraints,
+// and JL(c) = sum_j lambda_j dF(j, c) takes the place of lambda_j J(j, c).
+
+// (tf, tf), (tf, z_c) and (z_r, z_c) of one model at one node
+SFB_LIE_HD inline double d2_tftf(double w, double h, double tau, bool timescaled, double HL, double JL)
+{
+  const double s = timescaled ? w * h : w;
+  double v       = (s * tau * tau) * HL;
+  if (timescaled) v += (w * 2 * tau) * JL;
+  return v;
+}
+SFB_LIE_HD inline double d2_tfz(double w, double h, double tau, bool timescaled, double HL, double JL)
+{
+  const double s = timescaled ? w * h : w;
+  double v       = (s * tau) * HL;
+  if (timescaled) v += w * JL;
+  return v;
+}
+SFB_LIE_HD inline double d2_zz(double w, double h, bool timescaled, double HL) { return (timescaled ? w * h : w) * HL; }
+
+/// JL(c) = sum_j lambda_j dF(j, c), added in j order; dF points at column c of the node's first row.  Four rows are loaded at
+/// a time before their products are added, so a lane has four pairs of loads in flight; the order of the additions is j's.
+SFB_LIE_HD inline double d2_JL(int nf, const double * lam, const double * dF, int64_t nz)
+{
+  double JL = 0.0;
+  int j     = 0;
+  for (; j + 4 <= nf; j += 4) {
+    const double l0 = lam[j], l1 = lam[j + 1], l2 = lam[j + 2], l3 = lam[j + 3];
+    const double d0 = dF[j * nz], d1 = dF[(j + 1) * nz], d2 = dF[(j + 2) * nz], d3 = dF[(j + 3) * nz];
+    JL += l0 * d0;
+    JL += l1 * d1;
+    JL += l2 * d2;
+    JL += l3 * d3;
+  }
+  for (; j < nf; ++j) JL += lam[j] * dF[j * nz];
+  return JL;
+}
+
+/// One entry of the Hessian pattern, a gather: node >= 0 with the position (a, b), a <= b, in that node's z = (t | x_i | u_i)
+/// block (kHessNoNode: no node part; kHessAllNodes: every node, the (tf, tf) entry), and end = ea ne + eb, the position in
+/// the (tf | x0 | xf | q) block that is read (-1: no end part).
+struct OcpNlpHessItem {
+  int32_t node, a, b, end;
+};
+constexpr int32_t kHessNoNode = -1, kHessAllNodes = -2;
+
+/// CSC pattern (colptr [n + 1], rowind [nnzH]) and, with `items`, one record per entry.  NULL arrays: only the count.
+///   column tf {tf};  q_r {tf, q_0 .. q_r};  component j of x_0 {tf, q, x_00 .. x_0j};  of x_i {tf, x_i0 .. x_ij};
+///   of x_N {tf, q, x_0, x_N0 .. x_Nj};  of u_i {tf, x_i, u_i0 .. u_ij}
+inline int64_t ocp_nlp_hess_pattern(int nivals, const int32_t * K, const OcpDims & dm, int32_t * colptr, int32_t * rowind, OcpNlpHessItem * items)
+{
+  const int64_t nx = dm.nx, nu = dm.nu, nq = dm.nq, ne = 1 + 2 * nx + nq;
+  int64_t N = 0;
+  for (int s = 0; s < nivals; ++s) N += K[s];
+  const int64_t tri_x = nx * (nx + 1) / 2;
+  const int64_t nnz = 1 + nq + nq * (nq + 1) / 2 + nx * (1 + nq) + tri_x + (N - 1) * (nx + tri_x) + nx * (1 + nq + nx) + tri_x +
+                      N * (nu * (1 + nx) + nu * (nu + 1) / 2);
+  const bool pat = colptr && rowind;
+  if (!pat && !items) return nnz;
+  const int64_t qv = 1, xv = 1 + nq, uv = xv + nx * (N + 1), eq = 1 + 2 * nx;  // eq: q within the end block
+  int64_t e = 0, col = 0;
+  const auto put = [&](int64_t row, int64_t node, int64_t a, int64_t b, int64_t ea, int64_t eb) {
+    if (pat) rowind[e] = (int32_t)row;
+    if (items) items[e] = OcpNlpHessItem{(int32_t)node, (int32_t)a, (int32_t)b, ea < 0 ? -1 : (int32_t)(ea * ne + eb)};
+    ++e;
+  };
+  const auto begin_col = [&]() {
+    if (pat) colptr[col] = (int32_t)e;
+    ++col;
+  };
+  begin_col();
+  put(0, kHessAllNodes, 0, 0, 0, 0);
+  for (int64_t r = 0; r < nq; ++r) {
+    begin_col();
+    put(0, kHessNoNode, 0, 0, 0, eq + r);
+    for (int64_t s = 0; s <= r; ++s) put(qv + s, kHessNoNode, 0, 0, eq + s, eq + r);
+  }
+  for (int64_t i = 0; i <= N; ++i)
+    for (int64_t j = 0; j < nx; ++j) {
+      begin_col();
+      if (i == 0) {
+        put(0, 0, 0, 1 + j, 0, 1 + j);
+        for (int64_t s = 0; s < nq; ++s) put(qv + s, kHessNoNode, 0, 0, eq + s, 1 + j);
+        for (int64_t r = 0; r <= j; ++r) put(xv + r, 0, 1 + r, 1 + j, 1 + r, 1 + j);
+      } else if (i < N) {
+        put(0, i, 0, 1 + j, -1, 0);
+        for (int64_t r = 0; r <= j; ++r) put(xv + i * nx + r, i, 1 + r, 1 + j, -1, 0);
+      } else {
+        put(0, kHessNoNode, 0, 0, 0, 1 + nx + j);
+        for (int64_t s = 0; s < nq; ++s) put(qv + s, kHessNoNode, 0, 0, eq + s, 1 + nx + j);
+        for (int64_t r = 0; r < nx; ++r) put(xv + r, kHessNoNode, 0, 0, 1 + r, 1 + nx + j);
+        for (int64_t r = 0; r <= j; ++r) put(xv + N * nx + r, kHessNoNode, 0, 0, 1 + nx + r, 1 + nx + j);
+      }
+    }
+  for (int64_t i = 0; i < N; ++i)
+    for (int64_t j = 0; j < nu; ++j) {
+      begin_col();
+      put(0, i, 0, 1 + nx + j, -1, 0);
+      for (int64_t r = 0; r < nx; ++r) put(xv + i * nx + r, i, 1 + r, 1 + nx + j, -1, 0);
+      for (int64_t r = 0; r <= j; ++r) put(uv + i * nu + r, i, 1 + nx + r, 1 + nx + j, -1, 0);
+    }
+  if (pat) colptr[col] = (int32_t)e;
+  return nnz;
+}
+
+/// what every agent of one (mesh, dims) shares
+struct OcpNlpHessTables {
+  OcpDims d;
+  int32_t N;
+  int64_t m, nnz;  // rows of lambda; entries of the pattern
+  double ws;
+  const OcpNlpNode * nodes;      // [N]
+  const OcpNlpHessItem * items;  // [nnz]
+};
+/// one agent's arrays: x [n], lambda [m], sigma; dF [N][nf][nz] of f and g; HL [N][nz][nz] of f, g, cr; d2theta, d2ce_l [ne][ne].
+/// A segment of length zero takes NULL arrays.
+struct OcpNlpHessAgent {
+  const double *x, *lambda;
+  double sigma;
+  const double *dFf, *HLf, *dFg, *HLg, *HLcr, *d2theta, *d2ce_l;
+};
+/// a record with everything that does not depend on the agent looked up: the nodes [i0, i1), the offset of (a, b) in a
+/// node's HL, whether the entry is in the tf row, and the offset in the end blocks
+struct OcpNlpHessLane {
+  int32_t i0, i1, a, b, hl, end;
+};
+
+SFB_LIE_HD inline OcpNlpHessLane ocp_nlp_hess_decode(const OcpNlpHessTables & T, const OcpNlpHessItem it)
+{
+  const int32_t nz = 1 + T.d.nx + T.d.nu;
+  const int32_t i0 = it.node >= 0 ? it.node : 0, i1 = it.node >= 0 ? it.node + 1 : it.node == kHessAllNodes ? T.N : 0;
+  return OcpNlpHessLane{i0, i1, it.a, it.b, it.a * nz + it.b, it.end};
+}
+
+/// The value of one entry for one agent.  Fixed order of every sum: nodes ascending; within a node f, g, cr; the product
+/// with ws; then theta, then ce.  t0 = 0, so h = tf.
+SFB_LIE_HD inline double ocp_nlp_hess_value(const OcpNlpHessTables & T, const OcpNlpHessLane & L, const OcpNlpHessAgent & ag)
+{
+  const int nx = T.d.nx, nq = T.d.nq, ncr = T.d.ncr, nz = 1 + nx + T.d.nu;
+  const int64_t nzz = (int64_t)nz * nz;
+  const double h    = ag.x[0] - 0.0;
+  const bool tfrow  = L.a == 0;  // (tf, tf) and (tf, z_c) carry the JL term of the time-scaled models
+  double acc = 0.0;
+  for (int i = L.i0; i < L.i1; ++i) {
+    const OcpNlpNode nd = T.nodes[i];
+    {
+      const double HL = ag.HLf[i * nzz + L.hl];
+      const double JL = tfrow ? d2_JL(nx, ag.lambda + (int64_t)i * nx, ag.dFf + (int64_t)i * nx * nz + L.b, nz) : 0.0;
+      acc += !tfrow ? d2_zz(nd.w, h, true, HL) : L.b == 0 ? d2_tftf(nd.w, h, nd.tau, true, HL, JL) : d2_tfz(nd.w, h, nd.tau, true, HL, JL);
+    }
+    if (nq > 0) {
+      const double HL = ag.HLg[i * nzz + L.hl];
+      const double JL = tfrow ? d2_JL(nq, ag.lambda + (int64_t)T.N * nx, ag.dFg + (int64_t)i * nq * nz + L.b, nz) : 0.0;
+      acc += !tfrow ? d2_zz(nd.w, h, true, HL) : L.b == 0 ? d2_tftf(nd.w, h, nd.tau, true, HL, JL) : d2_tfz(nd.w, h, nd.tau, true, HL, JL);
+    }
+    if (ncr > 0) {
+      const double HL = ag.HLcr[i * nzz + L.hl];
+      acc += !tfrow ? d2_zz(nd.w, h, false, HL) : L.b == 0 ? d2_tftf(nd.w, h, nd.tau, false, HL, 0.0) : d2_tfz(nd.w, h, nd.tau, false, HL, 0.0);
+    }
+  }
+  double v = nlp_scaled(T.ws, acc);
+  if (L.end >= 0) {
+    v += nlp_end(ag.sigma * ag.d2theta[L.end]);
+    if (T.d.nce > 0) v += nlp_end(ag.d2ce_l[L.end]);
+  }
+  return v;
+}
+
+/// one agent on the host: the values [nnz] of sigma d2f + d2g(lambda) (the loop the kernel spreads over lanes)
+inline void ocp_nlp_hess_assemble(const OcpNlpHessTables & T, const OcpNlpHessAgent & agent, double sigma, double * hess_val)
+{
+  OcpNlpHessAgent a = agent;
+  a.sigma           = sigma;
+  for (int64_t e = 0; e < T.nnz; ++e) hess_val[e] = ocp_nlp_hess_value(T, ocp_nlp_hess_decode(T, T.items[e]), a);
 }
 
 }  // namespace meshfn

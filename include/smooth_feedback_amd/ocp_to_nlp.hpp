@@ -25,6 +25,9 @@
 //     side.  (detail::jac_end / hess_end of ocp_to_qp.hpp hold tf fixed and carry no q blocks, which the NLP needs.)
 //   * Ocp is any type with the members of OCP<...> of ocp_to_qp.hpp (that type asks every size to be positive; a problem
 //     without integrals or constraints brings a struct of its own).  X and U must be Rn<.>.
+// The Lagrangian Hessian sigma d2f + d2g(lambda) in one pass is d2l_dx2(x, sigma, lambda): the same pattern, its values written by
+// meshfn::ocp_nlp_hess_value entry by entry over the records of meshfn::ocp_nlp_hess_pattern -- the function and the records the
+// kernel behind sfb_ocp_nlp_hess_batch uses.  d2f_dx2 and d2g_dx2 keep their own code.
 // Left out: ocp_flatten / flatten_ocp, and any solver.
 #pragma once
 #include <algorithm>
@@ -218,6 +221,14 @@ public:
     Ff_.assign(N_ * Nx, 0.0), dFf_.assign(N_ * Nx * nz, 0.0), Fg_.assign(N_ * Nq, 0.0), dFg_.assign(N_ * Nq * nz, 0.0);
     Fcr_.assign(N_ * Ncr, 0.0), dFcr_.assign(N_ * Ncr * nz, 0.0), ce_.assign(Nce, 0.0), dce_.assign((std::size_t)Nce * ne, 0.0);
     X_.resize(N_ + 1), U_.resize(N_);
+    // the Lagrangian Hessian: the records of the model-free entry (the same pattern, built by the shared builder) and its contracted inputs
+    const int64_t nnzh = meshfn::ocp_nlp_hess_pattern((int)S, K.data(), dims_, nullptr, nullptr, nullptr);
+    d2l_.rows = d2l_.cols = (int32_t)n;
+    d2l_.colptr.assign(n + 1, 0), d2l_.rowind.assign((std::size_t)nnzh, 0), d2l_.val.assign((std::size_t)nnzh, 0.0);
+    hitems_.resize((std::size_t)nnzh);
+    meshfn::ocp_nlp_hess_pattern((int)S, K.data(), dims_, d2l_.colptr.data(), d2l_.rowind.data(), hitems_.data());
+    HLf_.assign(N_ * nz * nz, 0.0), HLg_.assign(Nq > 0 ? N_ * nz * nz : 0, 0.0), HLcr_.assign(Ncr > 0 ? N_ * nz * nz : 0, 0.0);
+    d2theta_.assign((std::size_t)ne * ne, 0.0), d2ce_l_.assign(Nce > 0 ? (std::size_t)ne * ne : 0, 0.0);
     dyn2_.lambda.assign(N_ * Nx, 0.0), int2_.lambda.assign(Nq, 0.0), cr2_.lambda.assign(N_ * Ncr, 0.0);
   }
 
@@ -232,6 +243,16 @@ public:
   meshfn::OcpNlpTables tables() const
   {
     return meshfn::OcpNlpTables{dims_, (int32_t)N_, cb_[4], (int64_t)dg_.val.size(), ws_, nodes_.data(), D_.data(), items_.data()};
+  }
+
+  /// the same for the Lagrangian Hessian (sfb_ocp_nlp_hess_batch), and one agent's arrays as d2l_dx2 last filled them
+  meshfn::OcpNlpHessTables hess_tables() const
+  {
+    return meshfn::OcpNlpHessTables{dims_, (int32_t)N_, cb_[4], (int64_t)d2l_.val.size(), ws_, nodes_.data(), hitems_.data()};
+  }
+  meshfn::OcpNlpHessAgent hess_agent(const std::vector<double> & x, const std::vector<double> & lambda, double sigma) const
+  {
+    return meshfn::OcpNlpHessAgent{x.data(), lambda.data(), sigma, dFf_.data(), HLf_.data(), dFg_.data(), HLg_.data(), HLcr_.data(), d2theta_.data(), d2ce_l_.data()};
   }
 
   double f(const std::vector<double> & x)
@@ -300,6 +321,38 @@ public:
     }
     return d2g_;
   }
+  /// sigma d2f_dx2 + d2g_dx2(lambda) in one pass: the model at the nodes (order 2) contracted with the multipliers into the
+  /// arrays of the model-free entry, then meshfn::ocp_nlp_hess_assemble -- the loop the kernel of sfb_ocp_nlp_hess_batch runs
+  const MeshCsc & d2l_dx2(const std::vector<double> & x, double sigma, const std::vector<double> & lambda)
+  {
+    states(x);
+    const double tf = x[0];
+    for (std::size_t i = 0; i < N_; ++i) {
+      const double t = 0.0 + (tf - 0.0) * nodes_[i].tau;
+      node_hessian<Nx>(ocp_.f, t, i, lambda.data() + cb_[0] + i * Nx, dFf_.data(), HLf_.data());
+      node_hessian<Nq>(ocp_.g, t, i, lambda.data() + cb_[1], dFg_.data(), HLg_.data());
+      node_hessian<Ncr>(ocp_.cr, t, i, lambda.data() + cb_[2] + i * Ncr, dFcr_.data(), HLcr_.data());
+    }
+    end_args(x);
+    {
+      EndEval<2, DT, 1, true, decltype(ocp_.theta), Nx, Nq> ev;
+      ev(ocp_.theta, tf, x0_, xf_, q_);
+      for (int a = 0; a < ne; ++a)
+        for (int b = 0; b < ne; ++b) d2theta_[(std::size_t)a * ne + b] = ev.H(a, b);
+    }
+    if constexpr (Nce > 0) {
+      EndEval<2, DT, Nce, false, decltype(ocp_.ce), Nx, Nq> ev;
+      ev(ocp_.ce, tf, x0_, xf_, q_);
+      for (int a = 0; a < ne; ++a)
+        for (int b = 0; b < ne; ++b) {
+          double acc = 0.0;
+          for (int r = 0; r < Nce; ++r) acc += lambda[(std::size_t)cb_[3] + r] * ev.H(a, r * ne + b);
+          d2ce_l_[(std::size_t)a * ne + b] = acc;
+        }
+    }
+    meshfn::ocp_nlp_hess_assemble(hess_tables(), hess_agent(x, lambda, sigma), sigma, d2l_.val.data());
+    return d2l_;
+  }
 
 private:
   void end_args(const std::vector<double> & x)
@@ -332,6 +385,23 @@ private:
         if constexpr (Deriv >= 1)
           for (int c = 0; c < nz; ++c) dF[(i * NF + r) * nz + c] = ev.J(r, c);
       }
+    }
+  }
+  /// node i of one model at order 2: its Jacobian into dF, and its Hessians contracted with lam [NF] into HL [i][nz][nz]
+  template<int NF, class Fn>
+  void node_hessian(Fn & fn, double t, std::size_t i, const double * lam, double * dF, double * HL)
+  {
+    if constexpr (NF > 0) {
+      MeshModelEval<2, DT, Fn, X, U> ev;
+      ev(fn, t, X_[i], U_[i]);
+      for (int r = 0; r < NF; ++r)
+        for (int c = 0; c < nz; ++c) dF[(i * NF + r) * nz + c] = ev.J(r, c);
+      for (int a = 0; a < nz; ++a)
+        for (int b = 0; b < nz; ++b) {
+          double acc = 0.0;
+          for (int r = 0; r < NF; ++r) acc += lam[r] * ev.H(a, r * nz + b);
+          HL[(i * nz + a) * nz + b] = acc;
+        }
     }
   }
   /// the model at the nodes (times tf tau_i) and the end constraint, into the arrays of the model-free entry
@@ -373,7 +443,9 @@ private:
   std::vector<meshfn::OcpNlpItem> items_;
   std::vector<double> xl_, xu_, gl_, gu_, g_;
   MeshCsr df_, dg_;
-  MeshCsc d2f_, d2g_, d2old_;
+  MeshCsc d2f_, d2g_, d2old_, d2l_;
+  std::vector<meshfn::OcpNlpHessItem> hitems_;
+  std::vector<double> HLf_, HLg_, HLcr_, d2theta_, d2ce_l_;
   std::vector<int> df_src_, d2_map_;
   int end_col_[ne], end_map_[ne][ne];
   std::vector<double> Ff_, dFf_, Fg_, dFg_, Fcr_, dFcr_, ce_, dce_;

@@ -168,6 +168,9 @@ def _load():
     L.sfb_ocp_nlp_bounds.argtypes = [mesh, dims] + [dp] * 8 + [C.POINTER(C.c_double)]
     L.sfb_ocp_nlp_batch_host.argtypes = [mesh, dims, i64] + [dp] * 11
     L.sfb_ocp_nlp_batch.argtypes = L.sfb_ocp_nlp_batch_host.argtypes + [vp]
+    L.sfb_ocp_nlp_hess_pattern.argtypes = [mesh, dims, vp, vp, C.POINTER(C.c_int64)]
+    L.sfb_ocp_nlp_hess_batch_host.argtypes = [mesh, dims, i64] + [dp] * 12
+    L.sfb_ocp_nlp_hess_batch.argtypes = L.sfb_ocp_nlp_hess_batch_host.argtypes + [vp]
     lay = C.POINTER(SfbMPCLayout)
     L.sfb_mpc_record_doubles.argtypes = [lay, i32]
     L.sfb_mpc_record_doubles.restype = i64

@@ -1,6 +1,7 @@
 // C-ABI for the batched ph-mesh path (include/sfb.h): resampling onto the degree-raised mesh, dynamics-error estimate,
 // the functions over the mesh (eval, integrate, dyn) with first derivatives and their sparsity patterns, and the
-// collocation NLP of an OCP over the mesh (structure, pattern, bounds, fused batched g / dg_dx).
+// collocation NLP of an OCP over the mesh (structure, pattern, bounds, fused batched g / dg_dx, and the pattern and fused
+// batched values of its Lagrangian Hessian).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -103,6 +104,10 @@ struct OcpNlpKey {
 struct OcpNlpEntry {
   sfb::DeviceBlock blk;
   L::meshfn::OcpNlpTables dev;
+  // the records of the Lagrangian Hessian, built by the first sfb_ocp_nlp_hess_batch of this (mesh, dims)
+  bool has_hess = false;
+  sfb::DeviceBlock hblk;
+  L::meshfn::OcpNlpHessTables hdev;
 };
 struct MeshCache {
   std::mutex mu;
@@ -309,9 +314,9 @@ sfb_status ocp_nlp_check(const sfb_mesh *mesh, const sfb_ocp_dims *d, int64_t ba
   return SFB_OK;
 }
 
-// launch(T) with the device tables of (mesh, dims), under the cache's lock
+// launch(entry) with the device tables of (mesh, dims), under the cache's lock; hess: with the Hessian's records as well
 template<class Launch>
-sfb_status with_device_ocpnlp(const sfb_mesh *mesh, const sfb_ocp_dims *d, Launch &&launch)
+sfb_status with_device_ocpnlp_entry(const sfb_mesh *mesh, const sfb_ocp_dims *d, bool hess, Launch &&launch)
 {
   namespace MF = L::meshfn;
   int device = 0;
@@ -353,7 +358,45 @@ sfb_status with_device_ocpnlp(const sfb_mesh *mesh, const sfb_ocp_dims *d, Launc
     ent.dev = MF::OcpNlpTables{dm, (int32_t)nodes.size(), cb[4], nnz, ws, dn, dD, di};
     it      = c.nlps.emplace(std::move(key), std::move(ent)).first;
   }
-  return launch(it->second.dev);
+  OcpNlpEntry &ent = it->second;
+  if (hess && !ent.has_hess) {
+    const MF::OcpDims dm = to_dims(d);
+    const int64_t nnzh   = MF::ocp_nlp_hess_pattern(mesh->nivals, mesh->K, dm, nullptr, nullptr, nullptr);
+    std::vector<MF::OcpNlpHessItem> items((size_t)nnzh);
+    MF::ocp_nlp_hess_pattern(mesh->nivals, mesh->K, dm, nullptr, nullptr, items.data());
+    sfb::Staging st;
+    MF::OcpNlpHessItem *di;
+    st.add(&di, items.size(), sfb::Staging::In, items.data());
+    const sfb_status rc = sfb::stage_per_call(st, ent.hblk);
+    if (rc != SFB_OK) return rc;
+    if ((e = st.upload()) != hipSuccess) return sfb::hip_fail(e, "ocp nlp hessian records upload");
+    ent.hdev     = MF::OcpNlpHessTables{dm, ent.dev.N, ent.dev.m, nnzh, ent.dev.ws, ent.dev.nodes, di};
+    ent.has_hess = true;
+  }
+  return launch(ent);
+}
+template<class Launch>
+sfb_status with_device_ocpnlp(const sfb_mesh *mesh, const sfb_ocp_dims *d, Launch &&launch)
+{
+  return with_device_ocpnlp_entry(mesh, d, false, [&](const OcpNlpEntry &ent) { return launch(ent.dev); });
+}
+
+// what the Hessian entries refuse, in the order of ocp_nlp_check: the mesh, the batch, the dims, sizes beyond 32-bit
+// indices, a NULL array with work to do (dFcr is not read: the running constraints are not time-scaled)
+sfb_status ocp_nlp_hess_check(const sfb_mesh *mesh, const sfb_ocp_dims *d, int64_t batch, const double *x, const double *lambda, const double *sigma,
+                              const double *dFf, const double *HLf, const double *dFg, const double *HLg, const double *HLcr, const double *d2theta,
+                              const double *d2ce_l, double *hess_val)
+{
+  const sfb_status st = ocp_dims_check(mesh, batch, d);
+  if (st != SFB_OK) return st;
+  const int64_t N = mesh_nodes(mesh), nz = 1 + (int64_t)d->nx + d->nu, ne = 1 + 2 * (int64_t)d->nx + d->nq;
+  if (N * nz * nz > 0x7fffffff || ne * ne > 0x7fffffff ||
+      L::meshfn::ocp_nlp_hess_pattern(mesh->nivals, mesh->K, to_dims(d), nullptr, nullptr, nullptr) > 0x7fffffff)
+    return sfb::fail(SFB_ERR_INVALID_ARG, "ocp nlp hessian: more entries than 32-bit indices hold");
+  if (batch > 0 && (!x || !lambda || !sigma || !dFf || !HLf || !d2theta || !hess_val || (d->nq > 0 && (!dFg || !HLg)) || (d->ncr > 0 && !HLcr) ||
+                    (d->nce > 0 && !d2ce_l)))
+    return sfb::fail(SFB_ERR_INVALID_ARG, "NULL array");
+  return SFB_OK;
 }
 
 // what the three mesh-function entries refuse, in this order: the mesh, the batch, negative sizes, an index range the
@@ -587,6 +630,80 @@ sfb_status sfb_ocp_nlp_batch_host(const sfb_mesh *mesh, const sfb_ocp_dims *dims
   if (st != SFB_OK) return st;
   if ((e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
   if (e != hipSuccess) return sfb::hip_fail(e, "sfb_ocp_nlp_batch_host");
+  return SFB_OK;
+}
+
+sfb_status sfb_ocp_nlp_hess_pattern(const sfb_mesh *mesh, const sfb_ocp_dims *dims, int32_t *colptr, int32_t *rowind, int64_t *nnz)
+{
+  const sfb_status st = ocp_dims_check(mesh, 0, dims);
+  if (st != SFB_OK) return st;
+  if ((colptr == nullptr) != (rowind == nullptr)) return sfb::fail(SFB_ERR_INVALID_ARG, "colptr and rowind: both or neither");
+  if (!colptr && !nnz) return sfb::fail(SFB_ERR_INVALID_ARG, "NULL array");
+  const int64_t n = L::meshfn::ocp_nlp_hess_pattern(mesh->nivals, mesh->K, to_dims(dims), nullptr, nullptr, nullptr);
+  if (n > 0x7fffffff) return sfb::fail(SFB_ERR_INVALID_ARG, "ocp nlp hessian: more entries than 32-bit indices hold");
+  if (colptr) L::meshfn::ocp_nlp_hess_pattern(mesh->nivals, mesh->K, to_dims(dims), colptr, rowind, nullptr);
+  if (nnz) *nnz = n;
+  return SFB_OK;
+}
+
+sfb_status sfb_ocp_nlp_hess_batch(const sfb_mesh *mesh, const sfb_ocp_dims *dims, int64_t batch, const double *x, const double *lambda,
+                                  const double *sigma, const double *dFf, const double *HLf, const double *dFg, const double *HLg, const double *dFcr,
+                                  const double *HLcr, const double *d2theta, const double *d2ce_l, double *hess_val, void *stream)
+{
+  (void)dFcr;
+  sfb_status st = ocp_nlp_hess_check(mesh, dims, batch, x, lambda, sigma, dFf, HLf, dFg, HLg, HLcr, d2theta, d2ce_l, hess_val);
+  if (st != SFB_OK) return st;
+  if (batch == 0) return SFB_OK;  // nothing to write: no device is asked for
+  st = sfb::require_device();
+  if (st != SFB_OK) return st;
+  return with_device_ocpnlp_entry(mesh, dims, true, [&](const OcpNlpEntry &ent) {
+    int64_t vb[5], cb[5];
+    L::meshfn::ocp_nlp_structure(ent.hdev.N, ent.hdev.d, vb, cb);
+    sfb::OcpNlpHessArgs a{};
+    a.T = ent.hdev; a.batch = batch; a.n = vb[4]; a.x = x; a.lambda = lambda; a.sigma = sigma; a.dFf = dFf; a.HLf = HLf; a.dFg = dFg; a.HLg = HLg;
+    a.HLcr = HLcr; a.d2theta = d2theta; a.d2ce_l = d2ce_l; a.hess = hess_val;
+    const hipError_t e = sfb::ocp_nlp_hess_launch(a, static_cast<hipStream_t>(stream));
+    return e != hipSuccess ? sfb::hip_fail(e, "ocp_nlp_hess_kernel launch") : SFB_OK;
+  });
+}
+
+sfb_status sfb_ocp_nlp_hess_batch_host(const sfb_mesh *mesh, const sfb_ocp_dims *dims, int64_t batch, const double *x, const double *lambda,
+                                       const double *sigma, const double *dFf, const double *HLf, const double *dFg, const double *HLg,
+                                       const double *dFcr, const double *HLcr, const double *d2theta, const double *d2ce_l, double *hess_val)
+{
+  (void)dFcr;
+  sfb_status st = ocp_nlp_hess_check(mesh, dims, batch, x, lambda, sigma, dFf, HLf, dFg, HLg, HLcr, d2theta, d2ce_l, hess_val);
+  if (st != SFB_OK) return st;
+  if (batch == 0) return SFB_OK;  // nothing to write: no device is asked for
+  st = sfb::require_device();
+  if (st != SFB_OK) return st;
+  const size_t B = (size_t)batch, N = (size_t)mesh_nodes(mesh), nx = (size_t)dims->nx, nq = (size_t)dims->nq, ncr = (size_t)dims->ncr,
+               nce = (size_t)dims->nce, nz = 1 + nx + (size_t)dims->nu, ne = 1 + 2 * nx + nq;
+  int64_t vb[5], cb[5];
+  L::meshfn::ocp_nlp_structure((int64_t)N, to_dims(dims), vb, cb);
+  const size_t nnz = (size_t)L::meshfn::ocp_nlp_hess_pattern(mesh->nivals, mesh->K, to_dims(dims), nullptr, nullptr, nullptr);
+  using S = sfb::Staging;
+  S s;
+  double *dx, *dl, *ds, *d1, *d2, *d3 = nullptr, *d4 = nullptr, *d5 = nullptr, *d6, *d7 = nullptr, *dh;
+  s.add(&dx, B * (size_t)vb[4], S::In, x);
+  s.add(&dl, B * (size_t)cb[4], S::In, lambda);
+  s.add(&ds, B, S::In, sigma);
+  s.add(&d1, B * N * nx * nz, S::In, dFf);
+  s.add(&d2, B * N * nz * nz, S::In, HLf);
+  if (nq) s.add(&d3, B * N * nq * nz, S::In, dFg);
+  if (nq) s.add(&d4, B * N * nz * nz, S::In, HLg);
+  if (ncr) s.add(&d5, B * N * nz * nz, S::In, HLcr);
+  s.add(&d6, B * ne * ne, S::In, d2theta);
+  if (nce) s.add(&d7, B * ne * ne, S::In, d2ce_l);
+  s.add(&dh, B * nnz, S::Out, hess_val);
+  sfb::DeviceBlock blk;
+  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
+  hipError_t e = s.upload();
+  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_ocp_nlp_hess_batch_host upload");
+  st = sfb_ocp_nlp_hess_batch(mesh, dims, batch, dx, dl, ds, d1, d2, d3, d4, nullptr, d5, d6, d7, dh, nullptr);
+  if (st != SFB_OK) return st;
+  if ((e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
+  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_ocp_nlp_hess_batch_host");
   return SFB_OK;
 }
 

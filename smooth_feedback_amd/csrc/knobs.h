@@ -21,6 +21,7 @@
 //   plan                          SFB_PLAN_UNITS     0: the supernodal engine of the numeric factorisation for every plan
 //                                 SFB_PLAN_DEBUG     1: print segments, units and sweep schedules of a plan
 //   collocation NLP               SFB_NLP_AGENTS     agents a lane of the fused assembly kernel walks with one decoded item (default 8)
+//                                 SFB_NLP_HESS_AGENTS  the same for the Lagrangian-Hessian kernel (default 4)
 //   MPC swarm                     SFB_MPC_TIMING     1: synchronise after every stage of a tick and print its wall time
 #pragma once
 

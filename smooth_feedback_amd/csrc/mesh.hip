@@ -27,6 +27,13 @@
 // one item, decodes it once (record -> node table -> mesh coefficient) and then walks kNlpAgents agents with it; the
 // lanes of a wave hold consecutive items, so every store instruction of a wave writes 512 contiguous bytes of one
 // agent.  Every value is meshfn::ocp_nlp_value, the function the host front calls.
+//
+// ocp_nlp_hess (sfb_ocp_nlp_hess_batch): the values of sigma d2f + d2g(lambda) over the upper-triangle CSC pattern, in the
+// same shape: a lane takes one of the nnzH records (a gather: a node and a position in its (t | x | u) block, a position
+// in the end block, or both), decodes it once and walks kNlpHessAgents agents; consecutive lanes hold consecutive entries
+// of one agent.  Every value is meshfn::ocp_nlp_hess_value with its fixed order of summation (nodes ascending; f, g, cr;
+// theta, ce): the tf-row lanes sum JL = sum_j lambda_j dF(j, c) themselves, and the (tf, tf) lane loops over all N nodes.
+// Every output double is written once; no LDS, plain loads and stores.
 #include "mesh_kernel.h"
 
 #include <cstdlib>
@@ -260,6 +267,26 @@ __global__ void __launch_bounds__(256) ocp_nlp_kernel(const OcpNlpArgs a)
   }
 }
 
+constexpr int kNlpHessAgents = 4;  // agents a lane walks with one decoded record (the knob SFB_NLP_HESS_AGENTS overrides it for A/B runs)
+
+__global__ void __launch_bounds__(256) ocp_nlp_hess_kernel(const OcpNlpHessArgs a)
+{
+  const MF::OcpNlpHessTables &T = a.T;
+  const int64_t b0 = (int64_t)blockIdx.x * a.agents;
+  const int64_t b1 = b0 + a.agents < a.batch ? b0 + a.agents : a.batch;
+  const int64_t N = T.N, nz = 1 + T.d.nx + T.d.nu, ne = 1 + 2 * T.d.nx + T.d.nq;
+  const int64_t sdF = N * nz, sHL = N * nz * nz, sE = ne * ne;
+  for (int64_t e = (int64_t)blockIdx.y * 256 + threadIdx.x; e < T.nnz; e += (int64_t)gridDim.y * 256) {
+    const MF::OcpNlpHessLane L = MF::ocp_nlp_hess_decode(T, T.items[e]);
+    double *out = a.hess + b0 * T.nnz + e;
+    for (int64_t b = b0; b < b1; ++b, out += T.nnz) {
+      const MF::OcpNlpHessAgent ag{a.x + b * a.n, a.lambda + b * T.m, a.sigma[b], a.dFf + b * sdF * T.d.nx, a.HLf + b * sHL,
+                                   a.dFg + b * sdF * T.d.nq, a.HLg + b * sHL, a.HLcr + b * sHL, a.d2theta + b * sE, a.d2ce_l + b * sE};
+      *out = MF::ocp_nlp_hess_value(T, L, ag);
+    }
+  }
+}
+
 template<class Kern>
 hipError_t lane_launch(Kern kern, const int64_t total, const MeshFnArgs &a, hipStream_t stream)
 {
@@ -306,6 +333,21 @@ hipError_t ocp_nlp_launch(const OcpNlpArgs &args, hipStream_t stream)
   const int64_t groups = (a.batch + a.agents - 1) / a.agents, chunks = (items + 255) / 256;
   if (groups > 0x7fffffff) return hipErrorInvalidValue;
   hipLaunchKernelGGL(ocp_nlp_kernel, dim3((unsigned)groups, (unsigned)(chunks < 65535 ? chunks : 65535)), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t ocp_nlp_hess_launch(const OcpNlpHessArgs &args, hipStream_t stream)
+{
+  OcpNlpHessArgs a = args;
+  a.agents         = kNlpHessAgents;
+  if (const char *k = knob("SFB_NLP_HESS_AGENTS")) {
+    const int v = std::atoi(k);
+    if (v >= 1 && v <= 1024) a.agents = v;
+  }
+  if (a.batch <= 0 || a.T.nnz <= 0) return hipSuccess;
+  const int64_t groups = (a.batch + a.agents - 1) / a.agents, chunks = (a.T.nnz + 255) / 256;
+  if (groups > 0x7fffffff) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ocp_nlp_hess_kernel, dim3((unsigned)groups, (unsigned)(chunks < 65535 ? chunks : 65535)), dim3(256), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -91,4 +91,14 @@ struct OcpNlpArgs {
 };
 hipError_t ocp_nlp_launch(const OcpNlpArgs &a, hipStream_t stream);
 
+// ---- its Lagrangian Hessian: the values of sigma d2f + d2g(lambda) [batch][nnzH] over the upper-triangle CSC pattern ----
+struct OcpNlpHessArgs {
+  smooth_feedback_amd::meshfn::OcpNlpHessTables T;  // device pointers: nodes and the decode records of one (mesh, dims)
+  int64_t batch, n;
+  int32_t agents;  // agents a lane walks with one decoded record (set by the launch)
+  const double *x, *lambda, *sigma, *dFf, *HLf, *dFg, *HLg, *HLcr, *d2theta, *d2ce_l;  // per agent; a segment of length zero: NULL
+  double *hess;
+};
+hipError_t ocp_nlp_hess_launch(const OcpNlpHessArgs &a, hipStream_t stream);
+
 }  // namespace sfb

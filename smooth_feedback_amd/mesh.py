@@ -13,7 +13,9 @@ out (variables [t0 | tf | x_0 .. x_N | u_0 .. u_{N-1}]).
 The collocation NLP of an optimal control problem over the mesh (ocp_to_nlp.hpp; sfb_ocp_nlp_*): dims = (nx, nu, nq, ncr, nce),
 variables [tf | q | x_0 .. x_N | u_0 .. u_{N-1}] with t0 = 0, constraints [dyn | integrals | running | end].  The model at the
 nodes (times tf tau_i) for f, g and cr and the end constraint with its Jacobian go in; g (B, m) and the CSR values of dg_dx
-(B, nnz) in the order of ocp_nlp_pattern come out of one fused launch."""
+(B, nnz) in the order of ocp_nlp_pattern come out of one fused launch.  The Hessian of its Lagrangian (sfb_ocp_nlp_hess_*):
+x, lambda, sigma, the Jacobians and the model Hessians contracted with the multipliers go in; the values (B, nnzH) of
+sigma d2f + d2g(lambda) over the upper-triangle CSC pattern of ocp_nlp_hess_pattern come out of one launch."""
 import ctypes as C
 
 import numpy as np
@@ -330,3 +332,69 @@ def ocp_nlp_batch(mesh, dims, x, Ff, dFf, Fg, dFg, Fcr, dFcr, ce, dce):
     tensors = [x] + [t if t is not None and t.numel() else None for t in (Ff, dFf, Fg, dFg, Fcr, dFcr, ce, dce)]
     _tensor_call(lambda mm, *a, stream: ocp_nlp_batch_device(mm, dims, B, *a, stream=stream), m, tensors, [g, dg])
     return g, dg
+
+
+def ocp_nlp_hess_pattern(mesh, dims):
+    """(colptr (n + 1,), rowind (nnzH,)) of the Lagrangian Hessian, upper triangle in CSC (sfb_ocp_nlp_hess_pattern; host only)"""
+    m, d = _mesh(mesh), _dims(dims)
+    nnz = C.c_int64()
+    _capi.check(_capi.lib.sfb_ocp_nlp_hess_pattern(C.byref(m.c), C.byref(d), None, None, C.byref(nnz)))
+    colptr, rowind = np.zeros(int(ocp_nlp_structure(m, dims)[0][4]) + 1, np.int32), np.zeros(nnz.value, np.int32)
+    _capi.check(_capi.lib.sfb_ocp_nlp_hess_pattern(C.byref(m.c), C.byref(d), _ptr(colptr), _ptr(rowind), C.byref(nnz)))
+    return colptr, rowind
+
+
+def _ocp_nlp_hess_shapes(m, d, B, n, rows):
+    """[(shape, the segment has work)] in the order of the entry's arguments"""
+    nz, ne, N = 1 + d.nx + d.nu, 1 + 2 * d.nx + d.nq, m.N
+    return [((B, n), True), ((B, rows), True), ((B,), True), ((B, N, d.nx, nz), True), ((B, N, nz, nz), True), ((B, N, d.nq, nz), d.nq > 0),
+            ((B, N, nz, nz), d.nq > 0), ((B, N, d.ncr, nz), False), ((B, N, nz, nz), d.ncr > 0), ((B, ne, ne), True), ((B, ne, ne), d.nce > 0)]
+
+
+def ocp_nlp_hess_batch_host(mesh, dims, x, lam, sigma, dFf, HLf, dFg, HLg, dFcr, HLcr, d2theta, d2ce_l):
+    """x (B, n), lam (B, m), sigma (B,) or a scalar; dFf (B, N, nx, nz), dFg (B, N, nq, nz), dFcr (not read); HLf, HLg, HLcr
+    (B, N, nz, nz): the model Hessians in (t, x, u) contracted with each node's multipliers; d2theta and d2ce_l = sum_r lambda_ce[r]
+    d2ce_r (B, ne, ne), rows and columns (tf | x0 | xf | q).  The arrays of a segment of length zero are not looked at (None will do).
+    -> the values (B, nnzH) of sigma d2f + d2g(lambda) in the order of ocp_nlp_hess_pattern (sfb_ocp_nlp_hess_batch_host)"""
+    m, d = _mesh(mesh), _dims(dims)
+    vb, cb = ocp_nlp_structure(m, dims)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] != vb[4]:
+        raise ValueError("x: expected shape (B, %d), got %r" % (vb[4], x.shape))
+    B = len(x)
+    sigma = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (B,)))
+    arrays = []
+    for k, (a, (shape, live)) in enumerate(zip([x, lam, sigma, dFf, HLf, dFg, HLg, dFcr, HLcr, d2theta, d2ce_l], _ocp_nlp_hess_shapes(m, d, B, int(vb[4]), int(cb[4])))):
+        if not live:
+            arrays.append(None)
+            continue
+        if a is None:
+            raise ValueError("input %d: expected shape %r, got None" % (k, shape))
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != shape:
+            raise ValueError("input %d: expected shape %r, got %r" % (k, shape, a.shape))
+        arrays.append(a)
+    hess = np.zeros((B, len(ocp_nlp_hess_pattern(m, dims)[1])))
+    ptr = lambda a: _ptr(a) if a is not None and a.size else None                   # noqa: E731
+    _capi.check(_capi.lib.sfb_ocp_nlp_hess_batch_host(C.byref(m.c), C.byref(d), B, *[ptr(a) for a in arrays], ptr(hess)))
+    return hess
+
+
+def ocp_nlp_hess_batch_device(mesh, dims, B, dx, dlam, dsigma, ddFf, dHLf, ddFg, dHLg, ddFcr, dHLcr, dd2theta, dd2ce_l, dhess, stream=0):
+    """sfb_ocp_nlp_hess_batch on device pointers (ints; a segment of length zero: 0), asynchronous on `stream`."""
+    m, d = _mesh(mesh), _dims(dims)
+    _capi.check(_capi.lib.sfb_ocp_nlp_hess_batch(C.byref(m.c), C.byref(d), int(B), dx or None, dlam or None, dsigma or None, ddFf or None, dHLf or None,
+                                                 ddFg or None, dHLg or None, ddFcr or None, dHLcr or None, dd2theta or None, dd2ce_l or None,
+                                                 dhess or None, stream or None))
+
+
+def ocp_nlp_hess_batch(mesh, dims, x, lam, sigma, dFf, HLf, dFg, HLg, dFcr, HLcr, d2theta, d2ce_l):
+    """ocp_nlp_hess_batch_host on torch tensors of the device, on the current stream (a segment of length zero: None; sigma (B,))"""
+    import torch
+    m, d = _mesh(mesh), _dims(dims)
+    B = x.shape[0]
+    hess = torch.empty((B, len(ocp_nlp_hess_pattern(m, dims)[1])), dtype=torch.float64, device=x.device)
+    live = [True, True, d.nq > 0, d.nq > 0, False, d.ncr > 0, True, d.nce > 0]
+    tensors = [x, lam, sigma] + [t if on and t is not None and t.numel() else None for t, on in zip((dFf, HLf, dFg, HLg, dFcr, HLcr, d2theta, d2ce_l), live)]
+    _tensor_call(lambda mm, *a, stream: ocp_nlp_hess_batch_device(mm, dims, B, *a, stream=stream), m, tensors, [hess])
+    return hess
