@@ -11,8 +11,21 @@
  *   - plain pointers and sizes only; no C++ / torch types;
  *   - every function returns an sfb_status (0 = ok); per-problem results use the reference's
  *     QPSolutionStatus values (qp.hpp:82-92) in `code[]`; the library never aborts or throws;
- *   - `*_batch` functions take DEVICE pointers and are asynchronous on `stream` (a hipStream_t,
- *     NULL = default stream); results are valid after the stream is synchronised;
+ *   - `*_batch` functions take DEVICE pointers and are asynchronous on `stream` (a hipStream_t, NULL = default stream,
+ *     non-blocking streams included): the call enqueues and returns.  The stream contract, as tested entry by entry on
+ *     non-blocking side streams (tests/test_stream_contract_gpu.py):
+ *       (1) every input is read behind `stream`: work enqueued on `stream` before the call -- a copy or a kernel that
+ *           produces P, q, a warm start, a launch order -- is seen by it, with no synchronisation in between;
+ *       (2) every output and every in-out buffer (EKF P, PID i_err / t_last, rollout states, trace tables) is complete for
+ *           whatever is enqueued on `stream` after the call, and for any stream that waits on an event recorded on `stream`
+ *           after it; the host needs a synchronisation of `stream` (not of the device) to read them.  Streams the library
+ *           owns (the polishers' stream of the sparse solve) are joined back into `stream` before the call's last launch;
+ *       (3) temporary memory is taken and released in stream order (hipMallocAsync / hipFreeAsync on `stream`), and
+ *           nothing is shared between two caller streams: calls on different streams with their own buffers (and
+ *           workspaces) may be in flight at once.
+ *     Blocking entries: none -- in its steady state no device-pointer entry waits on the host for `stream` to drain.  What may wait on the host is
+ *     first-use work (the upload of a plan's or a mesh's tables, creation of a stream's slot) and the fall-back to hipMalloc /
+ *     hipFree with a synchronisation of `stream` when the runtime refuses a stream-ordered allocation;
  *   - `*_batch_host` functions take HOST pointers, stage through device memory and are synchronous;
  *   - all floating point data is IEEE fp64; batch items are contiguous, batch-major;
  *   - there is NO CPU fallback: without a usable HIP device every compute call fails with

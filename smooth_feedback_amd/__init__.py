@@ -6,15 +6,18 @@ is the thin host-side mirror of the reference interface used by tests and bench.
 from . import _capi  # noqa: F401  (fails loudly if libsfb.so is missing)
 from ._capi import debug_set, debug_set_from  # noqa: F401  (debug knobs of the library: tests, A/B measurements)
 from .qp import (QPBatchSolution, QPSolution, QPSolutionStatus, QPSolver, QPSolverParams,  # noqa: F401
-                 QuadraticProgram, pack_colmajor, random_qp_batch, solve_qp, solve_qp_batch_device, solve_qp_batch_device_ws, Workspace,
+                 QuadraticProgram, pack_colmajor, random_qp_batch, solve_qp, solve_qp_batch_device, solve_qp_batch_device_phases,
+                 solve_qp_batch_device_trace, solve_qp_batch_device_ws, Workspace,
                  solve_qp_batch_host, QuadraticProgramSparse, SparseQPPlan, solve_qp_sparse,
                  solve_qp_tall_batch_device, solve_qp_tall_batch_host)
 
-from .ekf import (ekf_predict_batch_device, ekf_predict_batch_host, ekf_predict_stepper_batch_device,  # noqa: F401
+from .ekf import (ekf_predict_batch_device, ekf_predict_batch_host, ekf_predict_rk4_batch_device, ekf_predict_stepper_batch_device,  # noqa: F401
                   ekf_predict_update_batch_device, ekf_step_batch_host, ekf_update_batch_device)
-from .pid import (PIDGroup, pid_rollout_batch_device, pid_rollout_batch_host, pid_rollout_spline_batch_host,  # noqa: F401
+from .pid import (PIDGroup, pid_rollout_batch_device, pid_rollout_batch_host, pid_rollout_spline_batch_device,  # noqa: F401
+                  pid_rollout_spline_batch_host,
                   pid_step_batch_device, pid_step_batch_host)
-from .spline import spline_eval_batch_host, spline_fit_cubic_batch_host  # noqa: F401
+from .spline import (spline_eval_batch_device, spline_eval_batch_host, spline_fit_cubic_batch_device,  # noqa: F401
+                     spline_fit_cubic_batch_host)
 from .mesh import (PHMesh, mesh_dyn_batch, mesh_dyn_batch_device, mesh_dyn_batch_host, mesh_dyn_error_batch_device,  # noqa: F401
                    mesh_dyn_error_batch_host, mesh_dyn_pattern, mesh_eval_batch, mesh_eval_batch_device, mesh_eval_batch_host,
                    mesh_eval_pattern, mesh_integrate_batch, mesh_integrate_batch_device, mesh_integrate_batch_host,

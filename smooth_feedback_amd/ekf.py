@@ -93,3 +93,9 @@ def ekf_predict_batch_device(B, dof, dA, dQ, q_shared, ddt, dt_shared, dP, strea
 def ekf_update_batch_device(B, dof, ny, dH, dR, r_shared, dr, dP, ddelta, dinfo=0, stream=0):
     _capi.check(_capi.lib.sfb_ekf_update_batch(B, dof, ny, dH, dR, int(r_shared), dr, dP, ddelta, dinfo or None,
                                                stream or None))
+
+
+def ekf_predict_rk4_batch_device(B, dof, dA, dA_mid, dA_end, dQ, q_shared, ddt, dt_shared, dP, stream=0):
+    """sfb_ekf_predict_rk4_batch on device pointers (ints; dA_mid and dA_end 0: dA at every stage), asynchronous on `stream`."""
+    _capi.check(_capi.lib.sfb_ekf_predict_rk4_batch(B, dof, dA, dA_mid or None, dA_end or None, dQ, int(q_shared), ddt,
+                                                    int(dt_shared), dP, stream or None))

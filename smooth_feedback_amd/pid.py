@@ -172,3 +172,13 @@ def pid_rollout_batch_device(group, B, t0, dt, steps, dx, dv, dg_des0, dv_des, d
     _capi.check(_capi.lib.sfb_pid_rollout_batch(C.byref(g.c), B, float(t0), float(dt), int(steps), dx, dv, dg_des0, dv_des, int(des_shared), dkp,
                                                 dkd, dki, int(gains_shared), float(windup_limit), du_max or None, di_err, dt_last, du_last, dcost,
                                                 stream or None))
+
+
+def pid_rollout_spline_batch_device(group, B, t0, dt, steps, dx, dv, nknots, dtk, dgk, dV, spline_shared, dts0, dkp, dkd, dki, gains_shared,
+                                    windup_limit, du_max, di_err, dt_last, du_last, dcost, stream=0):
+    """sfb_pid_rollout_spline_batch on device pointers (ints; dts0 and du_max 0 / None: no time origins, no clamp), asynchronous
+    on `stream`."""
+    g = _group(group)
+    _capi.check(_capi.lib.sfb_pid_rollout_spline_batch(C.byref(g.c), B, float(t0), float(dt), int(steps), dx, dv, int(nknots), dtk, dgk, dV,
+                                                       int(spline_shared), dts0 or None, dkp, dkd, dki, int(gains_shared), float(windup_limit),
+                                                       du_max or None, di_err, dt_last, du_last, dcost, stream or None))

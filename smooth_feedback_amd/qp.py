@@ -165,6 +165,26 @@ def solve_qp_batch_device(B, n, m, dP, dq, dA, dl, du, dx, dy, dobj, diter, dcod
         dobj or None, diter or None, dcode, stream or None))
 
 
+def solve_qp_batch_device_trace(B, n, m, dP, dq, dA, dl, du, dx, dy, dobj, diter, dcode, dtrace, trace_rows, prm=None,
+                                dwarm_x=0, dwarm_y=0, stream=0):
+    """sfb_qp_dense_solve_batch_trace (n + m <= 128): solve_qp_batch_device with the reference's verbose table as data in
+    dtrace (B x trace_rows x 5 doubles, ITER preset to -1 by the caller)."""
+    cp = (prm or QPSolverParams()).to_c()
+    _capi.check(_capi.lib.sfb_qp_dense_solve_batch_trace(
+        C.byref(cp), B, n, m, dP, dq, dA, dl, du, dwarm_x or None, dwarm_y or None, dx, dy,
+        dobj or None, diter or None, dcode, dtrace, int(trace_rows), stream or None))
+
+
+def solve_qp_batch_device_phases(B, n, m, dP, dq, dA, dl, du, dx, dy, dobj, diter, dcode, dphase_us, prm=None,
+                                 dwarm_x=0, dwarm_y=0, stream=0, dtrace=0, trace_rows=0):
+    """sfb_qp_dense_solve_batch_phases (n + m <= 128): ... and the per-phase microseconds in the first B x 6 doubles of
+    dphase_us (B x 16 doubles: the rest is the kernel's scratch); dtrace 0: no table."""
+    cp = (prm or QPSolverParams()).to_c()
+    _capi.check(_capi.lib.sfb_qp_dense_solve_batch_phases(
+        C.byref(cp), B, n, m, dP, dq, dA, dl, du, dwarm_x or None, dwarm_y or None, dx, dy,
+        dobj or None, diter or None, dcode, dtrace or None, int(trace_rows), dphase_us, stream or None))
+
+
 TALL_MAX_N, TALL_MAX_M = 16, 1 << 20  # SFB_QP_DENSE_TALL_MAX_N / _M (include/sfb.h)
 
 
@@ -440,10 +460,23 @@ class SparseQPPlan:
         """sfb_sparse_qp_solve_batch[_ordered] on device pointers (ints); asynchronous on `stream`.
         dorder: int32 permutation (launch position -> item), 0 = natural order."""
         cp = (prm or QPSolverParams()).to_c()
+        if not dorder:
+            _capi.check(_capi.lib.sfb_sparse_qp_solve_batch(
+                self._h, C.byref(cp), B, dPx, dq, dAx, dl, du, dwarm_x or None, dwarm_y or None, dx, dy,
+                dobj or None, diter or None, dcode, dworkspace, stream or None))
+            return
         _capi.check(_capi.lib.sfb_sparse_qp_solve_batch_ordered(
             self._h, C.byref(cp), B, dPx, dq, dAx, dl, du, dwarm_x or None, dwarm_y or None, dx, dy,
-            dobj or None, diter or None, dcode, dworkspace, dorder or None, stream or None))
+            dobj or None, diter or None, dcode, dworkspace, dorder, stream or None))
 
+    def solve_batch_device_trace(self, B, dPx, dq, dAx, dl, du, dx, dy, dobj, diter, dcode, dworkspace, dtrace, trace_rows, prm=None,
+                                 dwarm_x=0, dwarm_y=0, stream=0):
+        """sfb_sparse_qp_solve_batch_trace on device pointers: the same solve through the TRACE instance of the kernel, with the
+        reference's verbose table as data in dtrace (B x trace_rows x 5 doubles, ITER preset to -1 by the caller)."""
+        cp = (prm or QPSolverParams()).to_c()
+        _capi.check(_capi.lib.sfb_sparse_qp_solve_batch_trace(
+            self._h, C.byref(cp), B, dPx, dq, dAx, dl, du, dwarm_x or None, dwarm_y or None, dx, dy,
+            dobj or None, diter or None, dcode, dworkspace, dtrace, int(trace_rows), stream or None))
 
     def solve_batch_device_phases(self, B, dPx, dq, dAx, dl, du, dx, dy, dobj, diter, dcode, dworkspace, dphase_us, prm=None,
                                   dwarm_x=0, dwarm_y=0, stream=0, dtrace=0, trace_rows=0):

@@ -45,3 +45,16 @@ def spline_eval_batch_host(group, tk, gk, V, t, ts0=None, batch=None):
     _capi.check(_capi.lib.sfb_spline_eval_batch_host(C.byref(g.c), B, K, _ptr(tk), _ptr(gk), _ptr(V), shared, _ptr(ts0) if ts0 is not None else None,
                                                      nt, _ptr(t), 1 if t.ndim == 1 else 0, *[_ptr(a) for a in out]))
     return out
+
+
+def spline_fit_cubic_batch_device(group, B, nknots, dtk, tk_shared, dgk, dV, stream=0):
+    """sfb_spline_fit_cubic_batch on device pointers (ints), asynchronous on `stream`."""
+    g = _group(group)
+    _capi.check(_capi.lib.sfb_spline_fit_cubic_batch(C.byref(g.c), int(B), int(nknots), dtk, int(tk_shared), dgk, dV, stream or None))
+
+
+def spline_eval_batch_device(group, B, nknots, dtk, dgk, dV, spline_shared, dts0, nt, dt, t_shared, dg, dvel, dacc, stream=0):
+    """sfb_spline_eval_batch on device pointers (ints; dts0 0 / None: no time origins), asynchronous on `stream`."""
+    g = _group(group)
+    _capi.check(_capi.lib.sfb_spline_eval_batch(C.byref(g.c), int(B), int(nknots), dtk, dgk, dV, int(spline_shared), dts0 or None, int(nt), dt,
+                                                int(t_shared), dg, dvel, dacc, stream or None))

@@ -38,6 +38,31 @@ def _compare(r, ref, tol=TOL):
     return bool(np.array_equal(r.primal, ref["x"]) and np.array_equal(r.dual, ref["y"]))
 
 
+def _compare_trace(tr, tref, B):
+    """the verbose table as data (B, rows, 5) against the oracle's: ITER, OBJ, PRI_RES, DUA_RES bit for bit on the used rows,
+    more than one check per item on average, checks at iter % 25 == 1 (:479), TIME (device clock, us) non-negative and growing"""
+    assert np.array_equal(tr[:, :, 0], tref[:, :, 0]), "check iterations differ"
+    used = tref[:, :, 0] >= 0
+    assert used.sum() > B and (tr[:, :, 0][used] % 25 == 1).all()
+    for col, name in ((1, "OBJ"), (2, "PRI_RES"), (3, "DUA_RES")):
+        a, b = tr[:, :, col][used], tref[:, :, col][used]
+        fin = np.isfinite(b)
+        assert np.array_equal(a[fin], b[fin]), (name, np.abs(a[fin] - b[fin]).max())
+    both = used[:, 1:] & used[:, :-1]
+    assert (tr[:, :, 4][used] >= 0).all() and (tr[:, 1:, 4][both] >= tr[:, :-1, 4][both]).all()  # TIME grows
+
+
+def _compare_full_pattern(r, ref, B):
+    """the full-pattern sparse route against the dense oracle (a fill-reducing order without pivoting): same codes, iteration
+    counts within one check interval, solutions to tolerance on the Optimal items with the same count -- at least half the batch"""
+    assert np.array_equal(r.code, ref["code"])
+    assert np.abs(r.iter.astype(np.int64) - ref["iter"].astype(np.int64)).max() <= 25
+    same = (r.iter == ref["iter"]) & (ref["code"] == 0)
+    assert same.sum() >= B // 2
+    scale = 1.0 + np.abs(ref["x"][same]).max(axis=1)
+    assert (np.abs(r.primal[same] - ref["x"][same]).max(axis=1) / scale).max() <= 1e-6
+
+
 @pytest.mark.parametrize("name", sorted(KNOWN_ANSWERS))
 def test_known_answers(sfb, oracle, name):
     """tests/test_qp.cpp:54-336 through the device path, incl. the hot start from own solution."""
@@ -354,21 +379,18 @@ def test_known_answers_padded_beyond_64(sfb, oracle):
 
 
 def test_sizes_beyond_the_big_dense_kernel_use_the_sparse_kernel(sfb, oracle, env_knob):
-    """n + m > 1024 (and, with SFB_QP_DENSE_BIG=0, everything above 64) runs on the shared-pattern sparse kernel with
+    """n + m > 1024 (and, with SFB_QP_DENSE_BIG=0, everything above 128) runs on the shared-pattern sparse kernel with
     a full pattern: a fill-reducing order without pivoting -- same codes, iteration counts within one check
-    interval, solutions to tolerance."""
+    interval, solutions to tolerance.  The knob does not move sizes up to 128 off the on-chip kernel (dense_solve_impl,
+    csrc/capi.hip): the (40, 30) of this test stays there and meets these bounds with room; the full-pattern route itself
+    is run at (40, 110) by tests/test_stream_contract_gpu.py."""
     env_knob(SFB_QP_DENSE_BIG=0)
     n, m, B = 40, 30, 16
     P, q, A, l, u = sfb.random_qp_batch(240, B, m, n, 0.6)
     prm = sfb.QPSolverParams(max_iter=4000)
     r = sfb.solve_qp_batch_host(P, q, A, l, u, prm)
     ref = oracle.qp_dense_solve_batch(P, q, A, l, u, params=_oracle_params(oracle, prm), nthreads=8)
-    assert np.array_equal(r.code, ref["code"])
-    assert np.abs(r.iter.astype(np.int64) - ref["iter"].astype(np.int64)).max() <= 25
-    same = (r.iter == ref["iter"]) & (ref["code"] == 0)
-    assert same.sum() >= B // 2
-    scale = 1.0 + np.abs(ref["x"][same]).max(axis=1)
-    assert (np.abs(r.primal[same] - ref["x"][same]).max(axis=1) / scale).max() <= 1e-6
+    _compare_full_pattern(r, ref, B)
 
 
 def test_cpp_front_solver_api_like_the_reference(sfb):
@@ -520,16 +542,7 @@ def test_verbose_table_as_data_matches_the_dense_oracle_trace(sfb, oracle, n, m,
     assert np.array_equal(r.objective, plain.objective, equal_nan=True)
     ref = oracle.qp_dense_solve_batch(P, q, A, l, u, params=_oracle_params(oracle, prm), nthreads=8, trace_rows=rows)
     assert np.array_equal(r.iter, ref["iter"]) and np.array_equal(r.code, ref["code"])
-    tr, tref = r.trace, ref["trace"]
-    assert np.array_equal(tr[:, :, 0], tref[:, :, 0]), "check iterations differ"
-    used = tref[:, :, 0] >= 0
-    assert used.sum() > B and (tr[:, :, 0][used] % 25 == 1).all()
-    for col, name in ((1, "OBJ"), (2, "PRI_RES"), (3, "DUA_RES")):
-        a, b = tr[:, :, col][used], tref[:, :, col][used]
-        fin = np.isfinite(b)
-        assert np.array_equal(a[fin], b[fin]), (name, np.abs(a[fin] - b[fin]).max())
-    both = used[:, 1:] & used[:, :-1]
-    assert (tr[:, :, 4][used] >= 0).all() and (tr[:, 1:, 4][both] >= tr[:, :-1, 4][both]).all()  # TIME grows
+    _compare_trace(r.trace, ref["trace"], B)
     # warm start and a table shorter than the number of checks
     w = sfb.solve_qp_batch_host(P, q, A, l, u, prm, warm_x=0.5 * plain.primal, warm_y=0.5 * plain.dual, trace_rows=2)
     wp = sfb.solve_qp_batch_host(P, q, A, l, u, prm, warm_x=0.5 * plain.primal, warm_y=0.5 * plain.dual)
