@@ -115,14 +115,20 @@ typedef struct sfb_qp_params {
  * iterations and reports SFB_QP_MAX_ITERATIONS (iter == cap) when it is hit. */
 #define SFB_QP_DEVICE_ITER_CAP 20000000
 
-/* Largest n+m the register/LDS-resident dense kernels handle (lane i owns KKT row i).  Larger dense problems are
- * accepted by the same entry points:
- *   n+m <= SFB_QP_DENSE_BIG_MAX_K: one QP per wavefront with the KKT matrix and its PIVOTED dense LDL'
- *     (Eigen::LDLT<.,Upper>, qp_solver.hpp:259,:428,:462) in a per-QP HBM workspace -- same arithmetic as the
- *     small kernels, bit-identical to the dense CPU restatement (the reference's ASIF example, n = 3, m = 203, and
- *     test, n = 4, m = 301, are of this size);
+/* The dense entry points accept every size; n+m decides which of four routes solves a batch (csrc/qp_dense_route.h):
+ *   n+m <= 32 and no max_time_ns: four QPs per wavefront, factor in registers; per-QP records and a queue in device memory;
+ *   otherwise n+m <= 128: one QP per wavefront, KKT matrix and factor on chip (registers / LDS).  No working memory
+ *     while the device holds the batch's waves at once; larger batches run time-sliced over per-QP records in
+ *     device memory;
+ *   otherwise n+m <= SFB_QP_DENSE_BIG_MAX_K: one QP per wavefront with the KKT matrix and its PIVOTED dense LDL'
+ *     (Eigen::LDLT<.,Upper>, qp_solver.hpp:259,:428,:462) in a per-QP HBM workspace (the reference's ASIF example,
+ *     n = 3, m = 203, and test, n = 4, m = 301, are of this size);
  *   beyond: the shared-pattern sparse kernel with a full pattern -- same ADMM and stopping tests on the same
- *     matrix entries, but a fill-reducing elimination order without pivoting: agreement to rounding only. */
+ *     matrix entries, but a fill-reducing elimination order without pivoting: agreement to rounding only.  Working
+ *     memory: A by rows and the sparse kernel's workspace.
+ * The first three share one arithmetic and are bit-identical to the dense CPU restatement, so the boundaries between
+ * them never show in a result.  SFB_QP_DENSE_MAX_K marks none of these boundaries any more (up to it the on-chip route
+ * keeps the factor in registers during the iterations); it stays defined for callers that refer to it. */
 #define SFB_QP_DENSE_MAX_K 64
 #define SFB_QP_DENSE_BIG_MAX_K 1024
 
@@ -178,9 +184,10 @@ void sfb_qp_params_default(sfb_qp_params *prm);
  * (l = +inf or u = -inf is the pre-check's PrimalInfeasible), and the kernels make of them exactly what the CPU restatement
  * does (tests/test_qp_dense_gpu.py, tests/test_qp_sparse_gpu.py::test_non_finite_*: codes, iteration counts and values up to
  * NaN payloads).  Shortcuts that rest on "0 times an entry is 0" (the first refinement round of polish) are covered by them.
- * Requires 1 <= n, 1 <= m (n+m > SFB_QP_DENSE_MAX_K: see there; n+m <= 19 198).
- * Working memory: sizes with n+m <= 32 (the four-per-wave kernel's records and queue) and n+m > SFB_QP_DENSE_MAX_K
- * (the factor in HBM) need device memory beyond the arguments.  This entry point takes it stream-ordered
+ * Requires 1 <= n, 1 <= m, n+m <= 19 198 (the four routes by n+m: see SFB_QP_DENSE_MAX_K above).
+ * Working memory: every route but the on-chip one (32 < n+m <= 128, or n+m <= 32 with max_time_ns, at a batch the device
+ * holds at once) needs device memory beyond the arguments -- the four-per-wave records and queue, the factor in HBM,
+ * the full-pattern sparse workspace, the records of a time-sliced on-chip launch.  This entry point takes it stream-ordered
  * (hipMallocAsync / hipFreeAsync) per call; sfb_qp_dense_solve_batch_ws below takes it from the caller instead.
  */
 sfb_status sfb_qp_dense_solve_batch(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,

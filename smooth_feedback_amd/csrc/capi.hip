@@ -18,6 +18,7 @@
 #include "../../include/sfb.h"
 #include "capi_common.h"
 #include "qp_dense_kernel.h"
+#include "stream_scratch.h"
 
 namespace sfb {
 
@@ -143,63 +144,44 @@ using sfb::hip_fail;
 using sfb::require_device;
 using sfb::make_kernel_params;
 
-sfb_status check_qp_args(const sfb_qp_params *prm, int64_t batch, int n, int m, const void *P, const void *q,
-                         const void *A, const void *l, const void *u, const void *wx, const void *wy, const void *x,
-                         const void *y, const void *code)
+using sfb::QpBatch;
+using sfb::DenseRoute;
+
+sfb_status check_qp_args(const sfb_qp_params *prm, int64_t batch, int n, int m, const QpBatch &g)
 {
   if (!prm) return fail(SFB_ERR_INVALID_ARG, "prm is NULL");
   if (batch < 0) return fail(SFB_ERR_INVALID_ARG, "batch < 0");
   if (n < 1 || m < 1) return fail(SFB_ERR_INVALID_ARG, "n and m must be >= 1");
-  if (batch > 0 && (!P || !q || !A || !l || !u || !x || !y || !code))
+  if (batch > 0 && (!g.P || !g.q || !g.A || !g.l || !g.u || !g.x || !g.y || !g.code))
     return fail(SFB_ERR_INVALID_ARG, "NULL problem / solution pointer");
-  if ((wx == nullptr) != (wy == nullptr))
+  if ((g.wx == nullptr) != (g.wy == nullptr))
     return fail(SFB_ERR_INVALID_ARG, "warm_x and warm_y must both be given or both be NULL");
   if (prm->max_iter > 0xFFFFFFFFll) return fail(SFB_ERR_INVALID_ARG, "max_iter exceeds uint32");
   if (batch > 0x7FFFFFFFll) return fail(SFB_ERR_UNSUPPORTED, "batch exceeds 2^31-1 per call");
   return SFB_OK;
 }
 
-// ---- dense problems with SFB_QP_DENSE_MAX_K < n+m <= 1024: the pivoted dense LDL' with the factor in HBM ----
-// (bit-identical to the dense oracle, i.e. to the reference's dense branch as far as that is pinned)
-sfb_status dense_big(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P, const double *q, const double *A,
-                     const double *l, const double *u, const double *wx, const double *wy, double *x, double *y, double *obj,
-                     uint32_t *iter, int32_t *code, hipStream_t stream, void *workspace)
+// what is left to report once the launches of a scratch user are on the stream: the error of the free, if any
+sfb_status released(sfb::StreamScratch &scratch)
 {
-  if (n + m <= sfb::kDenseMidMaxK) {  // up to 128: everything on chip, no workspace (qp_dense_mid.hip)
-    const sfb::DenseKernelParams kpm = make_kernel_params(prm, n, m);
-    const sfb::QpBatch gm{P, q, A, l, u, wx, wy, x, y, obj, iter, code};
-    const hipError_t em = sfb::qp_dense_mid_launch(kpm, batch, gm, stream, workspace);
-    if (em != hipSuccess) return hip_fail(em, "qp_dense_mid_kernel launch");
-    return SFB_OK;
-  }
-  const size_t bytes = (size_t)batch * sfb::qp_dense_big_ws_doubles(n, m) * sizeof(double);
-  char *buf          = static_cast<char *>(workspace);  // the caller's (sfb_workspace), or per call below
-  bool async_alloc   = true;
-  hipError_t e       = hipSuccess;
-  if (!workspace) {
-    e = hipMallocAsync(reinterpret_cast<void **>(&buf), bytes, stream);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      async_alloc = false;
-      e           = hipMalloc(reinterpret_cast<void **>(&buf), bytes);
-      if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-    }
-  }
-  const sfb::DenseKernelParams kp = make_kernel_params(prm, n, m);
-  const sfb::QpBatch g{P, q, A, l, u, wx, wy, x, y, obj, iter, code};
-  e = sfb::qp_dense_big_launch(kp, batch, g, reinterpret_cast<double *>(buf), stream);
-  if (workspace) {
-  } else if (async_alloc) {
-    (void)hipFreeAsync(buf, stream);
-  } else {
-    (void)hipStreamSynchronize(stream);
-    (void)hipFree(buf);
-  }
-  if (e != hipSuccess) return hip_fail(e, "qp_dense_big_kernel launch");
-  return SFB_OK;
+  const hipError_t e = scratch.release();
+  return e == hipSuccess ? SFB_OK : hip_fail(e, "freeing the call's working memory");
 }
 
-// ---- dense problems beyond that: the shared-pattern sparse kernel with a FULL pattern ----
+// ---- DenseRoute::Big: the pivoted dense LDL' with the factor in HBM ----
+// (bit-identical to the dense oracle, i.e. to the reference's dense branch as far as that is pinned)
+size_t dense_big_bytes(int64_t batch, int n, int m) { return (size_t)batch * sfb::qp_dense_big_ws_doubles(n, m) * sizeof(double); }
+
+sfb_status dense_big(const sfb_qp_params *prm, int64_t batch, int n, int m, const QpBatch &g, hipStream_t stream, void *workspace)
+{
+  sfb::StreamScratch scratch(workspace, dense_big_bytes(batch, n, m), stream);  // the caller's (sfb_workspace), or per call
+  if (scratch.error() != hipSuccess) return hip_fail(scratch.error(), "hipMalloc");
+  const hipError_t e = sfb::qp_dense_big_launch(make_kernel_params(prm, n, m), batch, g, static_cast<double *>(scratch.get()), stream);
+  if (e != hipSuccess) return hip_fail(e, "qp_dense_big_kernel launch");
+  return released(scratch);
+}
+
+// ---- DenseRoute::FullPattern: the shared-pattern sparse kernel with a FULL pattern ----
 // P (n x n, column-major, all entries stored) IS the CSC value array of a full pattern, so the stopping tests
 // and the objective see the same matrix entries in the same order as the dense kernels; only A has to be
 // re-laid out by rows.  What differs from the reference's dense solver is the factorisation order (fill-reducing
@@ -252,10 +234,7 @@ sfb_status dense_via_sparse_bytes(sfb_sparse_qp_plan *plan, int64_t batch, int n
   return SFB_OK;
 }
 
-sfb_status dense_via_sparse(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P, const double *q,
-                            const double *A, const double *l, const double *u, const double *wx, const double *wy,
-                            double *x, double *y, double *obj, uint32_t *iter, int32_t *code, hipStream_t stream,
-                            void *workspace)
+sfb_status dense_via_sparse(const sfb_qp_params *prm, int64_t batch, int n, int m, const QpBatch &g, hipStream_t stream, void *workspace)
 {
   sfb_sparse_qp_plan *plan = nullptr;
   sfb_status st            = dense_full_pattern_plan(n, m, &plan);
@@ -263,125 +242,151 @@ sfb_status dense_via_sparse(const sfb_qp_params *prm, int64_t batch, int n, int 
   size_t abytes = 0, bytes = 0;
   st = dense_via_sparse_bytes(plan, batch, n, m, &abytes, &bytes);
   if (st != SFB_OK) return st;
-  char *buf        = static_cast<char *>(workspace);
-  bool async_alloc = true;
-  hipError_t e     = hipSuccess;
-  if (!workspace) {
-    e = hipMallocAsync(reinterpret_cast<void **>(&buf), bytes, stream);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      async_alloc = false;
-      e           = hipMalloc(reinterpret_cast<void **>(&buf), bytes);
-      if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-    }
-  }
+  sfb::StreamScratch scratch(workspace, bytes, stream);
+  if (scratch.error() != hipSuccess) return hip_fail(scratch.error(), "hipMalloc");
+  char *buf  = static_cast<char *>(scratch.get());
   double *Ax = reinterpret_cast<double *>(buf);
-  hipLaunchKernelGGL(dense_A_to_rows_kernel, dim3((unsigned)batch), dim3(64), 0, stream, A, Ax, n, m);
-  if ((e = hipGetLastError()) != hipSuccess) {
-    if (workspace) {
-    } else if (async_alloc) (void)hipFreeAsync(buf, stream);
-    else (void)hipFree(buf);
-    return hip_fail(e, "dense_A_to_rows_kernel launch");
-  }
-  st = sfb_sparse_qp_solve_batch(plan, prm, batch, P, q, Ax, l, u, wx, wy, x, y, obj, iter, code, buf + abytes, stream);
-  if (workspace) {
-  } else if (async_alloc) {
-    (void)hipFreeAsync(buf, stream);
-  } else {
-    (void)hipStreamSynchronize(stream);
-    (void)hipFree(buf);
-  }
-  return st;
+  hipLaunchKernelGGL(dense_A_to_rows_kernel, dim3((unsigned)batch), dim3(64), 0, stream, g.A, Ax, n, m);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "dense_A_to_rows_kernel launch");
+  QpBatch rows = g;
+  rows.A       = Ax;
+  st = sfb::sparse_solve_batch(plan, prm, batch, rows, buf + abytes, nullptr, stream);
+  if (st != SFB_OK) return st;
+  return released(scratch);
 }
 
-// verbose, ONE dense problem with n + m <= 128 (device pointers of the call): the per-iteration table of qp_solver.hpp:490-501
-// from the TRACE instance of the on-chip dense kernel (qp_dense_mid.hip) -- the same pivoted arithmetic as the solve whose
-// results the caller receives (every dense route is bit-identical to the dense oracle), so the rows ARE that solve's iterates.
-// The closing summary (:550-565) follows from the same launch's phase stamps.  The re-solve runs WITHOUT the caller's time
+// ---- one table: a route's working memory and its launch, side by side ----
+// SFB_QP_DENSE_BIG=0 (A/B, tests): sizes beyond 128 through the un-pivoted sparse kernel as well
+DenseRoute dense_route_of(const sfb_qp_params *prm, int n, int m)
+{
+  const char *const bv = sfb::knob("SFB_QP_DENSE_BIG");
+  return sfb::dense_route(n + m, prm->max_time_ns >= 0, bv && bv[0] == '0');
+}
+
+// device memory the route's launch needs beyond its arguments (0: everything on chip)
+sfb_status dense_route_bytes(DenseRoute route, const sfb_qp_params *prm, int64_t batch, int n, int m, size_t *bytes)
+{
+  switch (route) {
+    case DenseRoute::Four: *bytes = sfb::qp_dense4_ws_bytes(n, m, batch); return SFB_OK;
+    case DenseRoute::Mid: *bytes = sfb::qp_dense_mid_ws_bytes(make_kernel_params(prm, n, m), batch); return SFB_OK;
+    case DenseRoute::Big: *bytes = dense_big_bytes(batch, n, m); return SFB_OK;
+    case DenseRoute::FullPattern: {
+      sfb_sparse_qp_plan *plan = nullptr;
+      const sfb_status st      = dense_full_pattern_plan(n, m, &plan);
+      if (st != SFB_OK) return st;
+      size_t abytes = 0;
+      return dense_via_sparse_bytes(plan, batch, n, m, &abytes, bytes);
+    }
+  }
+  return fail(SFB_ERR_UNSUPPORTED, "unknown dense route");
+}
+
+// workspace: at least dense_route_bytes of device memory, or nullptr = stream-ordered allocation inside the launch
+sfb_status dense_route_launch(DenseRoute route, const sfb_qp_params *prm, int64_t batch, int n, int m, const QpBatch &g, hipStream_t stream,
+                              void *workspace)
+{
+  hipError_t e = hipSuccess;
+  switch (route) {
+    case DenseRoute::Four:
+      e = sfb::qp_dense4_launch(make_kernel_params(prm, n, m), batch, g, stream, workspace);
+      return e == hipSuccess ? SFB_OK : hip_fail(e, "qp_dense4_kernel launch");
+    case DenseRoute::Mid:
+      e = sfb::qp_dense_mid_launch(make_kernel_params(prm, n, m), batch, g, stream, workspace);
+      return e == hipSuccess ? SFB_OK : hip_fail(e, "qp_dense_mid_kernel launch");
+    case DenseRoute::Big: return dense_big(prm, batch, n, m, g, stream, workspace);
+    case DenseRoute::FullPattern: return dense_via_sparse(prm, batch, n, m, g, stream, workspace);
+  }
+  return fail(SFB_ERR_UNSUPPORTED, "unknown dense route");
+}
+
+// ---- verbose, ONE dense problem (device pointers of the call): the per-iteration table of qp_solver.hpp:490-501 ----
+// Both tables come from a second, diagnostic solve of the same problem through a TRACE instance.  What they share: the
+// solve's results and its table behind whatever the caller declared in `a`, rows preset to ITER = -1, `run(g, dtrace)`,
+// then table, iter and code down.  The block stays in `t` so that the caller can fetch its extras.
+struct TableSolve {
+  sfb::DeviceBlock blk;
+  std::vector<double> tr;
+  uint32_t iter = 0;
+  int32_t code  = -1;
+};
+template<class Run>
+bool table_solve(sfb::DeviceArena &a, int n, int m, int rows, QpBatch g, TableSolve &t, Run run)
+{
+  double *dtr = nullptr;
+  a.add(&g.x, (size_t)n); a.add(&g.y, (size_t)m); a.add(&g.obj, 1); a.add(&dtr, (size_t)rows * 5); a.add(&g.iter, 1); a.add(&g.code, 1);
+  t.blk = sfb::DeviceBlock(a.bytes());
+  if (t.blk.error() != hipSuccess || !a.bind(t.blk.get())) return false;
+  t.tr.assign((size_t)rows * 5, 0.0);
+  for (int r = 0; r < rows; ++r) t.tr[(size_t)r * 5] = -1.0;
+  return sfb::upload(dtr, t.tr.data(), t.tr.size()) == hipSuccess && run(g, dtr) && hipDeviceSynchronize() == hipSuccess &&
+         sfb::download(t.tr.data(), dtr, t.tr.size()) == hipSuccess && sfb::download(&t.iter, g.iter, 1) == hipSuccess &&
+         sfb::download(&t.code, g.code, 1) == hipSuccess;
+}
+
+// n + m <= 128: the table from the TRACE instance of the on-chip dense kernel (qp_dense_mid.hip) -- the same pivoted arithmetic as
+// the solve whose results the caller receives (every dense route is bit-identical to the dense oracle), so the rows ARE that solve's
+// iterates.  The closing summary (:550-565) follows from the same launch's phase stamps.  The re-solve runs WITHOUT the caller's time
 // limit and for at most the iterations the returned solve took (real_iter, nullable): a solve that ended with MaxTime has
 // its table end at the same iteration instead of wherever the second run's clock would cut it.
-void dense_native_table(const sfb_qp_params *prm, int n, int m, const double *P, const double *q, const double *A, const double *l,
-                        const double *u, const double *wx, const double *wy, const uint32_t *real_iter, const int32_t *real_code)
+void dense_native_table(const sfb_qp_params *prm, int n, int m, const QpBatch &g, const uint32_t *real_iter, const int32_t *real_code)
 {
-  const int rows = sfb::verbose_table_rows(prm);
-  std::vector<double> tr((size_t)rows * 5, 0.0);
-  for (int r = 0; r < rows; ++r) tr[(size_t)r * 5] = -1.0;
-  char *buf = nullptr;
-  if (hipMalloc(reinterpret_cast<void **>(&buf), ((size_t)n + m + 2 + tr.size() + 16) * 8 + 16) != hipSuccess) { (void)hipGetLastError(); return; }
-  double *tx = reinterpret_cast<double *>(buf), *ty = tx + n, *tobj = ty + m, *dtr = tobj + 1, *dph = dtr + tr.size();
-  uint32_t *titer = reinterpret_cast<uint32_t *>(dph + 16);
-  int32_t *tcode  = reinterpret_cast<int32_t *>(titer + 1);
+  const int rows   = sfb::verbose_table_rows(prm);
   sfb_qp_params p2 = *prm;
   p2.verbose       = 0;
   p2.max_time_ns   = -1;
   if (real_iter != nullptr && (p2.max_iter < 0 || (int64_t)*real_iter < p2.max_iter)) p2.max_iter = (int64_t)*real_iter;
   const sfb::DenseKernelParams kp = make_kernel_params(&p2, n, m);
-  const sfb::QpBatch g{P, q, A, l, u, wx, wy, tx, ty, tobj, titer, tcode};
-  double ph[6] = {0, 0, 0, 0, 0, 0};
-  uint32_t it2 = 0;
-  int32_t code2 = -1;
+  sfb::DeviceArena a;
+  double *dph = nullptr, ph[6] = {0, 0, 0, 0, 0, 0};
+  a.add(&dph, 16);
+  TableSolve t;
   // (the phase scratch is zeroed: whatever stamps a kernel variant leaves out read as 0, not as what the allocation held)
-  const bool ok = hipMemcpy(dtr, tr.data(), tr.size() * 8, hipMemcpyHostToDevice) == hipSuccess && hipMemset(dph, 0, 16 * 8) == hipSuccess &&
-                  sfb::qp_dense_mid_trace_launch(kp, 1, g, nullptr, dtr, rows, dph) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
-                  hipMemcpy(tr.data(), dtr, tr.size() * 8, hipMemcpyDeviceToHost) == hipSuccess &&
-                  hipMemcpy(ph, dph, sizeof(ph), hipMemcpyDeviceToHost) == hipSuccess &&
-                  hipMemcpy(&it2, titer, 4, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(&code2, tcode, 4, hipMemcpyDeviceToHost) == hipSuccess;
-  (void)hipFree(buf);
-  if (ok) {
-    sfb::verbose_table("dense", n, m, tr.data(), rows, nullptr);
-    sfb::verbose_summary(real_code ? *real_code : code2, real_iter ? *real_iter : it2, ph);
-    if (real_iter != nullptr && real_code != nullptr && (it2 != *real_iter || (code2 != *real_code && *real_code != SFB_QP_MAX_TIME)))
-      std::printf("[sfb] verbose: NOTE the table's solve ended after %u iterations with code %d, the returned solve after %u iterations with code %d\n",
-                  it2, (int)code2, *real_iter, (int)*real_code);
-  } else (void)hipGetLastError();
+  const bool ok = table_solve(a, n, m, rows, g, t, [&](const QpBatch &gt, double *dtr) {
+                    return hipMemset(dph, 0, 16 * 8) == hipSuccess && sfb::qp_dense_mid_trace_launch(kp, 1, gt, nullptr, dtr, rows, dph) == hipSuccess;
+                  }) && sfb::download(ph, dph, 6) == hipSuccess;
+  if (!ok) { (void)hipGetLastError(); return; }
+  sfb::verbose_table("dense", n, m, t.tr.data(), rows, nullptr);
+  sfb::verbose_summary(real_code ? *real_code : t.code, real_iter ? *real_iter : t.iter, ph);
+  if (real_iter != nullptr && real_code != nullptr && (t.iter != *real_iter || (t.code != *real_code && *real_code != SFB_QP_MAX_TIME)))
+    std::printf("[sfb] verbose: NOTE the table's solve ended after %u iterations with code %d, the returned solve after %u iterations with code %d\n",
+                t.iter, (int)t.code, *real_iter, (int)*real_code);
 }
 
-// verbose, ONE dense problem (device pointers of the call): the per-iteration table of qp_solver.hpp:490-501.  The dense
-// kernels carry no trace; the table is produced by a second, diagnostic solve of the same problem through the sparse
-// kernel's TRACE instance on the full pattern -- no pivoting there, so its iterates equal the dense kernel's up to rounding
-// (the header says so); the results the caller receives are the dense kernel's.
-void dense_verbose_table(const sfb_qp_params *prm, int n, int m, const double *P, const double *q, const double *A, const double *l,
-                         const double *u, const double *wx, const double *wy, const uint32_t *real_iter, const int32_t *real_code)
+// beyond 128 the dense kernels carry no trace: the diagnostic solve goes through the sparse kernel's TRACE instance on the
+// full pattern -- no pivoting there, so its iterates equal the dense kernel's up to rounding (the header says so); the
+// results the caller receives are the dense kernel's.
+void dense_verbose_table(const sfb_qp_params *prm, int n, int m, const QpBatch &g, const uint32_t *real_iter, const int32_t *real_code)
 {
   sfb_sparse_qp_plan *plan = nullptr;
   if (dense_full_pattern_plan(n, m, &plan) != SFB_OK) return;
   size_t abytes = 0, bytes = 0;
   if (dense_via_sparse_bytes(plan, 1, n, m, &abytes, &bytes) != SFB_OK) return;
-  const int rows     = sfb::verbose_table_rows(prm);
-  const size_t extra = ((size_t)n + m + 2 + (size_t)rows * 5) * sizeof(double) + 16;
-  char *buf          = nullptr;
-  if (hipMalloc(reinterpret_cast<void **>(&buf), bytes + extra) != hipSuccess) { (void)hipGetLastError(); return; }
-  double *Ax = reinterpret_cast<double *>(buf), *tx = reinterpret_cast<double *>(buf + bytes), *ty = tx + n, *tobj = ty + m,
-         *dtrace = tobj + 1;
-  uint32_t *titer = reinterpret_cast<uint32_t *>(dtrace + (size_t)rows * 5);
-  int32_t *tcode  = reinterpret_cast<int32_t *>(titer + 1);
-  std::vector<double> tr((size_t)rows * 5, 0.0);
-  for (int r = 0; r < rows; ++r) tr[(size_t)r * 5] = -1.0;
+  const int rows   = sfb::verbose_table_rows(prm);
   sfb_qp_params p2 = *prm;
   p2.verbose       = 0;
-  bool ok = hipMemcpy(dtrace, tr.data(), tr.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
-  if (ok) {
-    hipLaunchKernelGGL(dense_A_to_rows_kernel, dim3(1), dim3(64), 0, nullptr, A, Ax, n, m);
-    ok = hipGetLastError() == hipSuccess &&
-         sfb_sparse_qp_solve_batch_trace(plan, &p2, 1, P, q, Ax, l, u, wx, wy, tx, ty, tobj, titer, tcode, buf + abytes, dtrace, rows,
-                                         nullptr) == SFB_OK &&
-         hipDeviceSynchronize() == hipSuccess && hipMemcpy(tr.data(), dtrace, tr.size() * 8, hipMemcpyDeviceToHost) == hipSuccess;
-  }
-  uint32_t titer_h = 0;
-  int32_t tcode_h  = -1;
-  if (ok) ok = hipMemcpy(&titer_h, titer, 4, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(&tcode_h, tcode, 4, hipMemcpyDeviceToHost) == hipSuccess;
-  (void)hipFree(buf);
+  sfb::DeviceArena a;
+  char *buf = nullptr;  // A by rows, then the sparse kernel's workspace
+  a.add(&buf, bytes);
+  TableSolve t;
+  const bool ok = table_solve(a, n, m, rows, g, t, [&](const QpBatch &gt, double *dtr) {
+    QpBatch gr = gt;
+    gr.A       = reinterpret_cast<double *>(buf);
+    hipLaunchKernelGGL(dense_A_to_rows_kernel, dim3(1), dim3(64), 0, nullptr, g.A, reinterpret_cast<double *>(buf), n, m);
+    return hipGetLastError() == hipSuccess && sfb::sparse_solve_batch(plan, &p2, 1, gr, buf + abytes, nullptr, nullptr, dtr, rows) == SFB_OK;
+  });
   if (!ok) {
     (void)hipGetLastError();
-    std::printf("[sfb] verbose: the diagnostic solve behind the per-iteration table failed (%s); no table\n", sfb_last_error());
+    if (t.blk.get() != nullptr)  // (without memory: no diagnostic solve, no table, no remark)
+      std::printf("[sfb] verbose: the diagnostic solve behind the per-iteration table failed (%s); no table\n", sfb_last_error());
     return;
   }
-  sfb::verbose_table("dense", n, m, tr.data(), rows,
+  sfb::verbose_table("dense", n, m, t.tr.data(), rows,
                      "(table: diagnostic solve without pivoting, equal to the solve's iterates up to rounding)");
   // the solve whose results the caller receives is the pivoted dense kernel's: say so when the two ended differently
-  if (real_iter != nullptr && real_code != nullptr && (titer_h != *real_iter || tcode_h != *real_code))
+  if (real_iter != nullptr && real_code != nullptr && (t.iter != *real_iter || t.code != *real_code))
     std::printf("[sfb] verbose: NOTE the table's diagnostic solve ended after %u iterations with code %d, the returned (pivoted) solve after "
-                "%u iterations with code %d\n", titer_h, (int)tcode_h, *real_iter, (int)*real_code);
+                "%u iterations with code %d\n", t.iter, (int)t.code, *real_iter, (int)*real_code);
 }
 
 }  // namespace
@@ -521,37 +526,21 @@ struct sfb_workspace {
   int device   = -1;
 };
 
-// device workspace one dense call needs beyond its arguments (0: the LDS-resident one-QP-per-wave kernels)
+// device workspace one dense call needs beyond its arguments (0: everything on chip)
 static sfb_status dense_workspace_need(const sfb_qp_params *prm, int64_t batch, int n, int m, size_t *need)
 {
-  const int k = n + m;
-  *need       = 0;
-  if (k > SFB_QP_DENSE_MAX_K) {
-    const char *const bv = sfb::knob("SFB_QP_DENSE_BIG");  // 0 (tests): sizes beyond 128 through the un-pivoted sparse kernel
-    const bool big_off   = bv && bv[0] == '0';
-    if (k <= sfb::kDenseMidMaxK || (k <= sfb::kDenseBigMaxK && !big_off)) {
-      *need = k <= sfb::kDenseMidMaxK ? sfb::qp_dense_mid_ws_bytes(make_kernel_params(prm, n, m), batch)
-                                      : (size_t)batch * sfb::qp_dense_big_ws_doubles(n, m) * sizeof(double);
-      return SFB_OK;
-    }
-    sfb_sparse_qp_plan *plan = nullptr;
-    sfb_status st            = dense_full_pattern_plan(n, m, &plan);
-    if (st != SFB_OK) return st;
-    size_t abytes = 0;
-    return dense_via_sparse_bytes(plan, batch, n, m, &abytes, need);
-  }
-  // (a time limit sends k <= 32 to the 32 < k <= 128 kernel, which implements it: the larger of the two needs covers both)
-  const size_t need_mid = sfb::qp_dense_mid_ws_bytes(make_kernel_params(prm, n, m), batch);
-  *need = k <= 32 ? std::max(sfb::qp_dense4_ws_bytes(n, m, batch), prm->max_time_ns >= 0 ? need_mid : (size_t)0) : need_mid;
-  return SFB_OK;
+  *need                  = 0;
+  const DenseRoute route = dense_route_of(prm, n, m);
+  const sfb_status st    = dense_route_bytes(route, prm, batch, n, m, need);
+  // the over-ask sfb.h documents: a time limit sends k <= 32 to Mid, which implements it; the larger of the Four and Mid needs is asked for
+  if (st == SFB_OK && route == DenseRoute::Mid && n + m <= sfb::kDenseFourMaxK) *need = std::max(*need, sfb::qp_dense4_ws_bytes(n, m, batch));
+  return st;
 }
 
-static sfb_status dense_solve_impl(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P, const double *q,
-                                   const double *A, const double *l, const double *u, const double *warm_x,
-                                   const double *warm_y, double *x, double *y, double *obj, uint32_t *iter, int32_t *code,
-                                   sfb_workspace *ws, bool ws_given, void *stream)
+static sfb_status dense_solve_impl(const sfb_qp_params *prm, int64_t batch, int n, int m, const QpBatch &g, sfb_workspace *ws, bool ws_given,
+                                   void *stream)
 {
-  sfb_status st = check_qp_args(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, code);
+  sfb_status st = check_qp_args(prm, batch, n, m, g);
   if (st != SFB_OK) return st;
   if (ws_given && !ws) return fail(SFB_ERR_INVALID_ARG, "workspace is NULL");
   st = require_device();
@@ -568,21 +557,7 @@ static sfb_status dense_solve_impl(const sfb_qp_params *prm, int64_t batch, int 
       return fail(SFB_ERR_INVALID_ARG, "workspace belongs to another device than the current one");
     wsmem = need ? ws->mem : nullptr;
   }
-  if (n + m > SFB_QP_DENSE_MAX_K) {
-    // SFB_QP_DENSE_BIG=0 (A/B, tests): route these sizes to the un-pivoted sparse kernel as well
-    const char *const bv = sfb::knob("SFB_QP_DENSE_BIG");
-    const bool big_off   = bv && bv[0] == '0';
-    if (n + m <= sfb::kDenseMidMaxK || (n + m <= sfb::kDenseBigMaxK && !big_off))
-      return dense_big(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code, static_cast<hipStream_t>(stream),
-                       wsmem);
-    return dense_via_sparse(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code,
-                            static_cast<hipStream_t>(stream), wsmem);
-  }
-  const sfb::DenseKernelParams kp = make_kernel_params(prm, n, m);
-  hipError_t e = sfb::qp_dense_launch(kp, batch, P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code,
-                                      static_cast<hipStream_t>(stream), wsmem);
-  if (e != hipSuccess) return hip_fail(e, "qp_dense_kernel launch");
-  return SFB_OK;
+  return dense_route_launch(dense_route_of(prm, n, m), prm, batch, n, m, g, static_cast<hipStream_t>(stream), wsmem);
 }
 
 sfb_status sfb_qp_dense_solve_batch(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
@@ -590,7 +565,17 @@ sfb_status sfb_qp_dense_solve_batch(const sfb_qp_params *prm, int64_t batch, int
                                     const double *warm_x, const double *warm_y, double *x, double *y, double *obj,
                                     uint32_t *iter, int32_t *code, void *stream)
 {
-  return dense_solve_impl(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code, nullptr, false, stream);
+  const QpBatch g{P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code};
+  return dense_solve_impl(prm, batch, n, m, g, nullptr, false, stream);
+}
+
+sfb_status sfb_qp_dense_solve_batch_ws(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
+                                       const double *q, const double *A, const double *l, const double *u,
+                                       const double *warm_x, const double *warm_y, double *x, double *y, double *obj,
+                                       uint32_t *iter, int32_t *code, sfb_workspace *workspace, void *stream)
+{
+  const QpBatch g{P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code};
+  return dense_solve_impl(prm, batch, n, m, g, workspace, true, stream);
 }
 
 // ---- tall problems through the reduced n x n system (qp_dense_tall.hip) ----
@@ -601,42 +586,51 @@ static sfb_status check_tall_size(int n, int m)
   return SFB_OK;
 }
 
-sfb_status sfb_qp_dense_tall_solve_batch(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
-                                         const double *q, const double *A, const double *l, const double *u,
-                                         const double *warm_x, const double *warm_y, double *x, double *y, double *obj,
-                                         uint32_t *iter, int32_t *code, void *stream)
+static sfb_status tall_solve_impl(const sfb_qp_params *prm, int64_t batch, int n, int m, const QpBatch &g, void *stream)
 {
-  sfb_status st = check_qp_args(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, code);
+  sfb_status st = check_qp_args(prm, batch, n, m, g);
   if (st != SFB_OK) return st;
   if ((st = check_tall_size(n, m)) != SFB_OK) return st;
   if ((st = require_device()) != SFB_OK) return st;
   if (batch == 0) return SFB_OK;
   const hipStream_t hs = static_cast<hipStream_t>(stream);
-  const sfb::DenseKernelParams kp = make_kernel_params(prm, n, m);
-  const sfb::QpBatch g{P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code};
   // rows that fit neither registers nor LDS keep sy and z in device memory: stream-ordered, like the big dense kernel's factor
-  const size_t bytes = sfb::qp_dense_tall_ws_bytes(n, m, batch);
-  char *buf          = nullptr;
-  bool async_alloc   = true;
-  hipError_t e       = hipSuccess;
-  if (bytes) {
-    e = hipMallocAsync(reinterpret_cast<void **>(&buf), bytes, hs);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      async_alloc = false;
-      e           = hipMalloc(reinterpret_cast<void **>(&buf), bytes);
-      if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-    }
-  }
-  e = sfb::qp_dense_tall_launch(kp, batch, g, hs, buf);
-  if (!bytes) {
-  } else if (async_alloc) {
-    (void)hipFreeAsync(buf, hs);
-  } else {
-    (void)hipStreamSynchronize(hs);
-    (void)hipFree(buf);
-  }
+  sfb::StreamScratch scratch(nullptr, sfb::qp_dense_tall_ws_bytes(n, m, batch), hs);
+  if (scratch.error() != hipSuccess) return hip_fail(scratch.error(), "hipMalloc");
+  const hipError_t e = sfb::qp_dense_tall_launch(make_kernel_params(prm, n, m), batch, g, hs, scratch.get());
   if (e != hipSuccess) return hip_fail(e, "qp_dense_tall_kernel launch");
+  return released(scratch);
+}
+
+sfb_status sfb_qp_dense_tall_solve_batch(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
+                                         const double *q, const double *A, const double *l, const double *u,
+                                         const double *warm_x, const double *warm_y, double *x, double *y, double *obj,
+                                         uint32_t *iter, int32_t *code, void *stream)
+{
+  const QpBatch g{P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code};
+  return tall_solve_impl(prm, batch, n, m, g, stream);
+}
+
+// ---- the per-iteration table and the phase times as data: always the TRACE instance of the on-chip kernel ----
+static sfb_status check_dense_trace(int n, int m, const double *trace, int32_t trace_rows)
+{
+  if (trace_rows < 0 || (trace_rows > 0 && !trace)) return fail(SFB_ERR_INVALID_ARG, "trace is NULL or trace_rows < 0");
+  if (n + m > sfb::kDenseMidMaxK) return fail(SFB_ERR_UNSUPPORTED, "the per-iteration table of a dense problem needs n + m <= 128");
+  return SFB_OK;
+}
+
+static sfb_status dense_phases_impl(const sfb_qp_params *prm, int64_t batch, int n, int m, const QpBatch &g, double *trace,
+                                    int32_t trace_rows, double *phase_us, void *stream)
+{
+  sfb_status st = check_qp_args(prm, batch, n, m, g);
+  if (st != SFB_OK) return st;
+  if ((st = check_dense_trace(n, m, trace, trace_rows)) != SFB_OK) return st;
+  st = require_device();
+  if (st != SFB_OK) return st;
+  if (batch == 0) return SFB_OK;
+  const hipError_t e = sfb::qp_dense_mid_trace_launch(make_kernel_params(prm, n, m), batch, g, static_cast<hipStream_t>(stream),
+                                                      trace_rows > 0 ? trace : nullptr, trace_rows, phase_us);
+  if (e != hipSuccess) return hip_fail(e, "qp_dense_mid_trace_kernel launch");
   return SFB_OK;
 }
 
@@ -645,7 +639,8 @@ sfb_status sfb_qp_dense_solve_batch_trace(const sfb_qp_params *prm, int64_t batc
                                           double *x, double *y, double *obj, uint32_t *iter, int32_t *code, double *trace,
                                           int32_t trace_rows, void *stream)
 {
-  return sfb_qp_dense_solve_batch_phases(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code, trace, trace_rows, nullptr, stream);
+  const QpBatch g{P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code};
+  return dense_phases_impl(prm, batch, n, m, g, trace, trace_rows, nullptr, stream);
 }
 
 sfb_status sfb_qp_dense_solve_batch_phases(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P, const double *q,
@@ -653,26 +648,8 @@ sfb_status sfb_qp_dense_solve_batch_phases(const sfb_qp_params *prm, int64_t bat
                                            double *x, double *y, double *obj, uint32_t *iter, int32_t *code, double *trace,
                                            int32_t trace_rows, double *phase_us, void *stream)
 {
-  sfb_status st = check_qp_args(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, code);
-  if (st != SFB_OK) return st;
-  if (trace_rows < 0 || (trace_rows > 0 && !trace)) return fail(SFB_ERR_INVALID_ARG, "trace is NULL or trace_rows < 0");
-  if (n + m > sfb::kDenseMidMaxK) return fail(SFB_ERR_UNSUPPORTED, "the per-iteration table of a dense problem needs n + m <= 128");
-  st = require_device();
-  if (st != SFB_OK) return st;
-  if (batch == 0) return SFB_OK;
-  const sfb::DenseKernelParams kp = make_kernel_params(prm, n, m);
-  const sfb::QpBatch g{P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code};
-  const hipError_t e = sfb::qp_dense_mid_trace_launch(kp, batch, g, static_cast<hipStream_t>(stream), trace_rows > 0 ? trace : nullptr, trace_rows, phase_us);
-  if (e != hipSuccess) return hip_fail(e, "qp_dense_mid_trace_kernel launch");
-  return SFB_OK;
-}
-
-sfb_status sfb_qp_dense_solve_batch_ws(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
-                                       const double *q, const double *A, const double *l, const double *u,
-                                       const double *warm_x, const double *warm_y, double *x, double *y, double *obj,
-                                       uint32_t *iter, int32_t *code, sfb_workspace *workspace, void *stream)
-{
-  return dense_solve_impl(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code, workspace, true, stream);
+  const QpBatch g{P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code};
+  return dense_phases_impl(prm, batch, n, m, g, trace, trace_rows, phase_us, stream);
 }
 
 sfb_status sfb_qp_dense_workspace_bytes(const sfb_qp_params *prm, int64_t batch, int n, int m, int64_t *bytes)
@@ -753,40 +730,6 @@ void host_stage_give(int dev, HostStage s)
 
 extern "C" {
 
-static sfb_status dense_host_multi_impl(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P, const double *q,
-                                        const double *A, const double *l, const double *u, const double *warm_x, const double *warm_y,
-                                        double *x, double *y, double *obj, uint32_t *iter, int32_t *code, const bool tall)
-{
-  sfb_status st = check_qp_args(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, code);
-  if (st != SFB_OK) return st;
-  if (tall && (st = check_tall_size(n, m)) != SFB_OK) return st;
-  if (batch == 0) return require_device();
-  const size_t N = (size_t)n, M = (size_t)m;
-  const auto solve = tall ? sfb_qp_dense_tall_solve_batch_host : sfb_qp_dense_solve_batch_host;
-  return sfb::run_sharded(batch, [&](int, int64_t b0, int64_t cnt) {
-    const size_t o = (size_t)b0;
-    return solve(prm, cnt, n, m, P + o * N * N, q + o * N, A + o * M * N, l + o * M, u + o * M,
-                 warm_x ? warm_x + o * N : nullptr, warm_y ? warm_y + o * M : nullptr, x + o * N,
-                 y + o * M, obj ? obj + o : nullptr, iter ? iter + o : nullptr, code + o);
-  });
-}
-
-sfb_status sfb_qp_dense_solve_batch_host_multi(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
-                                               const double *q, const double *A, const double *l, const double *u,
-                                               const double *warm_x, const double *warm_y, double *x, double *y,
-                                               double *obj, uint32_t *iter, int32_t *code)
-{
-  return dense_host_multi_impl(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code, false);
-}
-
-sfb_status sfb_qp_dense_tall_solve_batch_host_multi(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
-                                                    const double *q, const double *A, const double *l, const double *u,
-                                                    const double *warm_x, const double *warm_y, double *x, double *y,
-                                                    double *obj, uint32_t *iter, int32_t *code)
-{
-  return dense_host_multi_impl(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code, true);
-}
-
 void sfb_host_staging_trim(void)
 {
   std::map<int, HostStage> old;
@@ -799,29 +742,19 @@ void sfb_host_staging_trim(void)
 }
 
 // the host-pointer solve of both dense routes (tall: the reduced-KKT kernel) on the kept staging buffer
-static sfb_status dense_host_impl(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
-                                  const double *q, const double *A, const double *l, const double *u,
-                                  const double *warm_x, const double *warm_y, double *x, double *y,
-                                  double *obj, uint32_t *iter, int32_t *code, const bool tall)
+static sfb_status dense_host_impl(const sfb_qp_params *prm, int64_t batch, int n, int m, const QpBatch &h, const bool tall)
 {
-  sfb_status st = check_qp_args(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, code);
+  sfb_status st = check_qp_args(prm, batch, n, m, h);
   if (st != SFB_OK) return st;
   if (tall && (st = check_tall_size(n, m)) != SFB_OK) return st;
   st = require_device();
   if (st != SFB_OK) return st;
   if (batch == 0) return SFB_OK;
 
-  const size_t B = (size_t)batch, N = (size_t)n, M = (size_t)m, W = warm_x ? B : 0;
-  using S = sfb::Staging;
-  S s;
-  double *dP, *dq, *dA, *dl, *du, *dwx, *dwy, *dx, *dy, *dobj;
-  uint32_t *dit;
-  int32_t *dcode;
-  s.add(&dP, B * N * N, S::In, P); s.add(&dq, B * N, S::In, q); s.add(&dA, B * M * N, S::In, A);
-  s.add(&dl, B * M, S::In, l); s.add(&du, B * M, S::In, u);
-  s.add(&dwx, W * N, S::In, warm_x); s.add(&dwy, W * M, S::In, warm_y);
-  s.add(&dx, B * N, S::Out, x); s.add(&dy, B * M, S::Out, y); s.add(&dobj, B, S::Out, obj);
-  s.add(&dit, B, S::Out, iter); s.add(&dcode, B, S::Out, code);
+  const size_t B = (size_t)batch, N = (size_t)n, M = (size_t)m;
+  sfb::Staging s;
+  QpBatch d{};
+  sfb::stage_qp(s, B, N * N, N, M * N, M, h, d);
   // Staging memory of the host-pointer entry point: ONE buffer per device is kept between calls (ASIFilter solves one
   // small QP per tick through here, and a hipMalloc / hipFree pair per call would dominate its latency).  The lock is
   // held only while the buffer is taken or handed back: concurrent callers do not serialise -- one of them gets the
@@ -844,7 +777,6 @@ static sfb_status dense_host_impl(const sfb_qp_params *prm, int64_t batch, int n
     ~Return() { host_stage_give(dev, s); }
   } ret{devid, mine};
   if (!s.bind(mine.mem)) return fail(SFB_ERR_UNSUPPORTED, "more staged arrays than the table holds");
-  if (!warm_x) dwx = dwy = nullptr;
 
   st = SFB_OK;
   using clk = std::chrono::steady_clock;
@@ -853,8 +785,7 @@ static sfb_status dense_host_impl(const sfb_qp_params *prm, int64_t batch, int n
   auto tv1 = tv0, tv2 = tv0;
   if ((e = s.upload()) == hipSuccess) {
     tv1 = clk::now();
-    st = (tall ? sfb_qp_dense_tall_solve_batch : sfb_qp_dense_solve_batch)(prm, batch, n, m, dP, dq, dA, dl, du, dwx, dwy, dx, dy, dobj, dit,
-                                                                           dcode, nullptr);
+    st  = tall ? tall_solve_impl(prm, batch, n, m, d, nullptr) : dense_solve_impl(prm, batch, n, m, d, nullptr, false, nullptr);
     if (st == SFB_OK && (e = hipDeviceSynchronize()) == hipSuccess) {
       tv2 = clk::now();
       e   = s.download();
@@ -864,73 +795,52 @@ static sfb_status dense_host_impl(const sfb_qp_params *prm, int64_t batch, int n
   const auto tv3 = clk::now();
   if (st == SFB_OK && prm->verbose && batch == 1 && !tall) {  // (inputs still on the device)
     uint32_t it1 = 0;
-    const bool have_it = iter ? (it1 = iter[0], true) : hipMemcpy(&it1, dit, 4, hipMemcpyDeviceToHost) == hipSuccess;
-    if (n + m <= sfb::kDenseMidMaxK) dense_native_table(prm, n, m, dP, dq, dA, dl, du, dwx, dwy, have_it ? &it1 : nullptr, code);  // the solve's own iterates
-    else dense_verbose_table(prm, n, m, dP, dq, dA, dl, du, dwx, dwy, have_it ? &it1 : nullptr, code);
+    const bool have_it = h.iter ? (it1 = h.iter[0], true) : hipMemcpy(&it1, d.iter, 4, hipMemcpyDeviceToHost) == hipSuccess;
+    if (n + m <= sfb::kDenseMidMaxK) dense_native_table(prm, n, m, d, have_it ? &it1 : nullptr, h.code);  // the solve's own iterates
+    else dense_verbose_table(prm, n, m, d, have_it ? &it1 : nullptr, h.code);
   }
   if (st == SFB_OK && prm->verbose) {
     std::vector<uint32_t> itv;
-    if (!iter) {
+    if (!h.iter) {
       itv.resize(B);
-      if (hipMemcpy(itv.data(), dit, B * 4, hipMemcpyDeviceToHost) != hipSuccess) itv.clear();
+      if (hipMemcpy(itv.data(), d.iter, B * 4, hipMemcpyDeviceToHost) != hipSuccess) itv.clear();
     }
-    sfb::verbose_report(tall ? "tall dense QP batch (reduced KKT)" : "dense QP batch", batch, n, m, ms(tv0, tv1), ms(tv1, tv2), ms(tv2, tv3), code,
-                        iter ? iter : (itv.empty() ? nullptr : itv.data()));
+    sfb::verbose_report(tall ? "tall dense QP batch (reduced KKT)" : "dense QP batch", batch, n, m, ms(tv0, tv1), ms(tv1, tv2), ms(tv2, tv3), h.code,
+                        h.iter ? h.iter : (itv.empty() ? nullptr : itv.data()));
   }
   return st;
 }
 
-sfb_status sfb_qp_dense_solve_batch_host(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
-                                         const double *q, const double *A, const double *l, const double *u,
-                                         const double *warm_x, const double *warm_y, double *x, double *y,
-                                         double *obj, uint32_t *iter, int32_t *code)
+static sfb_status dense_host_multi_impl(const sfb_qp_params *prm, int64_t batch, int n, int m, const QpBatch &h, const bool tall)
 {
-  return dense_host_impl(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code, false);
-}
-
-sfb_status sfb_qp_dense_tall_solve_batch_host(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
-                                              const double *q, const double *A, const double *l, const double *u,
-                                              const double *warm_x, const double *warm_y, double *x, double *y,
-                                              double *obj, uint32_t *iter, int32_t *code)
-{
-  return dense_host_impl(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code, true);
-}
-
-sfb_status sfb_qp_dense_solve_batch_host_trace(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P, const double *q,
-                                               const double *A, const double *l, const double *u, const double *warm_x, const double *warm_y,
-                                               double *x, double *y, double *obj, uint32_t *iter, int32_t *code, double *trace,
-                                               int32_t trace_rows)
-{
-  return sfb_qp_dense_solve_batch_host_phases(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code, trace, trace_rows, nullptr);
-}
-
-sfb_status sfb_qp_dense_solve_batch_host_phases(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P, const double *q,
-                                                const double *A, const double *l, const double *u, const double *warm_x, const double *warm_y,
-                                                double *x, double *y, double *obj, uint32_t *iter, int32_t *code, double *trace,
-                                                int32_t trace_rows, double *phase_us)
-{
-  sfb_status st = check_qp_args(prm, batch, n, m, P, q, A, l, u, warm_x, warm_y, x, y, code);
+  sfb_status st = check_qp_args(prm, batch, n, m, h);
   if (st != SFB_OK) return st;
-  if (trace_rows < 0 || (trace_rows > 0 && !trace)) return fail(SFB_ERR_INVALID_ARG, "trace is NULL or trace_rows < 0");
-  if (n + m > sfb::kDenseMidMaxK) return fail(SFB_ERR_UNSUPPORTED, "the per-iteration table of a dense problem needs n + m <= 128");
+  if (tall && (st = check_tall_size(n, m)) != SFB_OK) return st;
+  if (batch == 0) return require_device();
+  const size_t N = (size_t)n, M = (size_t)m;
+  return sfb::run_sharded(batch, [&](int, int64_t b0, int64_t cnt) {
+    return dense_host_impl(prm, cnt, n, m, sfb::shard(h, (size_t)b0, N * N, N, M * N, M), tall);
+  });
+}
+
+static sfb_status dense_host_phases_impl(const sfb_qp_params *prm, int64_t batch, int n, int m, const QpBatch &h, double *trace,
+                                         int32_t trace_rows, double *phase_us)
+{
+  sfb_status st = check_qp_args(prm, batch, n, m, h);
+  if (st != SFB_OK) return st;
+  if ((st = check_dense_trace(n, m, trace, trace_rows)) != SFB_OK) return st;
   st = require_device();
   if (st != SFB_OK) return st;
   if (batch == 0) return SFB_OK;
-  const size_t B = (size_t)batch, N = (size_t)n, M = (size_t)m, W = warm_x ? B : 0, TR = B * (size_t)trace_rows * 5, PH = phase_us ? B * 16 : 0;
+  const size_t B = (size_t)batch, N = (size_t)n, M = (size_t)m, TR = B * (size_t)trace_rows * 5, PH = phase_us ? B * 16 : 0;
   using S = sfb::Staging;
   S s;
-  double *dP, *dq, *dA, *dl, *du, *dwx, *dwy, *dx, *dy, *dobj, *dtr, *dph;
-  uint32_t *dit;
-  int32_t *dcode;
-  s.add(&dP, B * N * N, S::In, P); s.add(&dq, B * N, S::In, q); s.add(&dA, B * M * N, S::In, A);
-  s.add(&dl, B * M, S::In, l); s.add(&du, B * M, S::In, u);
-  s.add(&dwx, W * N, S::In, warm_x); s.add(&dwy, W * M, S::In, warm_y);
-  s.add(&dx, B * N, S::Out, x); s.add(&dy, B * M, S::Out, y); s.add(&dobj, B, S::Out, obj);
+  double *dtr, *dph;
+  QpBatch d{};
   s.add(&dtr, TR, S::Out, trace); s.add(&dph, PH);  // (16 doubles of phase scratch per item, 6 of them come down)
-  s.add(&dit, B, S::Out, iter); s.add(&dcode, B, S::Out, code);
+  sfb::stage_qp(s, B, N * N, N, M * N, M, h, d);
   sfb::DeviceBlock blk;
   if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
-  if (!warm_x) dwx = dwy = nullptr;
   hipError_t e = s.upload();
   if (e == hipSuccess && TR) {  // unused rows keep ITER = -1
     std::vector<double> init(TR, 0.0);
@@ -939,13 +849,66 @@ sfb_status sfb_qp_dense_solve_batch_host_phases(const sfb_qp_params *prm, int64_
   }
   if (e == hipSuccess && PH) e = hipMemset(dph, 0, PH * 8);
   if (e == hipSuccess) {
-    st = sfb_qp_dense_solve_batch_phases(prm, batch, n, m, dP, dq, dA, dl, du, dwx, dwy, dx, dy, dobj, dit, dcode, TR ? dtr : nullptr, trace_rows,
-                                         PH ? dph : nullptr, nullptr);
+    st = dense_phases_impl(prm, batch, n, m, d, TR ? dtr : nullptr, trace_rows, PH ? dph : nullptr, nullptr);
     if (st == SFB_OK && (e = hipDeviceSynchronize()) == hipSuccess && (e = s.download()) == hipSuccess && PH)
       e = sfb::download(phase_us, dph, B * 6);
   }
   if (e != hipSuccess) return hip_fail(e, "sfb_qp_dense_solve_batch_host_trace");
   return st;
+}
+
+sfb_status sfb_qp_dense_solve_batch_host(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
+                                         const double *q, const double *A, const double *l, const double *u,
+                                         const double *warm_x, const double *warm_y, double *x, double *y,
+                                         double *obj, uint32_t *iter, int32_t *code)
+{
+  const QpBatch h{P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code};
+  return dense_host_impl(prm, batch, n, m, h, false);
+}
+
+sfb_status sfb_qp_dense_tall_solve_batch_host(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
+                                              const double *q, const double *A, const double *l, const double *u,
+                                              const double *warm_x, const double *warm_y, double *x, double *y,
+                                              double *obj, uint32_t *iter, int32_t *code)
+{
+  const QpBatch h{P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code};
+  return dense_host_impl(prm, batch, n, m, h, true);
+}
+
+sfb_status sfb_qp_dense_solve_batch_host_multi(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
+                                               const double *q, const double *A, const double *l, const double *u,
+                                               const double *warm_x, const double *warm_y, double *x, double *y,
+                                               double *obj, uint32_t *iter, int32_t *code)
+{
+  const QpBatch h{P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code};
+  return dense_host_multi_impl(prm, batch, n, m, h, false);
+}
+
+sfb_status sfb_qp_dense_tall_solve_batch_host_multi(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,
+                                                    const double *q, const double *A, const double *l, const double *u,
+                                                    const double *warm_x, const double *warm_y, double *x, double *y,
+                                                    double *obj, uint32_t *iter, int32_t *code)
+{
+  const QpBatch h{P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code};
+  return dense_host_multi_impl(prm, batch, n, m, h, true);
+}
+
+sfb_status sfb_qp_dense_solve_batch_host_trace(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P, const double *q,
+                                               const double *A, const double *l, const double *u, const double *warm_x, const double *warm_y,
+                                               double *x, double *y, double *obj, uint32_t *iter, int32_t *code, double *trace,
+                                               int32_t trace_rows)
+{
+  const QpBatch h{P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code};
+  return dense_host_phases_impl(prm, batch, n, m, h, trace, trace_rows, nullptr);
+}
+
+sfb_status sfb_qp_dense_solve_batch_host_phases(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P, const double *q,
+                                                const double *A, const double *l, const double *u, const double *warm_x, const double *warm_y,
+                                                double *x, double *y, double *obj, uint32_t *iter, int32_t *code, double *trace,
+                                                int32_t trace_rows, double *phase_us)
+{
+  const QpBatch h{P, q, A, l, u, warm_x, warm_y, x, y, obj, iter, code};
+  return dense_host_phases_impl(prm, batch, n, m, h, trace, trace_rows, phase_us);
 }
 
 }  // extern "C"

@@ -67,6 +67,7 @@ private:
   smooth_feedback_amd::detail::DeviceArena arena_;
   Host host_[smooth_feedback_amd::detail::DeviceArena::kCapacity];
 };
+using smooth_feedback_amd::detail::DeviceArena;
 using smooth_feedback_amd::detail::DeviceBlock;
 using smooth_feedback_amd::detail::download;
 using smooth_feedback_amd::detail::upload;
@@ -78,8 +79,36 @@ inline sfb_status stage_per_call(Staging &s, DeviceBlock &blk)
   return s.bind(blk.get()) ? SFB_OK : fail(SFB_ERR_UNSUPPORTED, "more staged arrays than the table holds");
 }
 
+
+// The arrays of a QP batch as every host-pointer entry stages them, after whatever the caller declared before: the seven
+// inputs, then x, y, obj, iter, code.  sizeP / sizeA: values of P / A per item (dense: n * n and m * n; sparse: the
+// pattern's counts, P / A carry Px / Ax).  Without a warm start dev.wx / dev.wy stay NULL and take no space.
+inline void stage_qp(Staging &s, size_t B, size_t sizeP, size_t n, size_t sizeA, size_t m, const QpBatch &host, QpBatch &dev)
+{
+  using S = Staging;
+  s.add(&dev.P, B * sizeP, S::In, host.P); s.add(&dev.q, B * n, S::In, host.q); s.add(&dev.A, B * sizeA, S::In, host.A);
+  s.add(&dev.l, B * m, S::In, host.l); s.add(&dev.u, B * m, S::In, host.u);
+  dev.wx = dev.wy = nullptr;
+  if (host.wx) { s.add(&dev.wx, B * n, S::In, host.wx); s.add(&dev.wy, B * m, S::In, host.wy); }
+  s.add(&dev.x, B * n, S::Out, host.x); s.add(&dev.y, B * m, S::Out, host.y); s.add(&dev.obj, B, S::Out, host.obj);
+  s.add(&dev.iter, B, S::Out, host.iter); s.add(&dev.code, B, S::Out, host.code);
+}
+
+// items [b0, ...) of a batch, for the shards of the *_multi entries; NULL stays NULL
+inline QpBatch shard(const QpBatch &g, size_t b0, size_t sizeP, size_t n, size_t sizeA, size_t m)
+{
+  const auto at = [b0](auto *p, size_t stride) { return p ? p + b0 * stride : nullptr; };
+  return {at(g.P, sizeP), at(g.q, n), at(g.A, sizeA), at(g.l, m), at(g.u, m), at(g.wx, n), at(g.wy, m),
+          at(g.x, n), at(g.y, m), at(g.obj, 1), at(g.iter, 1), at(g.code, 1)};
+}
+
 struct SparsePlanHost;
 const SparsePlanHost &plan_host(const sfb_sparse_qp_plan *plan);  // capi_sparse.hip: the pattern the kernel works on
 const SparsePlanHost &plan_io(const sfb_sparse_qp_plan *plan);    // the caller's pattern (== plan_host unless pruned)
+// capi_sparse.hip: every device-pointer solve of the sparse path (g.P / g.A: the value arrays Px / Ax); order, trace
+// ([batch][trace_rows][5]) and phase_us are optional
+sfb_status sparse_solve_batch(sfb_sparse_qp_plan *plan, const sfb_qp_params *prm, int64_t batch, const QpBatch &g, void *workspace,
+                              const int32_t *order, void *stream, double *trace = nullptr, int32_t trace_rows = 0,
+                              double *phase_us = nullptr);
 
 }  // namespace sfb

@@ -164,16 +164,14 @@ WsLayout ws_layout(const sfb_sparse_qp_plan *plan, int64_t batch)
   return L;
 }
 
-sfb_status check_sparse_args(const sfb_sparse_qp_plan *plan, const sfb_qp_params *prm, int64_t batch, const void *Px,
-                             const void *q, const void *Ax, const void *l, const void *u, const void *wx,
-                             const void *wy, const void *x, const void *y, const void *code)
+sfb_status check_sparse_args(const sfb_sparse_qp_plan *plan, const sfb_qp_params *prm, int64_t batch, const sfb::QpBatch &g)
 {
   if (!plan) return sfb::fail(SFB_ERR_INVALID_ARG, "plan is NULL");
   if (!prm) return sfb::fail(SFB_ERR_INVALID_ARG, "prm is NULL");
   if (batch < 0) return sfb::fail(SFB_ERR_INVALID_ARG, "batch < 0");
-  if (batch > 0 && (!q || !l || !u || !x || !y || !code || (plan->host.nnzP > 0 && !Px) || (sfb::plan_io(plan).nnzA > 0 && !Ax)))
+  if (batch > 0 && (!g.q || !g.l || !g.u || !g.x || !g.y || !g.code || (plan->host.nnzP > 0 && !g.P) || (sfb::plan_io(plan).nnzA > 0 && !g.A)))
     return sfb::fail(SFB_ERR_INVALID_ARG, "NULL problem / solution pointer");
-  if ((wx == nullptr) != (wy == nullptr))
+  if ((g.wx == nullptr) != (g.wy == nullptr))
     return sfb::fail(SFB_ERR_INVALID_ARG, "warm_x and warm_y must both be given or both be NULL");
   if (prm->max_iter > 0xFFFFFFFFll) return sfb::fail(SFB_ERR_INVALID_ARG, "max_iter exceeds uint32");
   if (batch > 0x7FFFFFFFll) return sfb::fail(SFB_ERR_UNSUPPORTED, "batch exceeds 2^31-1 per call");
@@ -331,15 +329,12 @@ sfb_status sfb_sparse_qp_plan_get_factor_order(const sfb_sparse_qp_plan *plan, i
   return SFB_OK;
 }
 
-namespace {
-sfb_status solve_batch_impl(sfb_sparse_qp_plan *plan, const sfb_qp_params *prm, int64_t batch,
-                                     const double *Px, const double *q, const double *Ax, const double *l,
-                                     const double *u, const double *warm_x, const double *warm_y, double *x,
-                                     double *y, double *obj, uint32_t *iter, int32_t *code, void *workspace,
-                                             const int32_t *order, void *stream, double *trace, int32_t trace_rows,
-                                             double *phase_us = nullptr)
+}  // extern "C"
+
+sfb_status sfb::sparse_solve_batch(sfb_sparse_qp_plan *plan, const sfb_qp_params *prm, int64_t batch, const QpBatch &g, void *workspace,
+                                   const int32_t *order, void *stream, double *trace, int32_t trace_rows, double *phase_us)
 {
-  sfb_status st = check_sparse_args(plan, prm, batch, Px, q, Ax, l, u, warm_x, warm_y, x, y, code);
+  sfb_status st = check_sparse_args(plan, prm, batch, g);
   if (st != SFB_OK) return st;
   if (batch > 0 && !workspace) return sfb::fail(SFB_ERR_INVALID_ARG, "workspace is NULL");
   st = sfb::require_device();
@@ -352,14 +347,15 @@ sfb_status solve_batch_impl(sfb_sparse_qp_plan *plan, const sfb_qp_params *prm, 
   hipStream_t hs   = static_cast<hipStream_t>(stream);
   const WsLayout L = ws_layout(plan, batch);
   char *wsc        = static_cast<char *>(workspace);
-  hipError_t e     = sfb::qp_sparse_launch(dc->dev, kp, batch, Px, q, Ax, l, u, warm_x, warm_y, x, y, obj, iter, code,
+  hipError_t e     = sfb::qp_sparse_launch(dc->dev, kp, batch, g.P, g.q, g.A, g.l, g.u, g.wx, g.wy, g.x, g.y, g.obj, g.iter, g.code,
                                            reinterpret_cast<double *>(wsc), hs, order, reinterpret_cast<int32_t *>(wsc + L.aux_off),
                                            plan->pruned ? &dc->dev_full : nullptr, reinterpret_cast<double *>(wsc + L.pool_off),
                                            trace, (int)trace_rows, phase_us);
   if (e != hipSuccess) return sfb::hip_fail(e, "qp_sparse_kernel launch");
   return SFB_OK;
 }
-}  // namespace
+
+extern "C" {
 
 sfb_status sfb_sparse_qp_solve_batch_ordered(sfb_sparse_qp_plan *plan, const sfb_qp_params *prm, int64_t batch,
                                              const double *Px, const double *q, const double *Ax, const double *l,
@@ -367,8 +363,8 @@ sfb_status sfb_sparse_qp_solve_batch_ordered(sfb_sparse_qp_plan *plan, const sfb
                                              double *y, double *obj, uint32_t *iter, int32_t *code, void *workspace,
                                              const int32_t *order, void *stream)
 {
-  return solve_batch_impl(plan, prm, batch, Px, q, Ax, l, u, warm_x, warm_y, x, y, obj, iter, code, workspace, order, stream,
-                          nullptr, 0);
+  const sfb::QpBatch g{Px, q, Ax, l, u, warm_x, warm_y, x, y, obj, iter, code};
+  return sfb::sparse_solve_batch(plan, prm, batch, g, workspace, order, stream);
 }
 
 sfb_status sfb_sparse_qp_solve_batch_trace(sfb_sparse_qp_plan *plan, const sfb_qp_params *prm, int64_t batch,
@@ -377,9 +373,9 @@ sfb_status sfb_sparse_qp_solve_batch_trace(sfb_sparse_qp_plan *plan, const sfb_q
                                            double *y, double *obj, uint32_t *iter, int32_t *code, void *workspace,
                                            double *trace, int32_t trace_rows, void *stream)
 {
+  const sfb::QpBatch g{Px, q, Ax, l, u, warm_x, warm_y, x, y, obj, iter, code};
   if (!trace || trace_rows <= 0) return sfb::fail(SFB_ERR_INVALID_ARG, "trace is NULL or trace_rows <= 0");
-  return solve_batch_impl(plan, prm, batch, Px, q, Ax, l, u, warm_x, warm_y, x, y, obj, iter, code, workspace, nullptr, stream,
-                          trace, trace_rows);
+  return sfb::sparse_solve_batch(plan, prm, batch, g, workspace, nullptr, stream, trace, trace_rows);
 }
 
 sfb_status sfb_sparse_qp_solve_batch_phases(sfb_sparse_qp_plan *plan, const sfb_qp_params *prm, int64_t batch,
@@ -388,10 +384,10 @@ sfb_status sfb_sparse_qp_solve_batch_phases(sfb_sparse_qp_plan *plan, const sfb_
                                             double *y, double *obj, uint32_t *iter, int32_t *code, void *workspace,
                                             double *trace, int32_t trace_rows, double *phase_us, void *stream)
 {
+  const sfb::QpBatch g{Px, q, Ax, l, u, warm_x, warm_y, x, y, obj, iter, code};
   if (!phase_us) return sfb::fail(SFB_ERR_INVALID_ARG, "phase_us is NULL");
   if (trace != nullptr && trace_rows <= 0) return sfb::fail(SFB_ERR_INVALID_ARG, "trace_rows <= 0");
-  return solve_batch_impl(plan, prm, batch, Px, q, Ax, l, u, warm_x, warm_y, x, y, obj, iter, code, workspace, nullptr, stream,
-                          trace, trace ? trace_rows : 0, phase_us);
+  return sfb::sparse_solve_batch(plan, prm, batch, g, workspace, nullptr, stream, trace, trace ? trace_rows : 0, phase_us);
 }
 
 sfb_status sfb_sparse_qp_solve_batch(sfb_sparse_qp_plan *plan, const sfb_qp_params *prm, int64_t batch,
@@ -400,35 +396,15 @@ sfb_status sfb_sparse_qp_solve_batch(sfb_sparse_qp_plan *plan, const sfb_qp_para
                                      double *y, double *obj, uint32_t *iter, int32_t *code, void *workspace,
                                      void *stream)
 {
-  return sfb_sparse_qp_solve_batch_ordered(plan, prm, batch, Px, q, Ax, l, u, warm_x, warm_y, x, y, obj, iter, code,
-                                           workspace, nullptr, stream);
+  const sfb::QpBatch g{Px, q, Ax, l, u, warm_x, warm_y, x, y, obj, iter, code};
+  return sfb::sparse_solve_batch(plan, prm, batch, g, workspace, nullptr, stream);
 }
 
-sfb_status sfb_sparse_qp_solve_batch_host(sfb_sparse_qp_plan *plan, const sfb_qp_params *prm, int64_t batch,
-                                          const double *Px, const double *q, const double *Ax, const double *l,
-                                          const double *u, const double *warm_x, const double *warm_y, double *x,
-                                          double *y, double *obj, uint32_t *iter, int32_t *code)
+// the host-pointer solve (hb: host arrays) on the plan's cached device buffer; trace and phase_us are optional
+static sfb_status sparse_host_impl(sfb_sparse_qp_plan *plan, const sfb_qp_params *prm, int64_t batch, const sfb::QpBatch &hb, double *trace,
+                                   int32_t trace_rows, double *phase_us)
 {
-  return sfb_sparse_qp_solve_batch_host_trace(plan, prm, batch, Px, q, Ax, l, u, warm_x, warm_y, x, y, obj, iter, code, nullptr, 0);
-}
-
-sfb_status sfb_sparse_qp_solve_batch_host_trace(sfb_sparse_qp_plan *plan, const sfb_qp_params *prm, int64_t batch,
-                                                const double *Px, const double *q, const double *Ax, const double *l,
-                                                const double *u, const double *warm_x, const double *warm_y, double *x,
-                                                double *y, double *obj, uint32_t *iter, int32_t *code, double *trace,
-                                                int32_t trace_rows)
-{
-  return sfb_sparse_qp_solve_batch_host_phases(plan, prm, batch, Px, q, Ax, l, u, warm_x, warm_y, x, y, obj, iter, code, trace,
-                                               trace_rows, nullptr);
-}
-
-sfb_status sfb_sparse_qp_solve_batch_host_phases(sfb_sparse_qp_plan *plan, const sfb_qp_params *prm, int64_t batch,
-                                                 const double *Px, const double *q, const double *Ax, const double *l,
-                                                 const double *u, const double *warm_x, const double *warm_y, double *x,
-                                                 double *y, double *obj, uint32_t *iter, int32_t *code, double *trace,
-                                                 int32_t trace_rows, double *phase_us)
-{
-  sfb_status st = check_sparse_args(plan, prm, batch, Px, q, Ax, l, u, warm_x, warm_y, x, y, code);
+  sfb_status st = check_sparse_args(plan, prm, batch, hb);
   if (st == SFB_OK && trace != nullptr && trace_rows <= 0) st = sfb::fail(SFB_ERR_INVALID_ARG, "trace_rows <= 0");
   // verbose for ONE problem (the reference's use of the flag: one QPSolver object, qp_solver.hpp:409-420, :490-501, :550-565):
   // the per-iteration table and the per-phase times are collected on the device and printed below
@@ -449,20 +425,15 @@ sfb_status sfb_sparse_qp_solve_batch_host_phases(sfb_sparse_qp_plan *plan, const
   const sfb::SparsePlanHost &h = sfb::plan_io(plan);  // the caller's pattern (strides of the value arrays)
   const size_t B = (size_t)batch, N = (size_t)h.n, M = (size_t)h.m, NP = (size_t)h.nnzP, NA = (size_t)h.nnzA;
   const size_t wsb  = ws_layout(plan, batch).total;  // multiple of 8
-  const size_t TR0 = trace ? B * (size_t)trace_rows * 5 : 0, W = warm_x ? B : 0;
+  const size_t TR0 = trace ? B * (size_t)trace_rows * 5 : 0;
   using S = sfb::Staging;
-  S s;  // the solver's workspace first (reuse_factor below), then the arrays; the phase times follow the table
+  S s;  // the solver's workspace first (reuse_factor below), then the table and the phase times, then the arrays
   char *dws;
-  double *dPx, *dq, *dAx, *dl, *du, *dwx, *dwy, *dx, *dy, *dobj, *dtrace, *dphase;
-  uint32_t *dit;
-  int32_t *dcode;
+  double *dtrace, *dphase;
+  sfb::QpBatch d{};
   s.add(&dws, wsb);
-  s.add(&dPx, B * NP, S::In, Px); s.add(&dq, B * N, S::In, q); s.add(&dAx, B * NA, S::In, Ax);
-  s.add(&dl, B * M, S::In, l); s.add(&du, B * M, S::In, u);
-  s.add(&dwx, W * N, S::In, warm_x); s.add(&dwy, W * M, S::In, warm_y);
-  s.add(&dx, B * N, S::Out, x); s.add(&dy, B * M, S::Out, y); s.add(&dobj, B, S::Out, obj);
   s.add(&dtrace, TR0, S::InOut, trace); s.add(&dphase, phase_us ? B * 6 : 0, S::Out, phase_us);
-  s.add(&dit, B, S::Out, iter); s.add(&dcode, B, S::Out, code);
+  sfb::stage_qp(s, B, NP, N, NA, M, hb, d);
   const size_t bytes = s.bytes();
   int devid    = 0;
   hipError_t e = hipGetDevice(&devid);
@@ -504,7 +475,6 @@ sfb_status sfb_sparse_qp_solve_batch_host_phases(sfb_sparse_qp_plan *plan, const
   hd->batch  = batch;
   hd->origin = tl_multi_origin;
   prm = &prm_call;
-  if (!warm_x) dwx = dwy = nullptr;
   using clk = std::chrono::steady_clock;
   auto ms   = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
   const auto tv0 = clk::now();
@@ -518,8 +488,8 @@ sfb_status sfb_sparse_qp_solve_batch_host_phases(sfb_sparse_qp_plan *plan, const
     // stream's work up to here explicitly.
     if ((e = hipEventRecord(hd->uploaded, nullptr)) != hipSuccess) break;
     if ((e = hipStreamWaitEvent(hd->stream, hd->uploaded, 0)) != hipSuccess) break;
-    st = solve_batch_impl(plan, prm, batch, dPx, dq, dAx, dl, du, dwx, dwy, dx, dy, dobj, dit, dcode, dws, nullptr, hd->stream,
-                          trace ? dtrace : nullptr, trace ? trace_rows : 0, phase_us ? dphase : nullptr);
+    st = sfb::sparse_solve_batch(plan, prm, batch, d, dws, nullptr, hd->stream, trace ? dtrace : nullptr, trace ? trace_rows : 0,
+                                 phase_us ? dphase : nullptr);
     if (st != SFB_OK) {
       (void)hipStreamSynchronize(hd->stream);
       break;
@@ -534,31 +504,60 @@ sfb_status sfb_sparse_qp_solve_batch_host_phases(sfb_sparse_qp_plan *plan, const
   }
   if (st == SFB_OK && !vphase.empty()) {  // the summary of qp_solver.hpp:550-565
     uint32_t it1 = 0;
-    if (iter) it1 = iter[0];
-    else if (hipMemcpy(&it1, dit, 4, hipMemcpyDeviceToHost) != hipSuccess) (void)hipGetLastError();
-    sfb::verbose_summary(code[0], it1, vphase.data());
+    if (hb.iter) it1 = hb.iter[0];
+    else if (hipMemcpy(&it1, d.iter, 4, hipMemcpyDeviceToHost) != hipSuccess) (void)hipGetLastError();
+    sfb::verbose_summary(hb.code[0], it1, vphase.data());
   }
   if (st == SFB_OK && prm->verbose) {
     std::vector<uint32_t> itv;
-    if (!iter) {
+    if (!hb.iter) {
       itv.resize(B);
-      if (hipMemcpy(itv.data(), dit, B * 4, hipMemcpyDeviceToHost) != hipSuccess) itv.clear();
+      if (hipMemcpy(itv.data(), d.iter, B * 4, hipMemcpyDeviceToHost) != hipSuccess) itv.clear();
     }
     std::printf("[sfb] sparse plan: nnz(K) %d, nnz(L) %d%s\n", plan->host.nnzK, plan->host.nnzL,
                 plan->pruned ? " (explicit zeros of A left out; whole-pattern fallback per item)" : "");
-    sfb::verbose_report("sparse QP batch", batch, h.n, h.m, ms(tv0, tv1), ms(tv1, tv2), ms(tv2, clk::now()), code,
-                        iter ? iter : (itv.empty() ? nullptr : itv.data()));
+    sfb::verbose_report("sparse QP batch", batch, h.n, h.m, ms(tv0, tv1), ms(tv1, tv2), ms(tv2, clk::now()), hb.code,
+                        hb.iter ? hb.iter : (itv.empty() ? nullptr : itv.data()));
   }
   return st;
 }
 
+sfb_status sfb_sparse_qp_solve_batch_host(sfb_sparse_qp_plan *plan, const sfb_qp_params *prm, int64_t batch,
+                                          const double *Px, const double *q, const double *Ax, const double *l,
+                                          const double *u, const double *warm_x, const double *warm_y, double *x,
+                                          double *y, double *obj, uint32_t *iter, int32_t *code)
+{
+  const sfb::QpBatch h{Px, q, Ax, l, u, warm_x, warm_y, x, y, obj, iter, code};
+  return sparse_host_impl(plan, prm, batch, h, nullptr, 0, nullptr);
+}
+
+sfb_status sfb_sparse_qp_solve_batch_host_trace(sfb_sparse_qp_plan *plan, const sfb_qp_params *prm, int64_t batch,
+                                                const double *Px, const double *q, const double *Ax, const double *l,
+                                                const double *u, const double *warm_x, const double *warm_y, double *x,
+                                                double *y, double *obj, uint32_t *iter, int32_t *code, double *trace,
+                                                int32_t trace_rows)
+{
+  const sfb::QpBatch h{Px, q, Ax, l, u, warm_x, warm_y, x, y, obj, iter, code};
+  return sparse_host_impl(plan, prm, batch, h, trace, trace_rows, nullptr);
+}
+
+sfb_status sfb_sparse_qp_solve_batch_host_phases(sfb_sparse_qp_plan *plan, const sfb_qp_params *prm, int64_t batch,
+                                                 const double *Px, const double *q, const double *Ax, const double *l,
+                                                 const double *u, const double *warm_x, const double *warm_y, double *x,
+                                                 double *y, double *obj, uint32_t *iter, int32_t *code, double *trace,
+                                                 int32_t trace_rows, double *phase_us)
+{
+  const sfb::QpBatch h{Px, q, Ax, l, u, warm_x, warm_y, x, y, obj, iter, code};
+  return sparse_host_impl(plan, prm, batch, h, trace, trace_rows, phase_us);
+}
 
 sfb_status sfb_sparse_qp_solve_batch_host_multi(sfb_sparse_qp_plan *plan, const sfb_qp_params *prm, int64_t batch,
                                                 const double *Px, const double *q, const double *Ax, const double *l,
                                                 const double *u, const double *warm_x, const double *warm_y, double *x,
                                                 double *y, double *obj, uint32_t *iter, int32_t *code)
 {
-  sfb_status st = check_sparse_args(plan, prm, batch, Px, q, Ax, l, u, warm_x, warm_y, x, y, code);
+  const sfb::QpBatch hb{Px, q, Ax, l, u, warm_x, warm_y, x, y, obj, iter, code};
+  sfb_status st = check_sparse_args(plan, prm, batch, hb);
   if (st != SFB_OK) return st;
   if (batch == 0) return sfb::require_device();
   const sfb::SparsePlanHost &h = sfb::plan_io(plan);
@@ -579,12 +578,8 @@ sfb_status sfb_sparse_qp_solve_batch_host_multi(sfb_sparse_qp_plan *plan, const 
   const sfb_qp_params *const prm_shard = &prm_call;
   const auto t_call = std::chrono::steady_clock::now();
   const sfb_status rs = sfb::run_sharded(batch, [&](int, int64_t b0, int64_t cnt) {
-    const size_t o = (size_t)b0;  // the plan uploads its tables to a device on first use; each device has its own workspace
-    tl_multi_origin = origin;
-    const sfb_status s1 = sfb_sparse_qp_solve_batch_host(plan, prm_shard, cnt, Px ? Px + o * NP : nullptr, q + o * N, Ax ? Ax + o * NA : nullptr,
-                                          l + o * M, u + o * M, warm_x ? warm_x + o * N : nullptr,
-                                          warm_y ? warm_y + o * M : nullptr, x + o * N, y + o * M, obj ? obj + o : nullptr,
-                                          iter ? iter + o : nullptr, code + o);
+    tl_multi_origin = origin;  // the plan uploads its tables to a device on first use; each device has its own workspace
+    const sfb_status s1 = sparse_host_impl(plan, prm_shard, cnt, sfb::shard(hb, (size_t)b0, NP, N, NA, M), nullptr, 0, nullptr);
     tl_multi_origin = 0;
     return s1;
   });

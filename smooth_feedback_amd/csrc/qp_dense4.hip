@@ -1,7 +1,7 @@
 // Batched dense ADMM QP solver for gfx950, k = n+m <= 32: FOUR QPs PER WAVEFRONT, one per 16-lane row.
 //
-// Same algorithm and the same bits as qp_dense.hip (reference qp_solver.hpp:343-568); what changes is
-// the mapping of the ADMM loop onto the wave:
+// Same algorithm and the same bits as the one-QP-per-wave kernels (qp_dense_mid.hip; reference qp_solver.hpp:343-568);
+// what changes is the mapping of the ADMM loop onto the wave:
 //   - a DPP row_newbcast FP64 fmac costs the same VALU time whether 16 or 64 lanes do useful work,
 //     and the one-QP-per-wave kernel keeps only one 16-lane row busy per sweep step.  Here every row
 //     carries its own QP ("slot"): lane cc of a row holds system rows cc and 16+cc, so a whole
@@ -35,6 +35,7 @@
 #include "knobs.h"
 #include "../../include/sfb.h"
 #include "qp_dense_common.h"
+#include "stream_scratch.h"
 
 namespace sfb {
 
@@ -866,36 +867,30 @@ __global__ void __launch_bounds__(64) qp_dense4_finish_kernel(const DenseKernelP
 
 size_t qp_dense4_lds_bytes(int n, int m) { return (size_t)kSlots * slot4_doubles(n, m) * sizeof(double); }
 
+// LDS of the setup / finish kernels (one QP per wavefront there): the packed KKT triangle, copies of P and A, the
+// vectors of the scaling / polish / report code in qp_dense_common.h
+static size_t qp_dense_lds_bytes(int n, int m)
+{
+  const int k = n + m;
+  const size_t doubles = ((size_t)k * (k + 1)) / 2 + (size_t)n * n + (size_t)m * n + 5 * (size_t)n + 8 * (size_t)m + (size_t)k;
+  const size_t ints    = (size_t)k + (size_t)m;
+  return doubles * sizeof(double) + ((ints * sizeof(int) + 15) / 16) * 16;
+}
+
 template<int NB>
 static hipError_t launch4(const DenseKernelParams &kp, int64_t batch, const QpBatch &g, int ncu, hipStream_t stream, void *workspace)
 {
   // per-launch workspace: QP records, then the queue (4 counters on their own cache lines + ring of `batch`
-  // 8-byte entries); stream-ordered allocation (no device synchronisation in the steady state)
+  // 8-byte entries); the caller's (sfb_workspace), or stream-ordered for this launch
   const Rec4 R        = rec4_layout<NB>(kp.n, kp.m);
   const size_t rbytes = (size_t)batch * (size_t)R.size * sizeof(double);
   const size_t qbytes = 64 * sizeof(unsigned) + 2 * (size_t)batch * sizeof(unsigned long long);
-  const size_t bytes  = rbytes + qbytes;
-  double *wsp        = static_cast<double *>(workspace);  // the caller's (sfb_workspace), or per-launch below
-  const bool owned   = workspace == nullptr;
-  bool async_alloc   = true;
-  hipError_t e       = hipSuccess;
-  if (owned) {
-    e = hipMallocAsync(reinterpret_cast<void **>(&wsp), bytes, stream);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      async_alloc = false;
-      e           = hipMalloc(reinterpret_cast<void **>(&wsp), bytes);
-      if (e != hipSuccess) return e;
-    }
-  }
+  StreamScratch scratch(workspace, rbytes + qbytes, stream);
+  if (scratch.error() != hipSuccess) return scratch.error();
+  double *wsp     = static_cast<double *>(scratch.get());
   unsigned *queue = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(wsp) + rbytes);
-  e               = hipMemsetAsync(queue, 0, qbytes, stream);
-  if (e != hipSuccess) {
-    if (!owned) return e;
-    if (async_alloc) (void)hipFreeAsync(wsp, stream);
-    else (void)hipFree(wsp);
-    return e;
-  }
+  hipError_t e    = hipMemsetAsync(queue, 0, qbytes, stream);
+  if (e != hipSuccess) return e;
   const dim3 block(kWave), full((unsigned)batch);
   const size_t lds1 = qp_dense_lds_bytes(kp.n, kp.m);
   hipLaunchKernelGGL((qp_dense4_setup_kernel<NB>), full, block, lds1, stream, kp, g, wsp);
@@ -916,16 +911,8 @@ static hipError_t launch4(const DenseKernelParams &kp, int64_t batch, const QpBa
     hipLaunchKernelGGL((qp_dense4_iterate_kernel<NB>), grid, block, lds, stream, kp, g, wsp, queue, (unsigned)batch,
                        slice_checks);
   hipLaunchKernelGGL((qp_dense4_finish_kernel<NB>), full, block, lds1, stream, kp, g, wsp);
-  e = hipGetLastError();
-  if (!owned) return e;
-  if (async_alloc) {
-    const hipError_t e2 = hipFreeAsync(wsp, stream);
-    if (e == hipSuccess) e = e2;
-  } else {
-    (void)hipStreamSynchronize(stream);
-    (void)hipFree(wsp);
-  }
-  return e;
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  return scratch.release();
 }
 
 size_t qp_dense4_ws_bytes(int n, int m, int64_t batch)

@@ -1,7 +1,7 @@
-// Building blocks shared by the dense QP kernels (qp_dense.hip: one QP per wavefront, k <= 64;
+// Building blocks of the one-wavefront-per-QP parts of the dense QP kernels (the setup and finish kernels of
 // qp_dense4.hip: four QPs per wavefront, k <= 32).  All of them are WAVE-WIDE routines working on one
 // problem whose data sits in LDS (lane i owns row/column i); arithmetic order is the oracle's
-// (oracle/qp_oracle.c), see the header of qp_dense.hip.
+// (oracle/qp_oracle.c).  Which kernel takes which size: qp_dense_route.h.
 #pragma once
 #include <hip/hip_runtime.h>
 

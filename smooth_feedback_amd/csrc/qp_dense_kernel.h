@@ -4,6 +4,8 @@
 
 #include <cstdint>
 
+#include "qp_dense_route.h"
+
 namespace sfb {
 
 // QPSolverParams (qp_solver.hpp:29-68) with the float members already widened to double exactly as
@@ -28,7 +30,6 @@ struct QpBatch {
   int32_t *code;
 };
 
-size_t qp_dense_lds_bytes(int n, int m);
 size_t qp_dense4_lds_bytes(int n, int m);
 
 // k = n+m <= 32: four QPs per wavefront, persistent grid with a device-side queue (qp_dense4.hip)
@@ -37,15 +38,13 @@ hipError_t qp_dense4_launch(const DenseKernelParams &kp, int64_t batch, const Qp
                             void *workspace = nullptr);
 size_t qp_dense4_ws_bytes(int n, int m, int64_t batch);
 
-// 64 < n+m <= 1024: one QP per wavefront, KKT matrix and pivoted LDL' in the QP's HBM workspace (qp_dense_big.hip);
-// workspace: batch * qp_dense_big_ws_doubles(n, m) doubles
+// 128 < n+m <= 1024 (kDenseBigMaxK): one QP per wavefront, KKT matrix and pivoted LDL' in the QP's HBM workspace
+// (qp_dense_big.hip); workspace: batch * qp_dense_big_ws_doubles(n, m) doubles
 size_t qp_dense_big_ws_doubles(int n, int m);
 hipError_t qp_dense_big_launch(const DenseKernelParams &kp, int64_t batch, const QpBatch &g, double *workspace, hipStream_t stream);
-constexpr int kDenseBigMaxK = 1024;
 
-// 32 < n+m <= 128: one QP per wavefront, everything on chip (qp_dense_mid.hip): packed factor in LDS, block sweeps with
+// n+m <= 128 (kDenseMidMaxK): one QP per wavefront, everything on chip (qp_dense_mid.hip): packed factor in LDS, block sweeps with
 // the pivot broadcast fused into the FP64 FMA, the matrix written in Eigen's pivot order before an unpivoted factorisation
-constexpr int kDenseMidMaxK = 128;
 size_t qp_dense_mid_lds_bytes(int n, int m);
 // workspace: qp_dense_mid_ws_bytes bytes of device memory (0 for batches the chip holds at once), or nullptr = stream-ordered allocation
 size_t qp_dense_mid_ws_bytes(const DenseKernelParams &kp, int64_t batch);
@@ -63,10 +62,5 @@ hipError_t qp_dense_mid_trace_launch(const DenseKernelParams &kp, int64_t batch,
 constexpr int kDenseTallMaxN = 16;
 size_t qp_dense_tall_ws_bytes(int n, int m, int64_t batch);
 hipError_t qp_dense_tall_launch(const DenseKernelParams &kp, int64_t batch, const QpBatch &g, hipStream_t stream, void *workspace);
-
-hipError_t qp_dense_launch(const DenseKernelParams &kp, int64_t batch, const double *P, const double *q,
-                           const double *A, const double *l, const double *u, const double *wx, const double *wy,
-                           double *x, double *y, double *obj, uint32_t *iter, int32_t *code, hipStream_t stream,
-                           void *workspace = nullptr);  // (workspace: see qp_dense4_launch; unused by the one-per-wave kernels)
 
 }  // namespace sfb

@@ -39,6 +39,7 @@
 #include "../../include/sfb.h"
 #include "knobs.h"
 #include "qp_dense_kernel.h"
+#include "stream_scratch.h"
 #include "sweep_rows.h"
 #include "wave_util.h"
 
@@ -1618,23 +1619,14 @@ hipError_t qp_dense_mid_launch(const DenseKernelParams &kp, int64_t batch, const
   const size_t need = qp_dense_mid_ws_bytes(kp, batch);
   if (need == 0) return mid_launch(kp, g, MidLaunch{MID_FUSED, (unsigned)batch, (unsigned)batch, nullptr, 0, nullptr, 0, nullptr, stream});
   // split launch: setup -> loop (persistent, time-sliced) -> finish
-  char *buf        = static_cast<char *>(workspace);
-  bool async_alloc = true;
-  hipError_t e     = hipSuccess;
-  if (buf == nullptr) {
-    e = hipMallocAsync(reinterpret_cast<void **>(&buf), need, stream);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      async_alloc = false;
-      e           = hipMalloc(reinterpret_cast<void **>(&buf), need);
-      if (e != hipSuccess) return e;
-    }
-  }
+  StreamScratch scratch(workspace, need, stream);
+  if (scratch.error() != hipSuccess) return scratch.error();
+  char *buf         = static_cast<char *>(scratch.get());
   const size_t wsd  = mid_save_doubles(kp.n, kp.m);
   const size_t qoff = (size_t)batch * wsd * sizeof(double);
   unsigned *queue   = reinterpret_cast<unsigned *>(buf + qoff);
   double *ws        = reinterpret_cast<double *>(buf);
-  e = hipMemsetAsync(queue, 0, need - qoff, stream);
+  hipError_t e      = hipMemsetAsync(queue, 0, need - qoff, stream);
   if (e == hipSuccess) e = mid_launch(kp, g, MidLaunch{MID_SETUP, (unsigned)batch, (unsigned)batch, ws, wsd, nullptr, 0, nullptr, stream});
   if (e == hipSuccess) {
     const int res = mid_resident(kp);
@@ -1642,15 +1634,8 @@ hipError_t qp_dense_mid_launch(const DenseKernelParams &kp, int64_t batch, const
     e = mid_launch(kp, g, MidLaunch{MID_LOOP, grid, (unsigned)batch, ws, wsd, queue, mid_slice(kp), nullptr, stream});
   }
   if (e == hipSuccess) e = mid_launch(kp, g, MidLaunch{MID_FINISH, (unsigned)batch, (unsigned)batch, ws, wsd, nullptr, 0, nullptr, stream});
-  if (workspace == nullptr) {
-    if (async_alloc) {
-      (void)hipFreeAsync(buf, stream);
-    } else {
-      (void)hipStreamSynchronize(stream);
-      (void)hipFree(buf);
-    }
-  }
-  return e;
+  if (e != hipSuccess) return e;
+  return scratch.release();
 }
 
 }  // namespace sfb

@@ -6,6 +6,7 @@ follows the oracle's operation order, so the tests also report whether results a
 """
 import json
 import os
+import types
 
 import numpy as np
 import pytest
@@ -441,18 +442,44 @@ def test_verbose_prints_a_summary_of_the_call(sfb, capfd):
     assert "[sfb]" not in capfd.readouterr().out
 
 
-@pytest.mark.parametrize("n,m", [(3, 5), (10, 20), (20, 30), (40, 60), (3, 203)])
-def test_explicit_workspace_gives_the_same_results(sfb, n, m):
+# (n, m, max_time, debug knobs): the five sizes of every dense path, then the boundaries of the routing (csrc/qp_dense_route.h) at which
+# the workspace asked for and the kernel launched could disagree
+WORKSPACE_CASES = [
+    pytest.param(3, 5, None, {}, id="3-5"), pytest.param(10, 20, None, {}, id="10-20"), pytest.param(20, 30, None, {}, id="20-30"),
+    pytest.param(40, 60, None, {}, id="40-60"), pytest.param(3, 203, None, {}, id="3-203"),
+    pytest.param(12, 20, 30.0, {}, id="12-20-time-limit"),                  # k = 32 with a time limit: Mid
+    pytest.param(12, 21, None, {}, id="12-21"),                             # k = 33
+    pytest.param(64, 64, None, {}, id="64-64"),                             # k = 128
+    pytest.param(64, 65, None, {}, id="64-65"),                             # k = 129: Big
+    pytest.param(64, 65, None, dict(SFB_QP_DENSE_BIG=0), id="64-65-full-pattern"),
+    pytest.param(20, 30, None, dict(SFB_MID_GRID=2, SFB_MID_SLICE=1), id="20-30-split-mid"),
+]
+
+
+@pytest.mark.parametrize("n,m,max_time,debug", WORKSPACE_CASES)
+def test_explicit_workspace_gives_the_same_results(sfb, env_knob, n, m, max_time, debug):
     """sfb_workspace_create / sfb_qp_dense_solve_batch_ws: the caller's device workspace instead of stream-ordered
     allocations inside the call -- every dense path (four-per-wave, one-per-wave, big dense), same results bit for
-    bit, twice on the same workspace; a workspace that is too small is refused."""
+    bit, twice on the same workspace; a workspace that is too small is refused.  The full-pattern route (SFB_QP_DENSE_BIG=0
+    at k = 129) agrees with the pivoted kernels to rounding only: its results are held to _compare_full_pattern's bounds
+    against the pivoted solve of the same batch."""
     import torch
     B = 96
     P, q, A, l, u = sfb.random_qp_batch(11, B, m, n, 0.6)
-    prm = sfb.QPSolverParams(max_iter=600)
-    ref = sfb.solve_qp_batch_host(P, q, A, l, u, prm)
+    prm = sfb.QPSolverParams(max_iter=600) if max_time is None else sfb.QPSolverParams(max_iter=600, max_time=max_time)
+    full_pattern = "SFB_QP_DENSE_BIG" in debug
+    if not full_pattern:
+        env_knob(**debug)
+    ref = sfb.solve_qp_batch_host(P, q, A, l, u, prm)   # (full pattern: the pivoted Big route, the knob is set below)
+    if full_pattern:
+        env_knob(**debug)
     need = sfb.Workspace.dense_bytes(B, n, m, prm)
-    assert (need == 0) == (32 < n + m <= 128)  # the on-chip kernels (qp_dense.hip, qp_dense_mid.hip) need none
+    if not debug and max_time is None:
+        assert (need == 0) == (32 < n + m <= 128)  # the on-chip kernel (qp_dense_mid.hip) needs none at this batch
+    if max_time is not None:   # the documented over-ask: the larger of the four-per-wave and the on-chip need
+        assert need >= sfb.Workspace.dense_bytes(B, n, m, sfb.QPSolverParams(max_iter=600))
+    if "SFB_MID_GRID" in debug:
+        assert need > 0        # the split launch keeps per-QP records and a queue
     ws = sfb.Workspace(need)
     dev = torch.device("cuda:0")
     d = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (P, q, A, l, u)]
@@ -463,6 +490,10 @@ def test_explicit_workspace_gives_the_same_results(sfb, n, m):
         sfb.solve_qp_batch_device_ws(B, n, m, *[a.data_ptr() for a in d], x.data_ptr(), y.data_ptr(), obj.data_ptr(),
                                      it.data_ptr(), code.data_ptr(), ws, prm, stream=torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
+        if full_pattern:
+            r = types.SimpleNamespace(code=code.cpu().numpy(), iter=it.cpu().numpy().astype(np.uint32), primal=x.cpu().numpy())
+            _compare_full_pattern(r, dict(code=ref.code, iter=ref.iter, x=ref.primal), B)
+            continue
         assert np.array_equal(code.cpu().numpy(), ref.code) and np.array_equal(it.cpu().numpy().astype(np.uint32), ref.iter)
         assert np.array_equal(x.cpu().numpy(), ref.primal, equal_nan=True) and np.array_equal(y.cpu().numpy(), ref.dual, equal_nan=True)
         assert np.array_equal(obj.cpu().numpy(), ref.objective, equal_nan=True)
