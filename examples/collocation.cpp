@@ -14,6 +14,9 @@
 #include <smooth/feedback/collocation/mesh_function.hpp>
 #include <smooth/feedback/mpc.hpp>
 
+#include <thread>
+
+#include "flat_ocp_harness.h"
 #include "lie_eval.h"
 #include "ocp_nlp_harness.h"
 #include "rigid_body_model.h"
@@ -685,6 +688,239 @@ int sfbx_flat_dynamics_host(int model, int rows, const double * xl, const double
   if (model == 0) flat_dynamics_rows<sfbx::VehicleModel6, sfbx::X6, sfbx::U2>(rows, xl, dxl, ul, e, v, out);
   else if (model == 1) flat_dynamics_rows<sfbx::RigidBodyModel, sfbx::X12B, sfbx::U6>(rows, xl, dxl, ul, e, v, out);
   else return -1;
+  return 0;
+}
+
+// ---- flatten_ocp (ocp_flatten.hpp) through examples/flat_ocp_harness.h ----
+int sfbx_flat_lie_eval(int group, int op, int64_t count, const double * in, double * out)
+{
+  if (count < 0 || op < 0 || op > 1) return -1;
+  const bool ok = sfbx::flat_lie_dispatch(group, [&]<class G>() {
+    constexpr int T = G::Dof;
+    for (int64_t k = 0; k < count; ++k) sfbx::flat_lie_item<G>(op, in + k * (op == 0 ? T : 2 * T), out + k * T * T);
+  });
+  return ok ? 0 : -1;
+}
+
+int sfbx_flat_ocp_sizes(int problem, int32_t N, int32_t * sizes)
+{
+  const bool ok = sfbx::flat_dispatch_problem(problem, [&]<class Ocp>() {
+    using S = sfbx::FlatSizes<Ocp>;
+    const int32_t v[7] = {S::Nx, S::Nu, S::Nq, S::Ncr, S::Nce, S::stride, (int32_t)S::n(N)};
+    std::copy(v, v + 7, sizes);
+  });
+  return ok ? 0 : -1;
+}
+
+int sfbx_flat_ocp_nodes_host(int problem, int64_t agents, int32_t N, const double * tau, const double * x, const double * traj, double * Ff, double * dFf,
+                             double * Fg, double * dFg, double * Fcr, double * dFcr, double * ce, double * dce, double * theta, double * dtheta, int threads)
+{
+  if (agents < 0 || N < 1 || threads < 1) return -1;
+  const bool ok = sfbx::flat_dispatch_problem(problem, [&]<class Ocp>() {
+    using S = sfbx::FlatSizes<Ocp>;
+    const auto part = [&](int64_t b0, int64_t b1) {  // agents [b0, b1): every pointer moved to agent b0
+      const auto model = sfbx::flat_swarm_model<Ocp>(traj + b0 * S::stride);
+      const sfbx::FlatNodeOut o{Ff + b0 * N * S::Nx,   dFf + b0 * N * S::Nx * S::nz,   Fg + b0 * N * S::Nq, dFg + b0 * N * S::Nq * S::nz,
+                                Fcr + b0 * N * S::Ncr, dFcr + b0 * N * S::Ncr * S::nz, ce + b0 * S::Nce,    dce + b0 * S::Nce * S::ne,
+                                theta + b0,            dtheta + b0 * S::ne};
+      sfbx::flat_nodes_host(model, b1 - b0, N, tau, x + b0 * S::n(N), o);
+    };
+    if (threads == 1) return part(0, agents);
+    std::vector<std::thread> pool;
+    for (int k = 0; k < threads; ++k) pool.emplace_back(part, agents * k / threads, agents * (k + 1) / threads);
+    for (auto & th : pool) th.join();
+  });
+  return ok ? 0 : -1;
+}
+
+int sfbx_flat_ocp_nlp_host(int problem, int mesh_kind, int64_t agents, const double * x, const double * traj, double * g, double * dg, double * f, double * df,
+                           int64_t * differing, int32_t * sizes, double * taus)
+{
+  if (agents < 0) return -1;
+  try {
+    const auto mesh = sfbx::flat_mesh(mesh_kind);
+    const bool ok   = sfbx::flat_dispatch_problem(problem, [&]<class Ocp>() {
+      using S          = sfbx::FlatSizes<Ocp>;
+      const auto model = sfbx::flat_swarm_model<Ocp>(traj);
+      auto nlp0        = sf::ocp_to_nlp(sfbx::flat_agent_ocp(model, 0), mesh);
+      const int64_t n = (int64_t)nlp0.n(), m = (int64_t)nlp0.m(), nnz = nlp0.tables().nnz;
+      if (sizes) sizes[0] = (int32_t)n, sizes[1] = (int32_t)m, sizes[2] = (int32_t)nnz, sizes[3] = (int32_t)mesh.N_colloc();
+      if (taus) {
+        const std::vector<double> t = mesh.all_nodes();
+        std::copy(t.begin(), t.end(), taus);
+      }
+      if (!x) return;
+      for (int64_t b = 0; b < agents; ++b)
+        sfbx::flat_nlp_host(model, b, mesh, x + b * n, g ? g + b * m : nullptr, dg ? dg + b * nnz : nullptr, f ? f + b : nullptr,
+                            df ? df + b * S::ne : nullptr, differing ? differing + b : nullptr);
+    });
+    return ok ? 0 : -1;
+  } catch (const std::exception & e) {
+    std::fprintf(stderr, "collocation harness: %s\n", e.what());
+    return -2;
+  }
+}
+
+// Caller code against <smooth/feedback/ocp_flatten.hpp> under the reference's names; figures [8] receives what each
+// scenario measured.  Returns 0, or the number of the first expectation that fails.
+//   1  a flattened Rn problem (term tables of ocp_nlp_harness.h around affine trajectories) gives the NLP of the original
+//      at x = xl + e: g, and dg with the tf column corrected by the chain rule through xl(tf tau_i), ul(tf tau_i)
+//   2  unflatten_ocpsol(nlpsol_to_ocpsol(flat)) at the nodes: x(t_i) = xl(t_i) (+) e_i, u likewise, Q and multipliers carried
+//   3  d2l_dx2 of the flattened planar vehicle (symmetric from its upper triangle) against central differences of sigma df + lambda' dg
+//   4  spline_trajectory: the adapter's point is the spline's, its velocity the body velocity of the curve
+int sfbx_test_flatten_api(double * figures)
+{
+  namespace F = smooth::feedback;
+  for (int k = 0; k < 8; ++k) figures[k] = 0.0;
+  // ---- 1 ----
+  {
+    constexpr int NX = 3, NU = 2, NQ = 2, NCR = 1, NCE = 3, nz = 1 + NX + NU, ne = 1 + 2 * NX + NQ;
+    // f = (x1 + sin u0, -x0 + t u1, x2 x0), g = (x0^2 + u0^2, cos x2), cr = x1 u1, theta = tf + q0 + x0_0 xf_1, ce = (tf, x0_0, xf_2 q1)
+    const int32_t tf_[] = {0, 2, 1, 0, 0, 0, 0,  0, 4, 3, 0, 0, 0, 0,  1, 1, 1, 0, 0, 0, 0,  1, 0, 1, 5, 1, 0, 0,  2, 3, 1, 1, 1, 0, 0};
+    const double cf_[]  = {1, 1, -1, 1, 1};
+    const int32_t tg_[] = {0, 1, 2, 0, 0, 0, 0,  0, 4, 2, 0, 0, 0, 0,  1, 3, 4, 0, 0, 0, 0};
+    const double cg_[]  = {1, 1, 1};
+    const int32_t tc_[] = {0, 2, 1, 5, 1, 0, 0};
+    const double cc_[]  = {1};
+    const int32_t tt_[] = {0, 0, 1, 0, 0, 0, 0,  0, 7, 1, 0, 0, 0, 0,  0, 1, 1, 5, 1, 0, 0};
+    const double ct_[]  = {1, 1, 1};
+    const int32_t te_[] = {0, 0, 1, 0, 0, 0, 0,  1, 1, 1, 0, 0, 0, 0,  2, 6, 1, 8, 1, 0, 0};
+    const double ce_[]  = {1, 1, 1};
+    sfbx::TermOcp<NX, NU, NQ, NCR, NCE> ocp{};
+    ocp.f.tab = {5, tf_, cf_}, ocp.g.tab = {3, tg_, cg_}, ocp.cr.tab = {1, tc_, cc_}, ocp.theta.tab = {3, tt_, ct_}, ocp.ce.tab = {3, te_, ce_};
+    if (!ocp.f.tab.valid(NX, nz) || !ocp.g.tab.valid(NQ, nz) || !ocp.cr.tab.valid(NCR, nz) || !ocp.theta.tab.valid(1, ne) || !ocp.ce.tab.valid(NCE, ne)) return 100;
+    const F::Vec<NX> a{0.3, -0.2, 0.5}, da{0.1, 0.25, -0.15};
+    const F::Vec<NU> c{0.2, -0.4}, dc{-0.3, 0.2};
+    const auto xl = F::trajectory([=](double t) { F::Rn<NX> x; for (int i = 0; i < NX; ++i) x.v[i] = a[i] + t * da[i]; return x; }, [=](double) { return da; });
+    const auto ul = F::trajectory([=](double t) { F::Rn<NU> u; for (int i = 0; i < NU; ++i) u.v[i] = c[i] + t * dc[i]; return u; }, [=](double) { return dc; });
+    F::Mesh<3, 6> mesh(2, 3);
+    mesh.set_N_colloc_ival(1, 4);
+    auto orig = F::ocp_to_nlp(ocp, mesh);
+    auto flat = F::ocp_to_nlp(F::flatten_ocp(ocp, xl, ul), mesh);
+    if (orig.n() != flat.n() || orig.m() != flat.m()) return 101;
+    const std::size_t n = orig.n(), N = mesh.N_colloc();
+    const std::vector<double> taus = mesh.all_nodes();
+    std::vector<double> z(n), xo(n);
+    for (std::size_t k = 0; k < n; ++k) z[k] = 0.3 * std::sin(1.0 + 1.7 * (double)k);
+    z[0] = 1.3;
+    xo   = z;
+    const auto xcol = [&](std::size_t i, int d) { return 1 + NQ + i * NX + d; };
+    const auto ucol = [&](std::size_t i, int d) { return 1 + NQ + (N + 1) * NX + i * NU + d; };
+    for (std::size_t i = 0; i <= N; ++i) {
+      const double t = z[0] * taus[i];
+      for (int d = 0; d < NX; ++d) xo[xcol(i, d)] = xl(t).v[d] + z[xcol(i, d)];
+      if (i < N)
+        for (int d = 0; d < NU; ++d) xo[ucol(i, d)] = ul(t).v[d] + z[ucol(i, d)];
+    }
+    const std::vector<double> go = orig.g(xo), gf = flat.g(z);
+    double eg = 0.0, ej = 0.0, ef = std::fabs(orig.f(xo) - flat.f(z));
+    for (std::size_t r = 0; r < go.size(); ++r) eg = std::max(eg, std::fabs(go[r] - gf[r]));
+    const F::MeshCsr Jo = orig.dg_dx(xo), Jf = flat.dg_dx(z);
+    if (Jo.colind != Jf.colind || Jo.rowptr != Jf.rowptr) return 102;
+    for (std::size_t r = 0; r + 1 < Jo.rowptr.size(); ++r) {
+      double tfcol = 0.0, chain = 0.0, got = 0.0;
+      for (int32_t p = Jo.rowptr[r]; p < Jo.rowptr[r + 1]; ++p) {
+        const std::size_t col = (std::size_t)Jo.colind[p];
+        if (col == 0) { tfcol = Jo.val[p], got = Jf.val[p]; continue; }
+        if (col >= xcol(0, 0) && col < ucol(0, 0)) chain += Jo.val[p] * da[(col - xcol(0, 0)) % NX] * taus[(col - xcol(0, 0)) / NX];
+        else if (col >= ucol(0, 0)) chain += Jo.val[p] * dc[(col - ucol(0, 0)) % NU] * taus[(col - ucol(0, 0)) / NU];
+        ej = std::max(ej, std::fabs(Jo.val[p] - Jf.val[p]));
+      }
+      ej = std::max(ej, std::fabs(tfcol + chain - got));
+    }
+    figures[0] = eg, figures[1] = ej, figures[2] = ef;
+    // the same functions at the same points: what is left is the rounding of xl + e against the collocation of xl (exact
+    // for an affine trajectory), a few ulps of numbers of size 10
+    if (!(eg <= 1e-12) || !(ej <= 1e-12) || !(ef <= 1e-12)) return 103;
+  }
+  // ---- 2 and 3: the planar vehicle around a constant-twist trajectory ----
+  {
+    using Ocp = sfbx::OcpSE2;
+    using S   = sfbx::FlatSizes<Ocp>;
+    const double row[S::stride] = {0.4, -0.3, std::cos(0.7), std::sin(0.7), 0.2, 0.1, 1.1, 0.05, 0.4, 0.3, -0.2, 0.1, 0.3, -0.25, 0.15};
+    const auto model = sfbx::flat_swarm_model<Ocp>(row);
+    const auto focp  = sfbx::flat_agent_ocp(model, 0);
+    F::Mesh<3, 5> mesh(2, 3);
+    auto nlp = F::ocp_to_nlp(focp, mesh);
+    static_assert(F::HessianNLP<decltype(nlp)>);
+    const std::size_t n = nlp.n(), m = nlp.m(), N = mesh.N_colloc();
+    F::NLPSolution s;
+    s.x.resize(n), s.lambda.resize(m);
+    for (std::size_t k = 0; k < n; ++k) s.x[k] = 0.2 * std::sin(0.5 + 1.3 * (double)k);
+    for (std::size_t k = 0; k < m; ++k) s.lambda[k] = 0.5 * std::cos(0.2 + 0.9 * (double)k);
+    s.x[0] = 2.0;
+    const auto flatsol = F::nlpsol_to_ocpsol(focp, mesh, s);
+    const auto sol     = F::unflatten_ocpsol<Ocp::X, Ocp::U, Ocp::Nq, Ocp::Ncr, Ocp::Nce>(flatsol, F::AgentStateTrajectory<sfbx::FlatSwarmModel<Ocp>>{&model, 0},
+                                                                                      F::AgentInputTrajectory<sfbx::FlatSwarmModel<Ocp>>{&model, 0});
+    const std::vector<double> taus = mesh.all_nodes();
+    double er = 0.0;
+    for (std::size_t i = 0; i <= N; ++i) {
+      const double t = s.x[0] * taus[i];
+      const auto de  = rminus(sol.x(t), model.xl(0, t));
+      for (int d = 0; d < S::Nx; ++d) er = std::max(er, std::fabs(de[d] - s.x[1 + S::Nq + i * S::Nx + d]));
+      if (i < N) {
+        const auto dv = rminus(sol.u(t), model.ul(0, t));
+        for (int d = 0; d < S::Nu; ++d) er = std::max(er, std::fabs(dv[d] - s.x[1 + S::Nq + (N + 1) * S::Nx + i * S::Nu + d]));
+      }
+    }
+    figures[3] = er;
+    // log(exp(e)) and the interpolation at a node: a few ulps of numbers below 1
+    if (!(er <= 1e-13)) return 200;
+    if (sol.tf != s.x[0] || sol.Q[0] != s.x[1] || sol.lambda_q[0] != flatsol.lambda_q[0] || sol.lambda_ce != flatsol.lambda_ce) return 201;
+    if (sol.lambda_dyn(0.3) != flatsol.lambda_dyn(0.3) || sol.lambda_cr(0.3) != flatsol.lambda_cr(0.3)) return 202;
+    // ---- 3 ----
+    const double sigma = 0.7;
+    const F::MeshCsc H = nlp.d2l_dx2(s.x, sigma, s.lambda);
+    std::vector<double> Hd(n * n, 0.0);
+    for (std::size_t c = 0; c < n; ++c)
+      for (int32_t p = H.colptr[c]; p < H.colptr[c + 1]; ++p) Hd[(std::size_t)H.rowind[p] * n + c] = Hd[c * n + (std::size_t)H.rowind[p]] = H.val[p];
+    const auto grad = [&](const std::vector<double> & xx) {
+      std::vector<double> gr(n, 0.0);
+      const F::MeshCsr & D = nlp.df_dx(xx);
+      for (std::size_t k = 0; k < D.val.size(); ++k) gr[(std::size_t)D.colind[k]] += sigma * D.val[k];
+      const F::MeshCsr & J = nlp.dg_dx(xx);
+      for (std::size_t r = 0; r < m; ++r)
+        for (int32_t p = J.rowptr[r]; p < J.rowptr[r + 1]; ++p) gr[(std::size_t)J.colind[p]] += s.lambda[r] * J.val[p];
+      return gr;
+    };
+    double eh = 0.0, hmax = 0.0;
+    for (const double v : Hd) hmax = std::max(hmax, std::fabs(v));
+    const double h = 2e-3;  // (chosen below)
+    for (std::size_t c = 0; c < n; ++c) {
+      auto xp = s.x, xm = s.x;
+      xp[c] += h, xm[c] -= h;
+      const auto gp = grad(xp), gm = grad(xm);
+      for (std::size_t r = 0; r < n; ++r) eh = std::max(eh, std::fabs((gp[r] - gm[r]) / (2 * h) - Hd[r * n + c]));
+    }
+    figures[4] = eh, figures[5] = hmax;
+    // The integrand carries no jacobian, so dg holds forward differences at 2^-26 of its flat value: noise of 2 eps |g| 2^26 =
+    // 3e-8 |g| in the gradient.  A central difference of that gradient at step h has noise 3e-8 / h and truncation h^2 / 6
+    // times a third derivative; they meet near h = 2e-3, at 1.5e-5 and some 1e-6.  d2l itself (differences of differences of
+    // the flat values at step eps^(1/4) = 1.2e-4) adds eps |f| / h^2 = 1.5e-8 |f| and h^2 / 12 = 1e-9 times a fourth derivative,
+    // times the weights of the sum.  Bound: 1e-4 (1 + max |H|), a factor of a few over those.  A Hessian off by a factor, or
+    // a missing cross block, is off by 1e-2 or more.
+    if (!(eh <= 1e-4 * (1.0 + hmax))) return 300;
+  }
+  // ---- 4: a Spline as a trajectory: the adapter returns the spline's point, and its velocity is the curve's body velocity ----
+  {
+    std::vector<double> tt;
+    std::vector<F::SE2> gg;
+    for (int k = 0; k <= 4; ++k) tt.push_back(0.5 * k), gg.push_back(F::SE2::exp({0.5 * k * 1.0, 0.1 * k, 0.5 * k * 0.6}));
+    const auto spline = F::fit_spline_cubic<F::SE2>(tt, gg);
+    const auto xl     = F::spline_trajectory(spline);
+    double ev = 0.0;
+    for (const double t : {0.3, 0.9, 1.6}) {
+      const F::SE2 a = xl(t), b = spline(t);
+      if (a.x != b.x || a.y != b.y || a.c != b.c || a.s != b.s) return 400;
+      const double h = 1e-5;
+      const auto d   = rminus(xl(t + h), xl(t - h));
+      const auto v   = xl.velocity(t);
+      for (int i = 0; i < 3; ++i) ev = std::max(ev, std::fabs(d[i] / (2 * h) - v[i]));
+    }
+    figures[6] = ev;
+    // a central difference at 1e-5 of a cubic curve with coefficients of size 1: truncation 1e-10, rounding eps / h = 2e-11
+    if (!(ev <= 1e-8)) return 401;
+  }
   return 0;
 }
 

@@ -1,0 +1,252 @@
+// Harness of flatten_ocp (include/smooth_feedback_amd/ocp_flatten.hpp) for the entries of collocation.cpp (host),
+// models_device.hip (device) and the stand-alone self-test flat_ocp_selftest.cpp: the two example problems of
+// ocp_se2_model.h around per-agent linearisation trajectories, and the Lie operations the flattening adds.
+//
+// Trajectories: per agent a start element and a constant body velocity, as PidSwarmTraj of models_device.hip:
+//   xl(b, t) = rplus(x0_b, t xi_b), dxl = xi_b;   ul(b, t) = u0_b + t du_b, dul = du_b
+// from one row of doubles per agent, [x0 (LieIO<X>::E) | xi (Nx) | u0 (Nu) | du (Nu)].
+// Problems: 0 the planar vehicle (OcpSE2), 1 the rigid body (OcpSE3).
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include <smooth/feedback/ocp_flatten.hpp>
+
+#include "lie_eval.h"
+#include "ocp_se2_model.h"
+
+namespace sfbx {
+
+template<class X, class U>
+struct FlatSwarmTraj {
+  static constexpr int EX = LieIO<X>::E, Nx = X::Dof, Nu = U::Dof, stride = EX + Nx + 2 * Nu;
+  const double * rows = nullptr;  // [agents][stride], host or device memory as the caller runs
+  SFB_LIE_HD X xl(int64_t b, double t) const
+  {
+    const double * p = rows + b * stride;
+    typename X::Tangent a{};
+    for (int i = 0; i < Nx; ++i) a[i] = t * p[EX + i];
+    return rplus(LieIO<X>::load(p), a);
+  }
+  SFB_LIE_HD typename X::Tangent dxl(int64_t b, double) const
+  {
+    const double * p = rows + b * stride;
+    typename X::Tangent a{};
+    for (int i = 0; i < Nx; ++i) a[i] = p[EX + i];
+    return a;
+  }
+  SFB_LIE_HD U ul(int64_t b, double t) const
+  {
+    const double * p = rows + b * stride + EX + Nx;
+    U u;
+    for (int i = 0; i < Nu; ++i) u.v[i] = p[i] + t * p[Nu + i];
+    return u;
+  }
+  SFB_LIE_HD typename U::Tangent dul(int64_t b, double) const
+  {
+    const double * p = rows + b * stride + EX + Nx + Nu;
+    typename U::Tangent a{};
+    for (int i = 0; i < Nu; ++i) a[i] = p[i];
+    return a;
+  }
+};
+
+/// the swarm model of ocp_flatten_device.hpp: the problem's functors and the agents' trajectories
+template<class Ocp>
+struct FlatSwarmModel : Ocp, FlatSwarmTraj<typename Ocp::X, typename Ocp::U> {};
+
+template<class Ocp>
+FlatSwarmModel<Ocp> flat_swarm_model(const double * rows)
+{
+  FlatSwarmModel<Ocp> m{};
+  m.rows = rows;
+  return m;
+}
+
+/// agent b's flattened problem
+template<class Ocp>
+auto flat_agent_ocp(const FlatSwarmModel<Ocp> & model, int64_t b)
+{
+  using M = FlatSwarmModel<Ocp>;
+  return smooth::feedback::flatten_ocp(static_cast<const Ocp &>(model), smooth::feedback::AgentStateTrajectory<M>{&model, b},
+                                       smooth::feedback::AgentInputTrajectory<M>{&model, b});
+}
+
+/// fn.template operator()<Ocp>() for the problem id; false for an unknown id
+template<class Fn>
+inline bool flat_dispatch_problem(int problem, Fn && fn)
+{
+  switch (problem) {
+  case 0: fn.template operator()<OcpSE2>(); return true;
+  case 1: fn.template operator()<OcpSE3>(); return true;
+  default: return false;
+  }
+}
+
+/// sizes of a problem on N nodes: n, nz, ne and the trajectory stride
+template<class Ocp>
+struct FlatSizes {
+  static constexpr int Nx = Ocp::Nx, Nu = Ocp::Nu, Nq = Ocp::Nq, Ncr = Ocp::Ncr, Nce = Ocp::Nce, nz = 1 + Nx + Nu, ne = 1 + 2 * Nx + Nq;
+  static constexpr int stride = FlatSwarmTraj<typename Ocp::X, typename Ocp::U>::stride;
+  static int64_t n(int64_t N) { return 1 + Nq + (N + 1) * Nx + N * Nu; }
+};
+
+/// host pointers of the node arrays, in the layout of smooth::feedback::FlatNodeArrays (ocp_flatten_device.hpp)
+struct FlatNodeOut {
+  double *Ff, *dFf, *Fg, *dFg, *Fcr, *dFcr, *ce, *dce, *theta, *dtheta;
+};
+
+/// the node arrays of agents [0, B) on the host: the flat functors' eval(), the loop the kernel spreads over lanes
+template<class Ocp>
+void flat_nodes_host(const FlatSwarmModel<Ocp> & model, int64_t B, int32_t N, const double * tau, const double * x, const FlatNodeOut & o)
+{
+  using S = FlatSizes<Ocp>;
+  namespace F = smooth::feedback;
+  constexpr int Nx = S::Nx, Nu = S::Nu, Nq = S::Nq, Ncr = S::Ncr, Nce = S::Nce, nz = S::nz, ne = S::ne;
+  const int64_t n = S::n(N);
+  for (int64_t b = 0; b < B; ++b) {
+    const auto flat   = flat_agent_ocp(model, b);
+    const double * xa = x + b * n;
+    const double tf   = xa[0];
+    for (int32_t i = 0; i < N; ++i) {
+      const double t = tf * tau[i];
+      F::Rn<Nx> e;
+      F::Rn<Nu> v;
+      for (int d = 0; d < Nx; ++d) e.v[d] = xa[1 + Nq + (int64_t)i * Nx + d];
+      for (int d = 0; d < Nu; ++d) v.v[d] = xa[1 + Nq + (int64_t)(N + 1) * Nx + (int64_t)i * Nu + d];
+      const int64_t node = b * N + i;
+      const auto put = [&](const auto & val, const auto & J, double * Fv, double * dF, int nf) {
+        for (int r = 0; r < nf; ++r) {
+          Fv[node * nf + r] = val[r];
+          for (int c = 0; c < nz; ++c) dF[(node * nf + r) * nz + c] = J(r, c);
+        }
+      };
+      {
+        F::Vec<Nx> val;
+        F::Mat<Nx, nz> J;
+        flat.f.eval(t, e, v, val, J);
+        put(val, J, o.Ff, o.dFf, Nx);
+      }
+      {
+        F::Vec<Nq> val;
+        F::Mat<Nq, nz> J;
+        flat.g.eval(t, e, v, val, J);
+        put(val, J, o.Fg, o.dFg, Nq);
+      }
+      {
+        F::Vec<Ncr> val;
+        F::Mat<Ncr, nz> J;
+        flat.cr.eval(t, e, v, val, J);
+        put(val, J, o.Fcr, o.dFcr, Ncr);
+      }
+    }
+    F::Rn<Nx> e0, ef;
+    F::Vec<Nq> q;
+    for (int d = 0; d < Nx; ++d) e0.v[d] = xa[1 + Nq + d], ef.v[d] = xa[1 + Nq + (int64_t)N * Nx + d];
+    for (int d = 0; d < Nq; ++d) q[d] = xa[1 + d];
+    {
+      F::Vec<Nce> val;
+      F::Mat<Nce, ne> J;
+      flat.ce.eval(tf, e0, ef, q, val, J);
+      for (int r = 0; r < Nce; ++r) {
+        o.ce[b * Nce + r] = val[r];
+        for (int c = 0; c < ne; ++c) o.dce[(b * Nce + r) * ne + c] = J(r, c);
+      }
+    }
+    {
+      F::Vec<1> val;
+      F::Mat<1, ne> J;
+      flat.theta.eval(tf, e0, ef, q, val, J);
+      o.theta[b] = val[0];
+      for (int c = 0; c < ne; ++c) o.dtheta[b * ne + c] = J(0, c);
+    }
+  }
+}
+
+/// the mesh of the tests (kind 0: two intervals with K = (3, 5)) and of the timing script (kind 1: 13 intervals of 4)
+using FlatMesh = smooth::feedback::Mesh<3, 5>;
+inline FlatMesh flat_mesh(int kind)
+{
+  if (kind == 1) return FlatMesh(13, 4);
+  FlatMesh m(2, 3);
+  m.set_N_colloc_ival(1, 5);
+  return m;
+}
+
+/// OCPNLP of agent b's flattened problem on `mesh` at x [n]: g [m], dg values [nnz], f, df [ne] over (tf | e0 | ef | q).
+/// `differing` (nullable) counts the doubles of g and dg that differ from meshfn::ocp_nlp_assemble over flat_nodes_host's arrays.
+template<class Ocp, class MeshT>
+void flat_nlp_host(const FlatSwarmModel<Ocp> & model, int64_t b, const MeshT & mesh, const double * xb, double * g, double * dg, double * f, double * df,
+                   int64_t * differing)
+{
+  using S = FlatSizes<Ocp>;
+  namespace F = smooth::feedback;
+  auto nlp = F::ocp_to_nlp(flat_agent_ocp(model, b), mesh);
+  const std::vector<double> xv(xb, xb + nlp.n());
+  const F::MeshCsr & J = nlp.dg_dx(xv);
+  const std::vector<double> & gv = nlp.g(xv);
+  if (g) std::copy(gv.begin(), gv.end(), g);
+  if (dg) std::copy(J.val.begin(), J.val.end(), dg);
+  if (f) *f = nlp.f(xv);
+  if (df) {
+    const F::MeshCsr & D = nlp.df_dx(xv);
+    const int64_t N = (int64_t)mesh.N_colloc();
+    for (int a = 0; a < S::ne; ++a) {  // the columns of (tf | e0 | ef | q) in the NLP
+      const int64_t col = a == 0 ? 0 : a <= S::Nx ? 1 + S::Nq + a - 1 : a <= 2 * S::Nx ? 1 + S::Nq + N * S::Nx + a - 1 - S::Nx : 1 + a - 1 - 2 * S::Nx;
+      for (std::size_t k = 0; k < D.val.size(); ++k)
+        if (D.colind[k] == col) df[a] = D.val[k];
+    }
+  }
+  if (differing) {
+    const int32_t N = (int32_t)mesh.N_colloc();
+    const std::vector<double> taus = mesh.all_nodes();
+    std::vector<double> Ff((size_t)N * S::Nx), dFf(Ff.size() * S::nz), Fg((size_t)N * S::Nq), dFg(Fg.size() * S::nz), Fcr((size_t)N * S::Ncr),
+      dFcr(Fcr.size() * S::nz), ce(S::Nce), dce((size_t)S::Nce * S::ne), th(1), dth(S::ne);
+    FlatSwarmModel<Ocp> one = model;
+    one.rows                = model.rows + b * S::stride;
+    flat_nodes_host(one, 1, N, taus.data(), xb, FlatNodeOut{Ff.data(), dFf.data(), Fg.data(), dFg.data(), Fcr.data(), dFcr.data(), ce.data(), dce.data(), th.data(), dth.data()});
+    std::vector<double> g2(gv.size()), dg2(J.val.size());
+    F::meshfn::ocp_nlp_assemble(nlp.tables(), F::meshfn::OcpNlpAgent{xb, Ff.data(), dFf.data(), Fg.data(), dFg.data(), Fcr.data(), dFcr.data(), ce.data(), dce.data()},
+                                g2.data(), dg2.data());
+    int64_t bad = 0;
+    const std::vector<double> & g1 = nlp.g(xv);
+    const F::MeshCsr & J1          = nlp.dg_dx(xv);
+    for (std::size_t k = 0; k < g2.size(); ++k) bad += std::memcmp(&g1[k], &g2[k], sizeof(double)) != 0;
+    for (std::size_t k = 0; k < dg2.size(); ++k) bad += std::memcmp(&J1.val[k], &dg2[k], sizeof(double)) != 0;
+    *differing = bad;
+  }
+}
+
+// ---- the Lie operations the flattening adds: op 0 dr_exp(a) (in T, out T x T), op 1 d/de (dr_expinv(e) w) (in e, w; out T x T) ----
+// groups: 1 SE2, 2 SO3, 5 SE3 (the ids of lie_eval.h), 6 Bundle<SE3, Rn<6>>, 7 Bundle<SE2, Rn<2>>
+template<class Fn>
+inline bool flat_lie_dispatch(int group, Fn && fn)
+{
+  switch (group) {
+  case 1: fn.template operator()<SE2>(); return true;
+  case 2: fn.template operator()<SO3>(); return true;
+  case 5: fn.template operator()<SE3>(); return true;
+  case 6: fn.template operator()<X12B>(); return true;
+  case 7: fn.template operator()<X5>(); return true;
+  default: return false;
+  }
+}
+template<class G>
+SFB_LIE_HD void flat_lie_item(int op, const double * in, double * out)
+{
+  constexpr int T = G::Dof;
+  typename G::Tangent a{}, w{};
+  for (int i = 0; i < T; ++i) a[i] = in[i];
+  Mat<T, T> m;
+  if (op == 0) {
+    m = G::dr_exp(a);
+  } else {
+    for (int i = 0; i < T; ++i) w[i] = in[T + i];
+    m = smooth::feedback::detail::FlatDExpinv<G>::apply(a, w);
+  }
+  for (int i = 0; i < T * T; ++i) out[i] = m.a[i];
+}
+
+}  // namespace sfbx

@@ -200,6 +200,31 @@ int sfbx_mpc_tick_dyn_error_host(int variant, int K, double tf, double t, const 
 /* the reference's mesh and dyn-error tests as caller code against <smooth/feedback/collocation/{mesh,dyn_error}.hpp>: 0, or the number of
  * the first expectation that fails */
 int sfbx_test_collocation_api(void);
+
+/* ---- flatten_ocp (include/smooth_feedback_amd/ocp_flatten.hpp; harness: examples/flat_ocp_harness.h) ----
+ * The Lie operations the flattening adds, per item: op 0 dr_exp(a) (in [T], out [T x T] column-major), op 1
+ * d/de (dr_expinv(e) w) (in [e | w], out [T x T]).  Groups: 1 SE2, 2 SO3, 5 SE3, 6 Bundle<SE3, Rn<6>>, 7 Bundle<SE2, Rn<2>>.
+ * -1 for anything else.  sfbx_flat_lie_eval_device (models_device.hip) runs the same item function, one GPU thread per item. */
+int sfbx_flat_lie_eval(int group, int op, int64_t count, const double *in, double *out);
+/* Problems: 0 the planar vehicle on Bundle<SE2, Rn<2>>, 1 the rigid body on Bundle<SE3, Rn<6>> (examples/ocp_se2_model.h).
+ * sizes [7]: nx, nu, nq, ncr, nce, doubles per trajectory row, n of the NLP on N nodes. */
+int sfbx_flat_ocp_sizes(int problem, int32_t N, int32_t *sizes);
+/* The flattened problem at the nodes tau [N] of `agents` agents on the host (`threads` threads): x [agents][n] in the NLP's
+ * layout, traj [agents][row] = [x0 | xi | u0 | du] (xl = rplus(x0, t xi), ul = u0 + t du).  Out, in the layout of
+ * sfb_ocp_nlp_batch: Ff, dFf, Fg, dFg, Fcr, dFcr, ce, dce, and theta [agents], dtheta [agents][1 + 2 nx + nq]. */
+int sfbx_flat_ocp_nodes_host(int problem, int64_t agents, int32_t N, const double *tau, const double *x, const double *traj,
+                             double *Ff, double *dFf, double *Fg, double *dFg, double *Fcr, double *dFcr, double *ce,
+                             double *dce, double *theta, double *dtheta, int threads);
+/* ocp_to_nlp(flatten_ocp(problem, agent's trajectories), mesh) per agent: g [agents][m], dg [agents][nnz], f [agents], df
+ * [agents][1 + 2 nx + nq] over (tf | e0 | ef | q); differing [agents] (nullable) counts the doubles of g and dg that are not
+ * bit-identical to meshfn::ocp_nlp_assemble over the arrays of sfbx_flat_ocp_nodes_host.  mesh_kind 0: two intervals with
+ * K = (3, 5); 1: 13 intervals of 4.  sizes [4] (nullable): n, m, nnz, N; taus [N + 1] (nullable).  x NULL: sizes only. */
+int sfbx_flat_ocp_nlp_host(int problem, int mesh_kind, int64_t agents, const double *x, const double *traj, double *g,
+                           double *dg, double *f, double *df, int64_t *differing, int32_t *sizes, double *taus);
+/* Scenarios written as caller code against <smooth/feedback/ocp_flatten.hpp> (a flattened Rn problem against its original,
+ * the unflatten round trip, d2l_dx2 against differences of the gradient, a Spline as a trajectory); figures [8]; 0 or the first failing expectation. */
+int sfbx_test_flatten_api(double *figures);
+
 /* mesh_eval (fn 0) / mesh_integrate (1) / mesh_dyn (2) of mesh_function.hpp at order deriv, differentiating the integrand by its
  * members (numerical 0) or by differences (1), on the script's mesh (also <1,2> and <4,6>).  Shapes 0 .. 3: an integrand given
  * as a term table on Rn state and input with (nx, nu, nf) = (3,2,3), (3,2,1), (1,0,1), (12,2,12): terms [nterms][5] rows

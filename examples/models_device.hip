@@ -12,8 +12,10 @@
 #include <smooth_feedback_amd/ekf_device.hpp>
 #include <smooth_feedback_amd/mpc_device.hpp>
 #include <smooth_feedback_amd/multi_device.hpp>
+#include <smooth_feedback_amd/ocp_flatten_device.hpp>
 #include <smooth_feedback_amd/pid_device.hpp>
 
+#include "flat_ocp_harness.h"
 #include "lie_eval.h"
 #include "rigid_body_model.h"
 #include "vehicle_model.h"
@@ -672,6 +674,198 @@ int sfbx_pid_swarm_spline_device(int64_t batch, double t0, double dt, int64_t st
     rc = -2;
   }
   return rc;
+}
+
+}  // extern "C"
+
+// ---- flatten_ocp on the device (ocp_flatten_device.hpp; harness: flat_ocp_harness.h) ----
+namespace {
+template<class G>
+__global__ void __launch_bounds__(64) flat_lie_kernel(const int op, const int64_t count, const double * __restrict__ in, double * __restrict__ out)
+{
+  constexpr int T   = G::Dof;
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= count) return;
+  sfbx::flat_lie_item<G>(op, in + k * (op == 0 ? T : 2 * T), out + k * T * T);
+}
+
+void flat_ok(hipError_t e, const char * what) { detail::hip_check(e, "flat_ocp_device", what); }
+
+// the ten node arrays of `agents` agents on N nodes in one block, and their sizes in the order of FlatNodeArrays
+template<class Ocp>
+struct FlatNodeBlock {
+  using S = sfbx::FlatSizes<Ocp>;
+  size_t len[10];
+  FlatNodeArrays arr{};
+  FlatNodeBlock(detail::DeviceArena & a, size_t B, size_t N)
+  {
+    const size_t l[10] = {B * N * S::Nx, B * N * S::Nx * S::nz, B * N * S::Nq, B * N * S::Nq * S::nz, B * N * S::Ncr, B * N * S::Ncr * S::nz,
+                          B * S::Nce,    B * S::Nce * S::ne,    B,             B * S::ne};
+    double ** slot[10] = {&arr.Ff, &arr.dFf, &arr.Fg, &arr.dFg, &arr.Fcr, &arr.dFcr, &arr.ce, &arr.dce, &arr.theta, &arr.dtheta};
+    for (int k = 0; k < 10; ++k) len[k] = l[k], a.add(slot[k], l[k]);
+  }
+  void download(double * const * host) const
+  {
+    const double * dev[10] = {arr.Ff, arr.dFf, arr.Fg, arr.dFg, arr.Fcr, arr.dFcr, arr.ce, arr.dce, arr.theta, arr.dtheta};
+    for (int k = 0; k < 10; ++k)
+      if (host[k]) flat_ok(detail::download(host[k], dev[k], len[k]), "download node arrays");
+  }
+};
+}  // namespace
+
+extern "C" {
+
+/* sfbx_flat_lie_eval (models.h) on the GPU: one thread per item runs the same item function. */
+int sfbx_flat_lie_eval_device(int group, int op, int64_t count, const double * in, double * out)
+{
+  if (count < 0 || op < 0 || op > 1) return -1;
+  try {
+    const bool ok = sfbx::flat_lie_dispatch(group, [&]<class G>() {
+      constexpr size_t T = G::Dof;
+      if (count == 0) return;
+      double *din, *dout;
+      detail::DeviceArena a;
+      a.add(&din, (size_t)count * (op == 0 ? T : 2 * T)); a.add(&dout, (size_t)count * T * T);
+      const detail::DeviceBlock blk(a, "flat_ocp_device");
+      flat_ok(detail::upload(din, in, (size_t)count * (op == 0 ? T : 2 * T)), "upload");
+      hipLaunchKernelGGL((flat_lie_kernel<G>), detail::lane_grid(count), dim3(64), 0, nullptr, op, count, din, dout);
+      flat_ok(hipGetLastError(), "flat_lie_kernel");
+      flat_ok(hipDeviceSynchronize(), "synchronise");
+      flat_ok(detail::download(out, dout, (size_t)count * T * T), "download");
+    });
+    return ok ? 0 : -1;
+  } catch (const std::exception & e) {
+    std::fprintf(stderr, "sfbx_flat_lie_eval_device: %s\n", e.what());
+    return -2;
+  }
+}
+
+/* sfbx_flat_ocp_nodes_host (models.h) on the GPU: flat_ocp_nodes_kernel alone over the nodes tau [N]; out arrays nullable. */
+int sfbx_flat_ocp_nodes_device(int problem, int64_t agents, int32_t N, const double * tau, const double * x, const double * traj, double * Ff,
+                               double * dFf, double * Fg, double * dFg, double * Fcr, double * dFcr, double * ce, double * dce, double * theta,
+                               double * dtheta)
+{
+  if (agents < 1 || N < 1) return -1;
+  try {
+    const bool ok = sfbx::flat_dispatch_problem(problem, [&]<class Ocp>() {
+      using S = sfbx::FlatSizes<Ocp>;
+      const size_t B = (size_t)agents, n = (size_t)S::n(N);
+      double *dtau, *dx, *dtraj;
+      detail::DeviceArena a;
+      a.add(&dtau, (size_t)N); a.add(&dx, B * n); a.add(&dtraj, B * S::stride);
+      FlatNodeBlock<Ocp> nodes(a, B, (size_t)N);
+      const detail::DeviceBlock blk(a, "flat_ocp_device");
+      flat_ok(detail::upload(dtau, tau, (size_t)N), "upload tau");
+      flat_ok(detail::upload(dx, x, B * n), "upload x");
+      flat_ok(detail::upload(dtraj, traj, B * S::stride), "upload traj");
+      const auto model = sfbx::flat_swarm_model<Ocp>(dtraj);
+      flat_ok(flat_ocp_nodes_launch<Ocp>(model, agents, N, dtau, dx, nodes.arr, nullptr), "flat_ocp_nodes_kernel");
+      flat_ok(hipDeviceSynchronize(), "synchronise");
+      double * const host[10] = {Ff, dFf, Fg, dFg, Fcr, dFcr, ce, dce, theta, dtheta};
+      nodes.download(host);
+    });
+    return ok ? 0 : -1;
+  } catch (const std::exception & e) {
+    std::fprintf(stderr, "sfbx_flat_ocp_nodes_device: %s\n", e.what());
+    return -2;
+  }
+}
+
+/* FlatOCPSwarmDevice on the mesh of sfbx_flat_ocp_nlp_host (models.h): eval() on the null stream -> g [agents][m], dg
+ * [agents][nnz], f [agents], df [agents][1 + 2 nx + nq], and the front's node arrays (nodes [10] host pointers in the order of
+ * FlatNodeArrays, each nullable).  side != 0: then once more on a non-blocking stream, behind a queue of large memsets and the
+ * upload of x on that stream (x on the device is NaN until that upload lands) -> g2, dg2, f2, df2.  info [4]: free device
+ * memory before and after a further eval(), the front's bytes, its n.  reps > 0: seconds [2] = the least time between device
+ * events of the node kernel and of sfb_ocp_nlp_batch over reps warmed runs each. */
+int sfbx_flat_ocp_front_device(int problem, int mesh_kind, int64_t agents, const double * x, const double * traj, int side, int reps, double * g,
+                               double * dg, double * f, double * df, double * const * nodes, double * g2, double * dg2, double * f2, double * df2,
+                               int64_t * info, double * seconds)
+{
+  if (agents < 1) return -1;
+  try {
+    const auto mesh = sfbx::flat_mesh(mesh_kind);
+    const bool ok   = sfbx::flat_dispatch_problem(problem, [&]<class Ocp>() {
+      using S     = sfbx::FlatSizes<Ocp>;
+      using Model = sfbx::FlatSwarmModel<Ocp>;
+      const size_t B = (size_t)agents;
+      double * dtraj;
+      detail::DeviceArena at;
+      at.add(&dtraj, B * S::stride);
+      const detail::DeviceBlock tblk(at, "flat_ocp_device");
+      flat_ok(detail::upload(dtraj, traj, B * S::stride), "upload traj");
+      FlatOCPSwarmDevice<Ocp, Model, sfbx::FlatMesh> front(Ocp{}, sfbx::flat_swarm_model<Ocp>(dtraj), mesh, agents);
+      const size_t n = (size_t)front.n(), m = (size_t)front.m(), nnz = (size_t)front.nnz();
+      double *dx, *dg_, *ddg, *df_, *ddf, *spin;
+      const size_t spin_len = side ? (size_t)8 << 20 : 0;  // 64 MB
+      detail::DeviceArena a;
+      a.add(&dx, B * n); a.add(&dg_, B * m); a.add(&ddg, B * nnz); a.add(&df_, B); a.add(&ddf, B * S::ne); a.add(&spin, spin_len);
+      const detail::DeviceBlock blk(a, "flat_ocp_device");
+      flat_ok(detail::upload(dx, x, B * n), "upload x");
+      front.eval(dx, dg_, ddg, df_, ddf, nullptr);
+      flat_ok(hipDeviceSynchronize(), "synchronise");
+      const auto fetch = [&](double * hg, double * hdg, double * hf, double * hdf) {
+        if (hg) flat_ok(detail::download(hg, dg_, B * m), "download g");
+        if (hdg) flat_ok(detail::download(hdg, ddg, B * nnz), "download dg");
+        if (hf) flat_ok(detail::download(hf, df_, B), "download f");
+        if (hdf) flat_ok(detail::download(hdf, ddf, B * S::ne), "download df");
+      };
+      fetch(g, dg, f, df);
+      if (nodes) {
+        const FlatNodeArrays & arr = front.node_arrays();
+        const size_t N             = (size_t)front.N_colloc();
+        const size_t len[8]    = {B * N * S::Nx, B * N * S::Nx * S::nz, B * N * S::Nq, B * N * S::Nq * S::nz, B * N * S::Ncr, B * N * S::Ncr * S::nz, B * S::Nce, B * S::Nce * S::ne};
+        const double * dev[8]  = {arr.Ff, arr.dFf, arr.Fg, arr.dFg, arr.Fcr, arr.dFcr, arr.ce, arr.dce};
+        for (int k = 0; k < 8; ++k)
+          if (nodes[k]) flat_ok(detail::download(nodes[k], dev[k], len[k]), "download node arrays");
+      }
+      if (info) {
+        size_t free0 = 0, free1 = 0, total = 0;
+        flat_ok(hipMemGetInfo(&free0, &total), "hipMemGetInfo");
+        front.eval(dx, dg_, ddg, df_, ddf, nullptr);
+        flat_ok(hipDeviceSynchronize(), "synchronise");
+        flat_ok(hipMemGetInfo(&free1, &total), "hipMemGetInfo");
+        info[0] = (int64_t)free0, info[1] = (int64_t)free1, info[2] = (int64_t)front.device_bytes(), info[3] = (int64_t)n;
+      }
+      if (side) {
+        hipStream_t st;
+        flat_ok(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreateWithFlags");
+        flat_ok(hipMemset(dx, 0xFF, B * n * sizeof(double)), "poison x");  // NaN until the upload below lands
+        flat_ok(hipMemset(dg_, 0, B * m * sizeof(double)), "clear g");
+        flat_ok(hipMemset(ddg, 0, B * nnz * sizeof(double)), "clear dg");
+        flat_ok(hipMemset(df_, 0, B * sizeof(double)), "clear f");
+        flat_ok(hipMemset(ddf, 0, B * S::ne * sizeof(double)), "clear df");
+        flat_ok(hipDeviceSynchronize(), "synchronise");
+        for (int k = 0; k < 8; ++k) flat_ok(hipMemsetAsync(spin, k, spin_len * sizeof(double), st), "hipMemsetAsync");
+        flat_ok(hipMemcpyAsync(dx, x, B * n * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+        front.eval(dx, dg_, ddg, df_, ddf, st);
+        flat_ok(hipStreamSynchronize(st), "hipStreamSynchronize");
+        fetch(g2, dg2, f2, df2);
+        flat_ok(hipStreamDestroy(st), "hipStreamDestroy");
+      }
+      if (reps > 0 && seconds) {
+        hipEvent_t e0, e1;
+        flat_ok(hipEventCreate(&e0), "event"); flat_ok(hipEventCreate(&e1), "event");
+        float best[2] = {1e30f, 1e30f};
+        for (int rep = 0; rep <= reps; ++rep)  // the first is the warm-up
+          for (int half = 0; half < 2; ++half) {
+            flat_ok(hipEventRecord(e0, nullptr), "record");
+            if (half == 0) flat_ok(front.nodes(dx, df_, ddf, nullptr), "flat_ocp_nodes_kernel");
+            else if (front.assemble(dx, dg_, ddg, nullptr) != SFB_OK) throw std::runtime_error(sfb_last_error());
+            flat_ok(hipEventRecord(e1, nullptr), "record");
+            flat_ok(hipEventSynchronize(e1), "synchronise");
+            float ms = 0;
+            flat_ok(hipEventElapsedTime(&ms, e0, e1), "elapsed");
+            if (rep > 0 && ms < best[half]) best[half] = ms;
+          }
+        flat_ok(hipEventDestroy(e0), "event"); flat_ok(hipEventDestroy(e1), "event");
+        seconds[0] = 1e-3 * best[0], seconds[1] = 1e-3 * best[1];
+      }
+    });
+    return ok ? 0 : -1;
+  } catch (const std::exception & e) {
+    std::fprintf(stderr, "sfbx_flat_ocp_front_device: %s\n", e.what());
+    return -2;
+  }
 }
 
 }  // extern "C"

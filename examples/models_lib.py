@@ -719,3 +719,112 @@ def ocp_nlp_hess_host(spec, ops, dims, tables, bounds, x, lam, sigma, numerical=
 
 def test_ocp_to_nlp_api():
     return lib().sfbx_test_ocp_to_nlp_api()
+
+
+# ---- flatten_ocp (include/smooth_feedback_amd/ocp_flatten.hpp; examples/flat_ocp_harness.h) ----
+FLAT_GROUPS = dict(SE2=(1, 3), SO3=(2, 3), SE3=(5, 6), X12B=(6, 12), X5=(7, 5))
+FLAT_PROBLEMS = dict(se2=0, se3=1)
+FLAT_NODE_KEYS = ("Ff", "dFf", "Fg", "dFg", "Fcr", "dFcr", "ce", "dce", "theta", "dtheta")
+
+
+def flat_lie_eval(group, op, a, w=None, device=False):
+    """op "dr_exp": dr_exp(a) per row of a [count][T]; op "d_expinv": d/de (dr_expinv(e) w) at e = a.  Returns [count][T][T]
+    (row, column).  device=True: one GPU thread per item runs the same item function."""
+    gid, T = FLAT_GROUPS[group]
+    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, T)
+    inp = a if op == "dr_exp" else np.ascontiguousarray(np.concatenate([a, np.asarray(w, dtype=np.float64).reshape(-1, T)], axis=1))
+    out = np.full((len(a), T * T), np.nan)
+    fn = dev_lib().sfbx_flat_lie_eval_device if device else lib().sfbx_flat_lie_eval
+    rc = fn(gid, 0 if op == "dr_exp" else 1, C.c_int64(len(a)), _p(inp), _p(out))
+    assert rc == 0, rc
+    return out.reshape(len(a), T, T).transpose(0, 2, 1)
+
+
+def flat_ocp_sizes(problem, N):
+    """dict nx, nu, nq, ncr, nce, row (doubles per trajectory row), n (NLP variables on N nodes), nz, ne"""
+    v = np.zeros(7, np.int32)
+    assert lib().sfbx_flat_ocp_sizes(FLAT_PROBLEMS[problem], N, _p(v)) == 0
+    d = dict(zip(("nx", "nu", "nq", "ncr", "nce", "row", "n"), [int(k) for k in v]))
+    d["nz"], d["ne"] = 1 + d["nx"] + d["nu"], 1 + 2 * d["nx"] + d["nq"]
+    return d
+
+
+def _flat_node_arrays(d, B, N):
+    nz, ne = d["nz"], d["ne"]
+    return dict(Ff=np.full((B, N, d["nx"]), np.nan), dFf=np.full((B, N, d["nx"], nz), np.nan), Fg=np.full((B, N, d["nq"]), np.nan),
+                dFg=np.full((B, N, d["nq"], nz), np.nan), Fcr=np.full((B, N, d["ncr"]), np.nan), dFcr=np.full((B, N, d["ncr"], nz), np.nan),
+                ce=np.full((B, d["nce"]), np.nan), dce=np.full((B, d["nce"], ne), np.nan), theta=np.full(B, np.nan), dtheta=np.full((B, ne), np.nan))
+
+
+def flat_ocp_nodes(problem, tau, x, traj, device=False, threads=1):
+    """The flattened problem at the nodes tau [N] for agents x [B][n], traj [B][row]: dict of the arrays sfb_ocp_nlp_batch takes
+    (Ff [B][N][nx], dFf [B][N][nx][nz], ..., ce, dce) and theta [B], dtheta [B][ne].  Host front, or (device=True)
+    flat_ocp_nodes_kernel of ocp_flatten_device.hpp."""
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    N = len(tau)
+    d = flat_ocp_sizes(problem, N)
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, d["n"])
+    traj = np.ascontiguousarray(traj, dtype=np.float64).reshape(len(x), d["row"])
+    out = _flat_node_arrays(d, len(x), N)
+    ptrs = [_p(out[k]) for k in FLAT_NODE_KEYS]
+    if device:
+        rc = dev_lib().sfbx_flat_ocp_nodes_device(FLAT_PROBLEMS[problem], C.c_int64(len(x)), N, _p(tau), _p(x), _p(traj), *ptrs)
+    else:
+        rc = lib().sfbx_flat_ocp_nodes_host(FLAT_PROBLEMS[problem], C.c_int64(len(x)), N, _p(tau), _p(x), _p(traj), *ptrs, threads)
+    assert rc == 0, rc
+    return out
+
+
+def flat_ocp_mesh(problem, mesh_kind=0):
+    """dict n, m, nnz, N, taus [N + 1] of the harness mesh (0: two intervals with K = (3, 5); 1: 13 intervals of 4)"""
+    sizes = np.zeros(4, np.int32); taus = np.zeros(128)
+    assert lib().sfbx_flat_ocp_nlp_host(FLAT_PROBLEMS[problem], mesh_kind, C.c_int64(1), None, None, None, None, None, None, None, _p(sizes), _p(taus)) == 0
+    n, m, nnz, N = [int(v) for v in sizes]
+    return dict(n=n, m=m, nnz=nnz, N=N, taus=taus[:N + 1].copy())
+
+
+def flat_ocp_nlp_host(problem, x, traj, mesh_kind=0):
+    """ocp_to_nlp(flatten_ocp(...), mesh) per agent on the host: dict g [B][m], dg [B][nnz], f [B], df [B][ne], differing [B]
+    (doubles of g, dg not bit-identical to meshfn::ocp_nlp_assemble over the host node arrays)."""
+    s = flat_ocp_mesh(problem, mesh_kind)
+    d = flat_ocp_sizes(problem, s["N"])
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, s["n"])
+    B = len(x)
+    traj = np.ascontiguousarray(traj, dtype=np.float64).reshape(B, d["row"])
+    out = dict(g=np.full((B, s["m"]), np.nan), dg=np.full((B, s["nnz"]), np.nan), f=np.full(B, np.nan), df=np.full((B, d["ne"]), np.nan),
+               differing=np.full(B, -1, np.int64))
+    rc = lib().sfbx_flat_ocp_nlp_host(FLAT_PROBLEMS[problem], mesh_kind, C.c_int64(B), _p(x), _p(traj), _p(out["g"]), _p(out["dg"]), _p(out["f"]),
+                                      _p(out["df"]), _p(out["differing"]), None, None)
+    assert rc == 0, rc
+    return out
+
+
+def flat_ocp_front_device(problem, x, traj, mesh_kind=0, side=False, reps=0):
+    """FlatOCPSwarmDevice::eval on the GPU (sfbx_flat_ocp_front_device): dict g, dg, f, df, the front's node arrays (Ff .. dce),
+    info (free device memory before and after a further eval, the front's bytes, n); side=True adds g2, dg2, f2, df2 of a run
+    on a non-blocking stream behind pending work; reps > 0 adds seconds (node kernel, sfb_ocp_nlp_batch)."""
+    s = flat_ocp_mesh(problem, mesh_kind)
+    d = flat_ocp_sizes(problem, s["N"])
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, s["n"])
+    B = len(x)
+    traj = np.ascontiguousarray(traj, dtype=np.float64).reshape(B, d["row"])
+    out = dict(g=np.full((B, s["m"]), np.nan), dg=np.full((B, s["nnz"]), np.nan), f=np.full(B, np.nan), df=np.full((B, d["ne"]), np.nan),
+               info=np.zeros(4, np.int64), seconds=np.zeros(2))
+    nodes = _flat_node_arrays(d, B, s["N"])
+    out.update({k: nodes[k] for k in FLAT_NODE_KEYS[:8]})
+    node_ptrs = (C.c_void_p * 8)(*[nodes[k].ctypes.data for k in FLAT_NODE_KEYS[:8]])
+    second = [None] * 4
+    if side:
+        for k in ("g", "dg", "f", "df"):
+            out[k + "2"] = np.full_like(out[k], np.nan)
+        second = [_p(out[k + "2"]) for k in ("g", "dg", "f", "df")]
+    rc = dev_lib().sfbx_flat_ocp_front_device(FLAT_PROBLEMS[problem], mesh_kind, C.c_int64(B), _p(x), _p(traj), int(side), int(reps), _p(out["g"]),
+                                              _p(out["dg"]), _p(out["f"]), _p(out["df"]), node_ptrs, *second, _p(out["info"]), _p(out["seconds"]))
+    assert rc == 0, rc
+    return out
+
+
+def test_flatten_api():
+    """(code, figures [8]) of sfbx_test_flatten_api: 0, or the first failing expectation"""
+    fig = np.zeros(8)
+    return int(lib().sfbx_test_flatten_api(_p(fig))), fig

@@ -9,6 +9,8 @@
 // 8 ("smooth semantics the host side must restate").  Every operation is pinned to 60-digit values computed from the
 // matrix groups (tests/golden/lie_reference.npz; tests/test_lie_host.py on the host, tests/test_lie_gpu.py in device code;
 // SE(3): tests/golden/lie_se3_reference.npz, tests/test_lie_se3_host.py, tests/test_lie_se3_gpu.py).
+// dr_exp, the right Jacobian of exp (what ocp_flatten.hpp needs), is pinned by tests/golden/flatten_reference.npz
+// (tests/test_flatten_host.py, tests/test_flatten_gpu.py).
 #pragma once
 #include <array>
 #include <cmath>
@@ -99,6 +101,7 @@ struct Rn {
   SFB_LIE_HD static Mat<N, N> ad(const Tangent &) { return Mat<N, N>::Zero(); }
   SFB_LIE_HD Tangent Ad(const Tangent &a) const { return a; }  // Ad_g a = vee(g hat(a) g^-1): commutative
   SFB_LIE_HD static Mat<N, N> dr_expinv(const Tangent &) { return Mat<N, N>::Identity(); }
+  SFB_LIE_HD static Mat<N, N> dr_exp(const Tangent &) { return Mat<N, N>::Identity(); }
 };
 
 namespace detail {
@@ -186,6 +189,8 @@ struct SE2 {
     const Mat<3, 3> A = ad(a);
     return Mat<3, 3>::Identity() + 0.5 * A + k * (A * A);
   }
+  // right Jacobian of exp, sum_n (-1)^n ad^n / (n + 1)! with ad^3 = -th^2 ad:  I - (1 - cos th)/th^2 ad + (th - sin th)/th^3 ad^2
+  SFB_LIE_HD static Mat<3, 3> dr_exp(const Tangent &a);
 };
 
 // ---- SO(3): unit quaternion (w, x, y, z), tangent = body angular velocity ----
@@ -255,6 +260,7 @@ struct SO3 {
     const Mat<3, 3> A = ad(a);
     return Mat<3, 3>::Identity() + 0.5 * A + k * (A * A);
   }
+  SFB_LIE_HD static Mat<3, 3> dr_exp(const Tangent &a);  // as SE2's, th = |a|
 };
 
 namespace detail {
@@ -310,7 +316,38 @@ SFB_LIE_HD inline Vec<3> cross(const Vec<3> &a, const Vec<3> &b)
 {
   return {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
 }
+// d/dt of B(t) = (1 - cos th) / th^2 (Odd = false) and of C(t) = (th - sin th) / th^3 (Odd = true), t = th^2: the coefficients
+// that couple v and w in SE3::dr_exp.
+//   B' = (sin th / th - 2 B) / (2 t) = sum_{n >= 1} (-1)^n n t^(n-1) / (2n + 2)!,
+//   C' = (B - 3 C) / (2 t)           = sum_{n >= 1} (-1)^n n t^(n-1) / (2n + 3)!.
+// The closed forms divide a difference that vanishes like t / 12 (t / 60) by t: absolute error 2 eps / t.  The series
+// through n = 12 leaves 13 t^12 / 28! = 4e-29 t^12 (B') and has no cancellation to speak of up to t = 4 (first terms 0.042,
+// 0.011 t); the switch sits there, where the closed form's error is 1e-16 on a value of 0.03.
+template<bool Odd>
+SFB_LIE_HD inline double dr_exp_dcoef(double t)
+{
+  if (t < 4.0) {
+    double fact = Odd ? 120.0 : 24.0, tp = 1.0, acc = 0.0;  // (2n + 2)! or (2n + 3)! at n = 1
+    for (int n = 1; n <= 12; ++n) {
+      acc += ((n & 1) ? -double(n) : double(n)) * tp / fact;
+      tp *= t;
+      fact *= Odd ? double(2 * n + 4) * double(2 * n + 5) : double(2 * n + 3) * double(2 * n + 4);
+    }
+    return acc;
+  }
+  const double th = std::sqrt(t), B = one_minus_cos_over_th2(t);
+  if constexpr (Odd) return (B - 3.0 * th_minus_sin_over_th3(t)) / (2.0 * t);
+  else return (std::sin(th) / th - 2.0 * B) / (2.0 * t);
+}
+// I - B ad + C ad^2 for a group with ad^3 = -th^2 ad (SE2, SO3)
+SFB_LIE_HD inline Mat<3, 3> dr_exp_rot(const Mat<3, 3> &A, double th2)
+{
+  return Mat<3, 3>::Identity() + (-one_minus_cos_over_th2(th2)) * A + th_minus_sin_over_th3(th2) * (A * A);
+}
 }  // namespace detail
+
+SFB_LIE_HD inline Mat<3, 3> SE2::dr_exp(const Tangent &a) { return detail::dr_exp_rot(ad(a), a[2] * a[2]); }
+SFB_LIE_HD inline Mat<3, 3> SO3::dr_exp(const Tangent &a) { return detail::dr_exp_rot(ad(a), a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); }
 
 // ---- SE(3): translation p and unit quaternion q (as SO3); tangent (v_0, v_1, v_2, w_0, w_1, w_2), body velocities ----
 struct SE3 {
@@ -402,6 +439,25 @@ struct SE3 {
       }
     return m;
   }
+  // right Jacobian of exp in the same block form [[J, Q], [0, J]]: J = SO3::dr_exp(w) = I - B W + C W^2 and Q its derivative
+  // in the direction v:  Q = -B V + C (W V + V W) + 2 (w.v) (-B'(th^2) W + C'(th^2) W^2)
+  SFB_LIE_HD static Mat<6, 6> dr_exp(const Tangent &a)
+  {
+    const Vec<3> v{a[0], a[1], a[2]}, w{a[3], a[4], a[5]};
+    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], wv2 = 2.0 * (w[0] * v[0] + w[1] * v[1] + w[2] * v[2]);
+    const double B = detail::one_minus_cos_over_th2(th2), C = detail::th_minus_sin_over_th3(th2);
+    const double dB = wv2 * detail::dr_exp_dcoef<false>(th2), dC = wv2 * detail::dr_exp_dcoef<true>(th2);
+    const Mat<3, 3> W = SO3::ad(w), V = SO3::ad(v), W2 = W * W, WV = W * V;
+    Mat<6, 6> m{};
+    for (int c = 0; c < 3; ++c)
+      for (int r = 0; r < 3; ++r) {
+        const double J = (r == c ? 1.0 : 0.0) - B * W(r, c) + C * W2(r, c);
+        m(r, c) = J;
+        m(3 + r, 3 + c) = J;
+        m(r, 3 + c) = -B * V(r, c) + C * (WV(r, c) + WV(c, r)) - dB * W(r, c) + dC * W2(r, c);
+      }
+    return m;
+  }
 };
 
 // ---- Bundle<G...>: direct product, tangent = concatenation (first part first) ----
@@ -472,6 +528,7 @@ struct Bundle {
   {
     return blockdiag(a, [](auto g, const auto &ai) { return decltype(g)::dr_expinv(ai); });
   }
+  SFB_LIE_HD static Mat<Dof, Dof> dr_exp(const Tangent &a) { return blockdiag(a, [](auto g, const auto &ai) { return decltype(g)::dr_exp(ai); }); }
 
 private:
   template<class F>

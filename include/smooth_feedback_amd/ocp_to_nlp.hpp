@@ -24,11 +24,11 @@
 //     J (rows x (1 + 2 Nx + Nq)), columns (tf | x0 | xf | q), and hessian(tf, x0, xf, q, H) with the rows' Hessians side by
 //     side.  (detail::jac_end / hess_end of ocp_to_qp.hpp hold tf fixed and carry no q blocks, which the NLP needs.)
 //   * Ocp is any type with the members of OCP<...> of ocp_to_qp.hpp (that type asks every size to be positive; a problem
-//     without integrals or constraints brings a struct of its own).  X and U must be Rn<.>.
+//     without integrals or constraints brings a struct of its own).  X and U must be Rn<.> (flatten_ocp of ocp_flatten.hpp makes them so).
 // The Lagrangian Hessian sigma d2f + d2g(lambda) in one pass is d2l_dx2(x, sigma, lambda): the same pattern, its values written by
 // meshfn::ocp_nlp_hess_value entry by entry over the records of meshfn::ocp_nlp_hess_pattern -- the function and the records the
 // kernel behind sfb_ocp_nlp_hess_batch uses.  d2f_dx2 and d2g_dx2 keep their own code.
-// Left out: ocp_flatten / flatten_ocp, and any solver.
+// A problem on Lie groups comes here through flatten_ocp (ocp_flatten.hpp).  Left out: any solver.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -154,7 +154,7 @@ public:
   using U = typename Ocp::U;
   static constexpr int Nx = Ocp::Nx, Nu = Ocp::Nu, Nq = Ocp::Nq, Ncr = Ocp::Ncr, Nce = Ocp::Nce, nz = 1 + Nx + Nu, ne = 1 + 2 * Nx + Nq;
   static_assert(is_rn<X>::value && is_rn<U>::value,
-                "ocp_to_nlp: X and U must be Rn<.>; a problem on a Lie group goes through flat_dynamics (the flattened problem) first");
+                "ocp_to_nlp: X and U must be Rn<.>; a problem on a Lie group goes through flatten_ocp (ocp_flatten.hpp) first");
   static_assert(Nx >= 1, "ocp_to_nlp: Nx >= 1");
 
   OCPNLP(Ocp ocp, Mesh mesh) : ocp_(std::move(ocp)), mesh_(std::move(mesh)), N_(mesh_.N_colloc()), dims_(ocp_dims(ocp_))
