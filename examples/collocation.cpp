@@ -761,6 +761,174 @@ int sfbx_flat_ocp_nlp_host(int problem, int mesh_kind, int64_t agents, const dou
   }
 }
 
+int sfbx_flat_ocp_hess_nodes_host(int problem, int64_t agents, int32_t N, const double * tau, const double * x, const double * lam, const double * traj,
+                                  double * HLf, double * HLg, double * HLcr, double * d2theta, double * d2ce_l, int threads)
+{
+  if (agents < 0 || N < 1 || threads < 1) return -1;
+  const bool ok = sfbx::flat_dispatch_problem(problem, [&]<class Ocp>() {
+    using S = sfbx::FlatSizes<Ocp>;
+    int64_t cb[5];
+    sfbx::flat_con_beg<Ocp>(N, cb);
+    const auto part = [&](int64_t b0, int64_t b1) {  // agents [b0, b1): every pointer moved to agent b0
+      const auto model = sfbx::flat_swarm_model<Ocp>(traj + b0 * S::stride);
+      const int64_t sq = (int64_t)N * S::nz * S::nz, se = (int64_t)S::ne * S::ne;
+      sfbx::flat_hess_nodes_host(model, b1 - b0, N, tau, x + b0 * S::n(N), lam + b0 * cb[4],
+                                 sfbx::FlatHessOut{HLf + b0 * sq, HLg + b0 * sq, HLcr + b0 * sq, d2theta + b0 * se, d2ce_l + b0 * se});
+    };
+    if (threads == 1) return part(0, agents);
+    std::vector<std::thread> pool;
+    for (int k = 0; k < threads; ++k) pool.emplace_back(part, agents * k / threads, agents * (k + 1) / threads);
+    for (auto & th : pool) th.join();
+  });
+  return ok ? 0 : -1;
+}
+
+int sfbx_flat_ocp_hess_host(int problem, int mesh_kind, int64_t agents, const double * x, const double * lam, const double * sigma, const double * traj,
+                            int value_differences, double * hess, int64_t * differing, int64_t * nnz_hess, int threads)
+{
+  if (agents < 0 || threads < 1) return -1;
+  try {
+    const auto mesh = sfbx::flat_mesh(mesh_kind);
+    const bool ok   = sfbx::flat_dispatch_problem(problem, [&]<class Ocp>() {
+      const auto model = sfbx::flat_swarm_model<Ocp>(traj);
+      auto nlp0        = sf::ocp_to_nlp(sfbx::flat_agent_ocp(model, 0), mesh);
+      const int64_t n = (int64_t)nlp0.n(), m = (int64_t)nlp0.m(), nnz = nlp0.hess_tables().nnz;
+      if (nnz_hess) *nnz_hess = nnz;
+      if (!x) return;
+      const auto part = [&](int64_t b0, int64_t b1) {
+        for (int64_t b = b0; b < b1; ++b) {
+          if (value_differences) {  // the default flattened problem: OCPNLP's second differences of the flat values
+            auto nlp = sf::ocp_to_nlp(sfbx::flat_agent_ocp(model, b), mesh);
+            const std::vector<double> xv(x + b * n, x + (b + 1) * n), lv(lam + b * m, lam + (b + 1) * m);
+            const auto & H = nlp.d2l_dx2(xv, sigma[b], lv);
+            if (hess) std::copy(H.val.begin(), H.val.end(), hess + b * nnz);
+          } else {
+            sfbx::flat_hess_nlp_host(model, b, mesh, x + b * n, lam + b * m, sigma[b], hess ? hess + b * nnz : nullptr, differing ? differing + b : nullptr);
+          }
+        }
+      };
+      if (threads == 1) return part(0, agents);
+      std::vector<std::thread> pool;
+      for (int k = 0; k < threads; ++k) pool.emplace_back(part, agents * k / threads, agents * (k + 1) / threads);
+      for (auto & th : pool) th.join();
+    });
+    return ok ? 0 : -1;
+  } catch (const std::exception & e) {
+    std::fprintf(stderr, "collocation harness: %s\n", e.what());
+    return -2;
+  }
+}
+
+// The opt-in Hessians of flatten_ocp<FlatHess::Differences> as caller code; figures [8].  Returns 0 or the first failing expectation.
+//   1  a QUADRATIC problem on Rn around affine trajectories: the flat Hessians against P' H P, H the analytic Hessian of the
+//      original at (t, xl + e, ul + v) and P the constant Jacobian of (t, xl(t) + e, ul(t) + v).  The flat Jacobian is linear in
+//      z there, so its central difference has no truncation; what is left is rounding.  figures: worst error, bound, per family.
+//   2  the default flatten_ocp has no hessian member (static), the opt-in one has.
+int sfbx_test_flatten_hess_api(double * figures)
+{
+  namespace F = smooth::feedback;
+  for (int k = 0; k < 8; ++k) figures[k] = 0.0;
+  constexpr int NX = 2, NU = 1, NQ = 1, NCR = 1, NCE = 2, nz = 1 + NX + NU, ne = 1 + 2 * NX + NQ;
+  // z = (t, x0, x1, u0): f = (x0 u0 + t^2 / 2, x1^2 - t x0), g = x0^2 + u0^2 + x0 x1, cr = x1 u0 + t u0
+  // ze = (tf, x0_0, x0_1, xf_0, xf_1, q): theta = tf q + x0_0 xf_1 + xf_0^2, ce = (tf xf_0, x0_1^2 + q xf_1)
+  const int32_t tf_[] = {0, 1, 1, 3, 1, 0, 0,  0, 0, 2, 0, 0, 0, 0,  1, 2, 2, 0, 0, 0, 0,  1, 0, 1, 1, 1, 0, 0};
+  const double cf_[]  = {1, 0.5, 1, -1};
+  const int32_t tg_[] = {0, 1, 2, 0, 0, 0, 0,  0, 3, 2, 0, 0, 0, 0,  0, 1, 1, 2, 1, 0, 0};
+  const double cg_[]  = {1, 1, 1};
+  const int32_t tc_[] = {0, 2, 1, 3, 1, 0, 0,  0, 0, 1, 3, 1, 0, 0};
+  const double cc_[]  = {1, 1};
+  const int32_t tt_[] = {0, 0, 1, 5, 1, 0, 0,  0, 1, 1, 4, 1, 0, 0,  0, 3, 2, 0, 0, 0, 0};
+  const double ct_[]  = {1, 1, 1};
+  const int32_t te_[] = {0, 0, 1, 3, 1, 0, 0,  1, 2, 2, 0, 0, 0, 0,  1, 5, 1, 4, 1, 0, 0};
+  const double ce_[]  = {1, 1, 1};
+  sfbx::TermOcp<NX, NU, NQ, NCR, NCE> ocp{};
+  ocp.f.tab = {4, tf_, cf_}, ocp.g.tab = {3, tg_, cg_}, ocp.cr.tab = {2, tc_, cc_}, ocp.theta.tab = {3, tt_, ct_}, ocp.ce.tab = {3, te_, ce_};
+  if (!ocp.f.tab.valid(NX, nz) || !ocp.g.tab.valid(NQ, nz) || !ocp.cr.tab.valid(NCR, nz) || !ocp.theta.tab.valid(1, ne) || !ocp.ce.tab.valid(NCE, ne)) return 100;
+  const F::Vec<NX> a{0.3, -0.2}, da{0.1, 0.25};
+  const F::Vec<NU> c{0.2}, dc{-0.3};
+  const auto xl = F::trajectory([=](double t) { F::Rn<NX> x; for (int i = 0; i < NX; ++i) x.v[i] = a[i] + t * da[i]; return x; }, [=](double) { return da; });
+  const auto ul = F::trajectory([=](double t) { F::Rn<NU> u; for (int i = 0; i < NU; ++i) u.v[i] = c[i] + t * dc[i]; return u; }, [=](double) { return dc; });
+  const auto plain = F::flatten_ocp(ocp, xl, ul);
+  const auto flat  = F::flatten_ocp<F::FlatHess::Differences>(ocp, xl, ul);
+  // ---- 2 ----
+  {
+    F::Rn<NX> e{};
+    F::Rn<NU> v{};
+    F::Vec<NQ> q{};
+    F::Mat<nz, NX * nz> Hf;
+    F::Mat<ne, ne> Ht;
+    static_assert(!sfbx::flat_has_hessian<decltype(plain.f), double, decltype(e), decltype(v), decltype(Hf)> &&
+                  !sfbx::flat_has_hessian<decltype(plain.theta), double, decltype(e), decltype(e), decltype(q), decltype(Ht)>);
+    static_assert(sfbx::flat_has_hessian<decltype(flat.f), double, decltype(e), decltype(v), decltype(Hf)> &&
+                  sfbx::flat_has_hessian<decltype(flat.theta), double, decltype(e), decltype(e), decltype(q), decltype(Ht)>);
+    (void)e, (void)v, (void)q, (void)Hf, (void)Ht;
+  }
+  // ---- 1 ----
+  const double t = 0.37, tfv = 1.3;
+  F::Rn<NX> e, e0, ef;
+  F::Rn<NU> v;
+  F::Vec<NQ> q{0.45};
+  e.v = {0.21, -0.34}, e0.v = {-0.15, 0.4}, ef.v = {0.33, 0.12}, v.v = {0.27};
+  F::Mat<nz, nz> P = F::Mat<nz, nz>::Zero();  // d (t, x, u) / d (t, e, v)
+  for (int k = 0; k < nz; ++k) P(k, k) = 1.0;
+  for (int k = 0; k < NX; ++k) P(1 + k, 0) = da[k];
+  for (int k = 0; k < NU; ++k) P(1 + NX + k, 0) = dc[k];
+  F::Mat<ne, ne> Pe = F::Mat<ne, ne>::Zero();  // d (tf, x0, xf, q) / d (tf, e0, ef, q): xf = xl(tf) + ef
+  for (int k = 0; k < ne; ++k) Pe(k, k) = 1.0;
+  for (int k = 0; k < NX; ++k) Pe(1 + NX + k, 0) = da[k];
+  const double h = F::detail::flat_hess_step, eps = std::numeric_limits<double>::epsilon();
+  double worst = 0.0, hmax = 0.0;
+  const auto compare = [&]<int NF, int NV>(const F::Mat<NV, NF * NV> & got, const F::Mat<NV, NF * NV> & H, const F::Mat<NV, NV> & Pm) {
+    double err = 0.0;
+    for (int r = 0; r < NF; ++r)
+      for (int i = 0; i < NV; ++i)
+        for (int j = 0; j < NV; ++j) {
+          double want = 0.0;
+          for (int k = 0; k < NV; ++k)
+            for (int l = 0; l < NV; ++l) want += Pm(k, i) * H(k, r * NV + l) * Pm(l, j);
+          err  = std::max(err, std::fabs(got(i, r * NV + j) - want));
+          hmax = std::max(hmax, std::fabs(want));
+        }
+    worst = std::max(worst, err);
+    return err;
+  };
+  const F::Rn<NX> x = rplus(xl(t), e.v), x0 = rplus(xl(0.0), e0.v), xf = rplus(xl(tfv), ef.v);
+  const F::Rn<NU> u = rplus(ul(t), v.v);
+  {
+    F::Mat<nz, NX * nz> got, H;
+    flat.f.hessian(t, e, v, got), ocp.f.hessian(t, x, u, H);
+    figures[2] = compare.template operator()<NX, nz>(got, H, P);
+  }
+  {
+    F::Mat<nz, NQ * nz> got, H;
+    flat.g.hessian(t, e, v, got), ocp.g.hessian(t, x, u, H);
+    figures[3] = compare.template operator()<NQ, nz>(got, H, P);
+  }
+  {
+    F::Mat<nz, NCR * nz> got, H;
+    flat.cr.hessian(t, e, v, got), ocp.cr.hessian(t, x, u, H);
+    figures[4] = compare.template operator()<NCR, nz>(got, H, P);
+  }
+  {
+    F::Mat<ne, ne> got, H;
+    flat.theta.hessian(tfv, e0, ef, q, got), ocp.theta.hessian(tfv, x0, xf, q, H);
+    figures[5] = compare.template operator()<1, ne>(got, H, Pe);
+  }
+  {
+    F::Mat<ne, NCE * ne> got, H;
+    flat.ce.hessian(tfv, e0, ef, q, got), ocp.ce.hessian(tfv, x0, xf, q, H);
+    figures[6] = compare.template operator()<NCE, ne>(got, H, Pe);
+  }
+  // An entry of the flat Jacobian is a sum of at most ne = 6 products of numbers below 2, each from a few roundings: off by at
+  // most 16 ne eps.  The difference of two of them over 2 h is off by 16 ne eps / h = 2.8e-9; nothing else, the Jacobian being
+  // linear in z and z +- h e_a exact to eps |z| (which moves the quotient by eps |z| / h |H|, inside the same bound).
+  const double bound = 16.0 * ne * eps / h * (1.0 + hmax);
+  figures[0] = worst, figures[1] = bound;
+  if (!(hmax >= 1.0)) return 101;  // the Hessians are there: entries 1 and 2
+  if (!(worst <= bound)) return 102;
+  return 0;
+}
+
 // Caller code against <smooth/feedback/ocp_flatten.hpp> under the reference's names; figures [8] receives what each
 // scenario measured.  Returns 0, or the number of the first expectation that fails.
 //   1  a flattened Rn problem (term tables of ocp_nlp_harness.h around affine trajectories) gives the NLP of the original

@@ -219,6 +219,137 @@ void flat_nlp_host(const FlatSwarmModel<Ocp> & model, int64_t b, const MeshT & m
   }
 }
 
+// ---- second order: the multiplier-contracted Hessians sfb_ocp_nlp_hess_batch takes ----
+/// agent b's flattened problem with hessian members (FlatHess::Differences)
+template<class Ocp>
+auto flat_agent_ocp_hess(const FlatSwarmModel<Ocp> & model, int64_t b)
+{
+  using M = FlatSwarmModel<Ocp>;
+  namespace F = smooth::feedback;
+  return F::flatten_ocp<F::FlatHess::Differences>(static_cast<const Ocp &>(model), F::AgentStateTrajectory<M>{&model, b}, F::AgentInputTrajectory<M>{&model, b});
+}
+
+/// whether fn.hessian(args...) exists (the default flat functors must have none)
+template<class Fn, class... Args>
+inline constexpr bool flat_has_hessian = requires(const Fn & fn, Args &... args) { fn.hessian(args...); };
+
+/// host pointers of the five arrays: HLf, HLg, HLcr [B][N][nz][nz], d2theta, d2ce_l [B][ne][ne], full squares
+struct FlatHessOut {
+  double *HLf, *HLg, *HLcr, *d2theta, *d2ce_l;
+};
+
+/// the constraint offsets of the NLP on N nodes (meshfn::ocp_nlp_structure): dynamics | integrals | running | end
+template<class Ocp>
+void flat_con_beg(int64_t N, int64_t cb[5])
+{
+  using S = FlatSizes<Ocp>;
+  cb[0] = 0, cb[1] = N * S::Nx, cb[2] = cb[1] + S::Nq, cb[3] = cb[2] + N * S::Ncr, cb[4] = cb[3] + S::Nce;
+}
+
+/// the five arrays of agents [0, B) on the host, one (agent, node, direction) and (agent, end direction) at a time: the primitives
+/// of the hessian members (flat_inner_direction, flat_end_direction), contracted as they come (flat_contract_direction)
+template<class Ocp>
+void flat_hess_nodes_host(const FlatSwarmModel<Ocp> & model, int64_t B, int32_t N, const double * tau, const double * x, const double * lam,
+                          const FlatHessOut & o)
+{
+  using S = FlatSizes<Ocp>;
+  namespace F = smooth::feedback;
+  namespace D = smooth::feedback::detail;
+  constexpr int Nx = S::Nx, Nu = S::Nu, Nq = S::Nq, Ncr = S::Ncr, Nce = S::Nce, nz = S::nz, ne = S::ne;
+  const int64_t n = S::n(N);
+  int64_t cb[5];
+  flat_con_beg<Ocp>(N, cb);
+  const auto put = [](double * sq, int nv, int a, const auto & row) {
+    for (int c = a; c < nv; ++c) sq[a * nv + c] = sq[c * nv + a] = row[c];
+  };
+  for (int64_t b = 0; b < B; ++b) {
+    const auto flat   = flat_agent_ocp(model, b);
+    const double * xa = x + b * n;
+    const double * la = lam + b * cb[4];
+    const double tf   = xa[0];
+    for (int32_t i = 0; i < N; ++i) {
+      const double t = tf * tau[i];
+      F::Rn<Nx> e;
+      F::Rn<Nu> v;
+      for (int d = 0; d < Nx; ++d) e.v[d] = xa[1 + Nq + (int64_t)i * Nx + d];
+      for (int d = 0; d < Nu; ++d) v.v[d] = xa[1 + Nq + (int64_t)(N + 1) * Nx + (int64_t)i * Nu + d];
+      const int64_t node = b * N + i;
+      for (int a = 0; a < nz; ++a) {
+        F::Vec<nz> row;
+        {
+          F::Mat<Nx, nz> Dm;
+          D::flat_inner_direction<Nx>(flat.f, t, e, v, a, Dm);
+          D::flat_contract_direction<Nx, nz>(Dm, la + cb[0] + (int64_t)i * Nx, row);
+          put(o.HLf + node * nz * nz, nz, a, row);
+        }
+        {
+          F::Mat<Nq, nz> Dm;
+          D::flat_inner_direction<Nq>(flat.g, t, e, v, a, Dm);
+          D::flat_contract_direction<Nq, nz>(Dm, la + cb[1], row);
+          put(o.HLg + node * nz * nz, nz, a, row);
+        }
+        {
+          F::Mat<Ncr, nz> Dm;
+          D::flat_inner_direction<Ncr>(flat.cr, t, e, v, a, Dm);
+          D::flat_contract_direction<Ncr, nz>(Dm, la + cb[2] + (int64_t)i * Ncr, row);
+          put(o.HLcr + node * nz * nz, nz, a, row);
+        }
+      }
+    }
+    F::Rn<Nx> e0, ef;
+    F::Vec<Nq> q;
+    for (int d = 0; d < Nx; ++d) e0.v[d] = xa[1 + Nq + d], ef.v[d] = xa[1 + Nq + (int64_t)N * Nx + d];
+    for (int d = 0; d < Nq; ++d) q[d] = xa[1 + d];
+    for (int a = 0; a < ne; ++a) {
+      F::Vec<ne> row;
+      {
+        F::Mat<1, ne> Dm;
+        D::flat_end_direction<1>(flat.theta, tf, e0, ef, q, a, Dm);
+        for (int c = 0; c < ne; ++c) row[c] = Dm(0, c);
+        put(o.d2theta + b * ne * ne, ne, a, row);
+      }
+      {
+        F::Mat<Nce, ne> Dm;
+        D::flat_end_direction<Nce>(flat.ce, tf, e0, ef, q, a, Dm);
+        D::flat_contract_direction<Nce, ne>(Dm, la + cb[3], row);
+        put(o.d2ce_l + b * ne * ne, ne, a, row);
+      }
+    }
+  }
+}
+
+/// d2l_dx2 of agent b's opt-in flattened problem on `mesh` at xb [n], lamb [m], sigma: hess_val [nnzH].  `differing`
+/// (nullable) counts the values that differ from meshfn::ocp_nlp_hess_assemble over flat_hess_nodes_host's and flat_nodes_host's arrays.
+template<class Ocp, class MeshT>
+void flat_hess_nlp_host(const FlatSwarmModel<Ocp> & model, int64_t b, const MeshT & mesh, const double * xb, const double * lamb, double sigma,
+                        double * hess_val, int64_t * differing)
+{
+  using S = FlatSizes<Ocp>;
+  namespace F = smooth::feedback;
+  auto nlp = F::ocp_to_nlp(flat_agent_ocp_hess(model, b), mesh);
+  const std::vector<double> xv(xb, xb + nlp.n()), lv(lamb, lamb + nlp.m());
+  const F::MeshCsc & H = nlp.d2l_dx2(xv, sigma, lv);
+  if (hess_val) std::copy(H.val.begin(), H.val.end(), hess_val);
+  if (differing) {
+    const int32_t N = (int32_t)mesh.N_colloc();
+    const std::vector<double> taus = mesh.all_nodes();
+    std::vector<double> Ff((size_t)N * S::Nx), dFf(Ff.size() * S::nz), Fg((size_t)N * S::Nq), dFg(Fg.size() * S::nz), Fcr((size_t)N * S::Ncr),
+      dFcr(Fcr.size() * S::nz), ce(S::Nce), dce((size_t)S::Nce * S::ne), th(1), dth(S::ne);
+    std::vector<double> HLf((size_t)N * S::nz * S::nz), HLg(HLf.size()), HLcr(HLf.size()), d2t((size_t)S::ne * S::ne), d2c(d2t.size());
+    FlatSwarmModel<Ocp> one = model;
+    one.rows                = model.rows + b * S::stride;
+    flat_nodes_host(one, 1, N, taus.data(), xb, FlatNodeOut{Ff.data(), dFf.data(), Fg.data(), dFg.data(), Fcr.data(), dFcr.data(), ce.data(), dce.data(), th.data(), dth.data()});
+    flat_hess_nodes_host(one, 1, N, taus.data(), xb, lamb, FlatHessOut{HLf.data(), HLg.data(), HLcr.data(), d2t.data(), d2c.data()});
+    std::vector<double> h2(H.val.size());
+    F::meshfn::ocp_nlp_hess_assemble(nlp.hess_tables(),
+                                     F::meshfn::OcpNlpHessAgent{xb, lamb, sigma, dFf.data(), HLf.data(), dFg.data(), HLg.data(), HLcr.data(), d2t.data(), d2c.data()},
+                                     sigma, h2.data());
+    int64_t bad = 0;
+    for (std::size_t k = 0; k < h2.size(); ++k) bad += std::memcmp(&H.val[k], &h2[k], sizeof(double)) != 0;
+    *differing = bad;
+  }
+}
+
 // ---- the Lie operations the flattening adds: op 0 dr_exp(a) (in T, out T x T), op 1 d/de (dr_expinv(e) w) (in e, w; out T x T) ----
 // groups: 1 SE2, 2 SO3, 5 SE3 (the ids of lie_eval.h), 6 Bundle<SE3, Rn<6>>, 7 Bundle<SE2, Rn<2>>
 template<class Fn>

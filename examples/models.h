@@ -221,6 +221,22 @@ int sfbx_flat_ocp_nodes_host(int problem, int64_t agents, int32_t N, const doubl
  * K = (3, 5); 1: 13 intervals of 4.  sizes [4] (nullable): n, m, nnz, N; taus [N + 1] (nullable).  x NULL: sizes only. */
 int sfbx_flat_ocp_nlp_host(int problem, int mesh_kind, int64_t agents, const double *x, const double *traj, double *g,
                            double *dg, double *f, double *df, int64_t *differing, int32_t *sizes, double *taus);
+/* The multiplier-contracted Hessians of the flattened problem at the nodes tau [N] on the host, by the difference law of
+ * ocp_flatten.hpp, one (agent, node, direction) at a time: lam [agents][m'] with
+ * m' = N nx + nq + N ncr + nce (dynamics | integrals | running | end).  Out, in the layout of sfb_ocp_nlp_hess_batch: HLf, HLg,
+ * HLcr [agents][N][nz][nz], d2theta, d2ce_l [agents][ne][ne], full squares. */
+int sfbx_flat_ocp_hess_nodes_host(int problem, int64_t agents, int32_t N, const double *tau, const double *x, const double *lam,
+                                  const double *traj, double *HLf, double *HLg, double *HLcr, double *d2theta, double *d2ce_l,
+                                  int threads);
+/* d2l_dx2 of ocp_to_nlp(flatten_ocp<FlatHess::Differences>(...), mesh) per agent: hess [agents][nnzH]; differing [agents]
+ * (nullable) counts the values not bit-identical to meshfn::ocp_nlp_hess_assemble over the host arrays above.
+ * value_differences != 0: the default flatten_ocp instead, whose d2l_dx2 differences the flat values (differing untouched).
+ * nnz_hess (nullable) receives nnzH; x NULL: that only. */
+int sfbx_flat_ocp_hess_host(int problem, int mesh_kind, int64_t agents, const double *x, const double *lam, const double *sigma,
+                            const double *traj, int value_differences, double *hess, int64_t *differing, int64_t *nnz_hess,
+                            int threads);
+/* Scenarios of the opt-in Hessians as caller code: figures [8]; 0 or the first failing expectation (see collocation.cpp). */
+int sfbx_test_flatten_hess_api(double *figures);
 /* Scenarios written as caller code against <smooth/feedback/ocp_flatten.hpp> (a flattened Rn problem against its original,
  * the unflatten round trip, d2l_dx2 against differences of the gradient, a Spline as a trajectory); figures [8]; 0 or the first failing expectation. */
 int sfbx_test_flatten_api(double *figures);

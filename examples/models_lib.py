@@ -824,6 +824,63 @@ def flat_ocp_front_device(problem, x, traj, mesh_kind=0, side=False, reps=0):
     return out
 
 
+FLAT_HESS_KEYS = ("HLf", "HLg", "HLcr", "d2theta", "d2ce_l")
+
+
+def _flat_hess_arrays(d, B, N):
+    nz, ne = d["nz"], d["ne"]
+    return dict(HLf=np.full((B, N, nz, nz), np.nan), HLg=np.full((B, N, nz, nz), np.nan), HLcr=np.full((B, N, nz, nz), np.nan),
+                d2theta=np.full((B, ne, ne), np.nan), d2ce_l=np.full((B, ne, ne), np.nan))
+
+
+def flat_ocp_hess_nodes(problem, tau, x, lam, traj, threads=1):
+    """The multiplier-contracted Hessians of the flattened problem at the nodes tau [N], the arrays sfb_ocp_nlp_hess_batch takes:
+    dict HLf, HLg, HLcr [B][N][nz][nz], d2theta, d2ce_l [B][ne][ne] (full squares) for x [B][n], lam [B][N nx + nq + N ncr + nce],
+    traj [B][row].  Host loop over the law of ocp_flatten.hpp."""
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    N = len(tau)
+    d = flat_ocp_sizes(problem, N)
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, d["n"])
+    B = len(x)
+    lam = np.ascontiguousarray(lam, dtype=np.float64).reshape(B, N * d["nx"] + d["nq"] + N * d["ncr"] + d["nce"])
+    traj = np.ascontiguousarray(traj, dtype=np.float64).reshape(B, d["row"])
+    out = _flat_hess_arrays(d, B, N)
+    ptrs = [_p(out[k]) for k in FLAT_HESS_KEYS]
+    rc = lib().sfbx_flat_ocp_hess_nodes_host(FLAT_PROBLEMS[problem], C.c_int64(B), N, _p(tau), _p(x), _p(lam), _p(traj), *ptrs, threads)
+    assert rc == 0, rc
+    return out
+
+
+def flat_ocp_nnz_hess(problem, mesh_kind=0):
+    nnz = np.zeros(1, np.int64)
+    assert lib().sfbx_flat_ocp_hess_host(FLAT_PROBLEMS[problem], mesh_kind, C.c_int64(1), None, None, None, None, 0, None, None, _p(nnz), 1) == 0
+    return int(nnz[0])
+
+
+def flat_ocp_hess_host(problem, x, lam, sigma, traj, mesh_kind=0, value_differences=False, threads=1):
+    """d2l_dx2 of ocp_to_nlp(flatten_ocp<FlatHess::Differences>(...), mesh) per agent on the host: dict hess [B][nnzH], differing [B]
+    (values not bit-identical to meshfn::ocp_nlp_hess_assemble over the host arrays of flat_ocp_hess_nodes).
+    value_differences=True: the default flatten_ocp, whose d2l_dx2 differences the flat values (differing stays -1)."""
+    s = flat_ocp_mesh(problem, mesh_kind)
+    d = flat_ocp_sizes(problem, s["N"])
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, s["n"])
+    B = len(x)
+    lam = np.ascontiguousarray(lam, dtype=np.float64).reshape(B, s["m"])
+    sigma = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (B,)))
+    traj = np.ascontiguousarray(traj, dtype=np.float64).reshape(B, d["row"])
+    out = dict(hess=np.full((B, flat_ocp_nnz_hess(problem, mesh_kind)), np.nan), differing=np.full(B, -1, np.int64))
+    rc = lib().sfbx_flat_ocp_hess_host(FLAT_PROBLEMS[problem], mesh_kind, C.c_int64(B), _p(x), _p(lam), _p(sigma), _p(traj), int(value_differences),
+                                       _p(out["hess"]), _p(out["differing"]), None, threads)
+    assert rc == 0, rc
+    return out
+
+
+def test_flatten_hess_api():
+    """(code, figures [8]) of sfbx_test_flatten_hess_api: 0, or the first failing expectation"""
+    fig = np.zeros(8)
+    return int(lib().sfbx_test_flatten_hess_api(_p(fig))), fig
+
+
 def test_flatten_api():
     """(code, figures [8]) of sfbx_test_flatten_api: 0, or the first failing expectation"""
     fig = np.zeros(8)

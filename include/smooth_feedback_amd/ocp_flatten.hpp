@@ -31,9 +31,23 @@
 // Inner derivatives: a wrapped functor may carry jacobian(t, x, u, J) (end functions: jacobian(tf, x0, xf, q, J)), right-
 // Jacobians on the group, columns (t | x | u) / (tf | x0 | xf | q); without one, forward differences with the step of
 // xu_jacobian / mesh_function.hpp (2^-26) on the group.
-// Second derivatives: the flat functors have NO hessian member, so d2f_dx2, d2g_dx2 and d2l_dx2 of a flattened problem go
-// through OCPNLP's differences of the flat values.  The reference's Hessian of FlatDyn is marked inefficient there; an analytic
-// one is out of scope here.
+// Second derivatives (the reference's flat functors carry Hessians, :221-241, :373-387, :476-490; an analytic chain rule through
+// d2r_exp is out of scope here).  flatten_ocp<FlatHess::None> (the default): the flat functors have NO hessian member and d2f_dx2,
+// d2g_dx2, d2l_dx2 of a flattened problem go through OCPNLP's differences of the flat values, four evaluations of the whole
+// change of variables per entry.  flatten_ocp<FlatHess::Differences>: they carry hessian(t, e, v, H) / hessian(tf, e0, ef, q, H)
+// in the layouts MeshModelEval and EndEval expect, and OCPNLP picks them up.  The law, built on ONE primitive, "the difference
+// along direction a" (flat_inner_direction / flat_end_direction below, SFB_LIE_HD like the rest of this header), used by the
+// uncontracted members and by the multiplier-contracted per-direction form (flat_contract_direction) alike:
+//   inner functor with a jacobian member    H_r(a, b) = (J(z + h e_a)(r, b) - J(z - h e_a)(r, b)) / (2 h),  J the closed form of
+//                                           eval() above, h = flat_hess_step = 2^-17: two Jacobians per direction
+//   inner functor without one               the four-point second difference of the flat VALUES at 2^-13, the rule and step of
+//                                           MeshModelEval: differencing a forward-difference Jacobian would amplify its 1e-8 noise by 1 / h
+//   symmetry                                computed for a <= b; the lower triangle mirrors the upper, H(b, a) = H(a, b)
+//   end functions                           the same with z = (tf | e0 | ef | q)
+//   time direction                          J(z +- h e_0) is the closed-form Jacobian at t +- h, so the convention above carries
+//                                           over: the body velocity counts as constant, and the second derivatives are exact (up to
+//                                           the difference) for trajectories of constant body velocity, as the Jacobians are
+//   contraction with multipliers            acc = 0; acc += lam[r] * d(r, b), r ascending: the order of OCPNLP::node_hessian
 #pragma once
 #include <functional>
 #include <type_traits>
@@ -99,6 +113,9 @@ struct AgentInputTrajectory {
   SFB_LIE_HD auto operator()(double t) const { return m->ul(b, t); }
   SFB_LIE_HD auto velocity(double t) const { return m->dul(b, t); }
 };
+
+/// second derivatives of the flat functors: none (OCPNLP differences the flat values) or hessian members by the law at the top
+enum class FlatHess { None, Differences };
 
 namespace detail {
 
@@ -277,10 +294,151 @@ SFB_LIE_HD Mat<NF, 1 + X::Dof + U::Dof> flat_chain_inner(const Mat<NF, 1 + X::Do
   return J;
 }
 
+// ---- second derivatives: the difference along direction a (the law at the top of this file) ----
+// eps^(1/3) = 2^-17.33 balances the central difference of a Jacobian known to eps: truncation h^2 |d3J| / 6 against rounding
+// eps |J| / h.  The nearest power of two, so that z + h e_a and z - h e_a are exact and 2 h divides exactly.
+inline constexpr double flat_hess_step = 7.62939453125e-06;  // 2^-17
+// eps^(1/4), the step of MeshModelEval's and EndEval's four-point second difference of values (sqrt of their 2^-26)
+inline constexpr double flat_hess_value_step = 1.220703125e-04;  // 2^-13
+
+/// z[c] += d as a compare-select over the entries, never a run-time index (c outside [0, N): nothing)
+template<int N>
+SFB_LIE_HD void flat_bump(Vec<N> & z, int c, double d)
+{
+  SFB_FLAT_UNROLL
+  for (int k = 0; k < N; ++k) z[k] += (k == c) ? d : 0.0;
+}
+
+/// D (NF x nv) of a flat inner functor `fun` (FlatDyn, FlatInnerFun) along direction a of z = (t | e | v).  With a jacobian
+/// member in the wrapped functor: D = (J(z + h e_a) - J(z - h e_a)) / (2 h), every column.  Without: columns b >= a hold the
+/// four-point second difference of the values in (a, b), the others 0.  Row r of the Hessians: H_r(a, b) = D(r, b), b >= a.
+template<int NF, class Fun>
+SFB_LIE_HD void flat_inner_direction(const Fun & fun, double t, const Rn<Fun::Nx> & e, const Rn<Fun::Nu> & v, int a, Mat<NF, Fun::nv> & D)
+{
+  constexpr int Nx = Fun::Nx, Nu = Fun::Nu, nv = Fun::nv;
+  if constexpr (Fun::inner_has_jacobian) {
+    const double h = flat_hess_step;
+    Rn<Nx> ep = e, em = e;
+    Rn<Nu> vp = v, vm = v;
+    const double dt = (a == 0) ? h : 0.0;
+    flat_bump<Nx>(ep.v, a - 1, h), flat_bump<Nx>(em.v, a - 1, -h);
+    flat_bump<Nu>(vp.v, a - 1 - Nx, h), flat_bump<Nu>(vm.v, a - 1 - Nx, -h);
+    Vec<NF> val;
+    Mat<NF, nv> Jm;
+    fun.eval(t + dt, ep, vp, val, D);
+    fun.eval(t - dt, em, vm, val, Jm);
+    SFB_FLAT_UNROLL
+    for (int k = 0; k < NF * nv; ++k) D.a[k] = (D.a[k] - Jm.a[k]) / (2 * h);
+  } else {
+    const double h = flat_hess_value_step;
+    D = Mat<NF, nv>::Zero();
+    const auto at = [&](double sa, double sb, int b) {
+      Rn<Nx> es = e;
+      Rn<Nu> vs = v;
+      const double dt = ((a == 0) ? sa : 0.0) + ((b == 0) ? sb : 0.0);
+      Vec<Nx> de{};
+      Vec<Nu> dv{};
+      flat_bump<Nx>(de, a - 1, sa), flat_bump<Nx>(de, b - 1, sb);
+      flat_bump<Nu>(dv, a - 1 - Nx, sa), flat_bump<Nu>(dv, b - 1 - Nx, sb);
+      SFB_FLAT_UNROLL
+      for (int k = 0; k < Nx; ++k) es.v[k] += de[k];
+      SFB_FLAT_UNROLL
+      for (int k = 0; k < Nu; ++k) vs.v[k] += dv[k];
+      return fun(t + dt, es, vs);
+    };
+    for (int b = 0; b < nv; ++b) {  // stays rolled in device code: the body is the flat function four times
+      if (b < a) continue;
+      const Vec<NF> pp = at(h, h, b), pm = at(h, -h, b), mp = at(-h, h, b), mm = at(-h, -h, b);
+      SFB_FLAT_UNROLL
+      for (int k = 0; k < nv; ++k)
+        if (k == b) {
+          SFB_FLAT_UNROLL
+          for (int r = 0; r < NF; ++r) D(r, k) = ((pp[r] - pm[r]) - (mp[r] - mm[r])) / (4 * h * h);
+        }
+    }
+  }
+}
+
+/// the same for a flat end functor (FlatEndptFun), z = (tf | e0 | ef | q)
+template<int R, class Fun>
+SFB_LIE_HD void flat_end_direction(const Fun & fun, double tf, const Rn<Fun::Nx> & e0, const Rn<Fun::Nx> & ef, const Vec<Fun::nq> & q, int a, Mat<R, Fun::ne> & D)
+{
+  constexpr int Nx = Fun::Nx, Nq = Fun::nq, ne = Fun::ne;
+  if constexpr (Fun::inner_has_jacobian) {
+    const double h = flat_hess_step;
+    Rn<Nx> e0p = e0, e0m = e0, efp = ef, efm = ef;
+    Vec<Nq> qp = q, qm = q;
+    const double dt = (a == 0) ? h : 0.0;
+    flat_bump<Nx>(e0p.v, a - 1, h), flat_bump<Nx>(e0m.v, a - 1, -h);
+    flat_bump<Nx>(efp.v, a - 1 - Nx, h), flat_bump<Nx>(efm.v, a - 1 - Nx, -h);
+    flat_bump<Nq>(qp, a - 1 - 2 * Nx, h), flat_bump<Nq>(qm, a - 1 - 2 * Nx, -h);
+    Vec<R> val;
+    Mat<R, ne> Jm;
+    fun.eval(tf + dt, e0p, efp, qp, val, D);
+    fun.eval(tf - dt, e0m, efm, qm, val, Jm);
+    SFB_FLAT_UNROLL
+    for (int k = 0; k < R * ne; ++k) D.a[k] = (D.a[k] - Jm.a[k]) / (2 * h);
+  } else {
+    const double h = flat_hess_value_step;
+    D = Mat<R, ne>::Zero();
+    const auto at = [&](double sa, double sb, int b) {
+      Rn<Nx> e0s = e0, efs = ef;
+      Vec<Nq> qs = q;
+      const double dt = ((a == 0) ? sa : 0.0) + ((b == 0) ? sb : 0.0);
+      Vec<Nx> d0{}, df{};
+      Vec<Nq> dq{};
+      flat_bump<Nx>(d0, a - 1, sa), flat_bump<Nx>(d0, b - 1, sb);
+      flat_bump<Nx>(df, a - 1 - Nx, sa), flat_bump<Nx>(df, b - 1 - Nx, sb);
+      flat_bump<Nq>(dq, a - 1 - 2 * Nx, sa), flat_bump<Nq>(dq, b - 1 - 2 * Nx, sb);
+      SFB_FLAT_UNROLL
+      for (int k = 0; k < Nx; ++k) e0s.v[k] += d0[k], efs.v[k] += df[k];
+      SFB_FLAT_UNROLL
+      for (int k = 0; k < Nq; ++k) qs[k] += dq[k];
+      return Fun::as_vec_flat(fun, tf + dt, e0s, efs, qs);
+    };
+    for (int b = 0; b < ne; ++b) {
+      if (b < a) continue;
+      const Vec<R> pp = at(h, h, b), pm = at(h, -h, b), mp = at(-h, h, b), mm = at(-h, -h, b);
+      SFB_FLAT_UNROLL
+      for (int k = 0; k < ne; ++k)
+        if (k == b) {
+          SFB_FLAT_UNROLL
+          for (int r = 0; r < R; ++r) D(r, k) = ((pp[r] - pm[r]) - (mp[r] - mm[r])) / (4 * h * h);
+        }
+    }
+  }
+}
+
+/// row[b] = sum_r lam[r] D(r, b): acc = 0, r ascending (OCPNLP::node_hessian): row a of a contracted square, from b = a on
+template<int NF, int NV>
+SFB_LIE_HD void flat_contract_direction(const Mat<NF, NV> & D, const double * lam, Vec<NV> & row)
+{
+  SFB_FLAT_UNROLL
+  for (int b = 0; b < NV; ++b) {
+    double acc = 0.0;
+    SFB_FLAT_UNROLL
+    for (int r = 0; r < NF; ++r) acc += lam[r] * D(r, b);
+    row[b] = acc;
+  }
+}
+
+/// the uncontracted squares from the directions: H (NV x NF NV, side by side), upper triangle computed, lower mirrored
+template<int NF, int NV, class Dir>
+SFB_LIE_HD void flat_hessian_from_directions(Mat<NV, NF * NV> & H, Dir && direction)
+{
+  for (int a = 0; a < NV; ++a) {
+    Mat<NF, NV> D;
+    direction(a, D);
+    for (int r = 0; r < NF; ++r)
+      for (int b = a; b < NV; ++b) H(a, r * NV + b) = H(b, r * NV + a) = D(r, b);
+  }
+}
+
 /// g or cr of the flattened problem (FlatInnerFun)
-template<class X, class U, int NF, class Fn, class Xl, class Ul>
+template<class X, class U, int NF, class Fn, class Xl, class Ul, FlatHess HM = FlatHess::None>
 struct FlatInnerFun {
   static constexpr int Nx = X::Dof, Nu = U::Dof, nv = 1 + Nx + Nu;
+  static constexpr bool inner_has_jacobian = requires(const Fn & fn, const X & x, const U & u, Mat<NF, nv> & J) { fn.jacobian(0.0, x, u, J); };
   Fn f;
   Xl xl;
   Ul ul;
@@ -297,12 +455,19 @@ struct FlatInnerFun {
     flat_inner_jacobian<NF>(f, t, rplus(xl(t), e.v), rplus(ul(t), v.v), val, Jf);
     J = flat_chain_inner<NF, X, U>(Jf, e.v, v.v, xl.velocity(t), ul.velocity(t));
   }
+  /// the Hessians of the NF rows side by side (MeshModelEval's layout), FlatHess::Differences only
+  SFB_LIE_HD void hessian(double t, const Rn<Nx> & e, const Rn<Nu> & v, Mat<nv, NF * nv> & H) const
+    requires(HM == FlatHess::Differences)
+  {
+    flat_hessian_from_directions<NF, nv>(H, [&](int a, Mat<NF, nv> & D) { flat_inner_direction<NF>(*this, t, e, v, a, D); });
+  }
 };
 
 /// the dynamics of the flattened problem (FlatDyn)
-template<class X, class U, class Fn, class Xl, class Ul>
+template<class X, class U, class Fn, class Xl, class Ul, FlatHess HM = FlatHess::None>
 struct FlatDyn {
   static constexpr int Nx = X::Dof, Nu = U::Dof, nv = 1 + Nx + Nu;
+  static constexpr bool inner_has_jacobian = requires(const Fn & fn, const X & x, const U & u, Mat<Nx, nv> & J) { fn.jacobian(0.0, x, u, J); };
   Fn f;
   Xl xl;
   Ul ul;
@@ -334,12 +499,19 @@ struct FlatDyn {
         for (int r = 0; r < Nx; ++r) J(r, 1 + c) += De(r, c) - Ad(r, c);
     }
   }
+  SFB_LIE_HD void hessian(double t, const Rn<Nx> & e, const Rn<Nu> & v, Mat<nv, Nx * nv> & H) const
+    requires(HM == FlatHess::Differences)
+  {
+    flat_hessian_from_directions<Nx, nv>(H, [&](int a, Mat<Nx, nv> & D) { flat_inner_direction<Nx>(*this, t, e, v, a, D); });
+  }
 };
 
 /// theta (Scalar: returns double) or ce of the flattened problem (FlatEndptFun), variables (tf | e0 | ef | q)
-template<class X, int Nq, int R, bool Scalar, class Fn, class Xl>
+template<class X, int Nq, int R, bool Scalar, class Fn, class Xl, FlatHess HM = FlatHess::None>
 struct FlatEndptFun {
-  static constexpr int Nx = X::Dof, ne = 1 + 2 * Nx + Nq;
+  static constexpr int Nx = X::Dof, nq = Nq, ne = 1 + 2 * Nx + Nq;
+  static constexpr bool inner_has_jacobian =
+    requires(const Fn & fn, const X & x, const Vec<Nq> & q, Mat<R, ne> & J) { fn.jacobian(0.0, x, x, q, J); };
   Fn f;
   Xl xl;
   SFB_LIE_HD static Vec<R> as_vec(const Fn & fn, double tf, const X & x0, const X & xf, const Vec<Nq> & q)
@@ -350,6 +522,12 @@ struct FlatEndptFun {
   SFB_LIE_HD auto operator()(double tf, const Rn<Nx> & e0, const Rn<Nx> & ef, const Vec<Nq> & q) const
   {
     return f(tf, rplus(xl(0.0), e0.v), rplus(xl(tf), ef.v), q);
+  }
+  /// the flat value as a vector, scalar or not
+  SFB_LIE_HD static Vec<R> as_vec_flat(const FlatEndptFun & fun, double tf, const Rn<Nx> & e0, const Rn<Nx> & ef, const Vec<Nq> & q)
+  {
+    if constexpr (Scalar) return Vec<R>{fun(tf, e0, ef, q)};
+    else return fun(tf, e0, ef, q);
   }
   SFB_LIE_HD void jacobian(double tf, const Rn<Nx> & e0, const Rn<Nx> & ef, const Vec<Nq> & q, Mat<R, ne> & J) const
   {
@@ -392,6 +570,12 @@ struct FlatEndptFun {
       for (int c = 0; c < Nq; ++c) J(r, 1 + 2 * Nx + c) = Jf(r, 1 + 2 * Nx + c);
     }
   }
+  /// the Hessians of the R rows side by side (EndEval's layout), FlatHess::Differences only
+  SFB_LIE_HD void hessian(double tf, const Rn<Nx> & e0, const Rn<Nx> & ef, const Vec<Nq> & q, Mat<ne, R * ne> & H) const
+    requires(HM == FlatHess::Differences)
+  {
+    flat_hessian_from_directions<R, ne>(H, [&](int a, Mat<R, ne> & D) { flat_end_direction<R>(*this, tf, e0, ef, q, a, D); });
+  }
 };
 
 }  // namespace detail
@@ -413,19 +597,20 @@ struct FlatOCP {
   Vec<Nce> cel{}, ceu{};
 };
 
-/// flatten_ocp (:513-541): the problem in (e, v) around the trajectories xl, ul; sizes Nq, Ncr, Nce >= 1
-template<class Ocp, class Xl, class Ul>
+/// flatten_ocp (:513-541): the problem in (e, v) around the trajectories xl, ul; sizes Nq, Ncr, Nce >= 1.
+/// flatten_ocp<FlatHess::Differences>(ocp, xl, ul): the flat functors carry hessian members (the law at the top).
+template<FlatHess HM = FlatHess::None, class Ocp, class Xl, class Ul>
 SFB_LIE_HD auto flatten_ocp(const Ocp & ocp, const Xl & xl, const Ul & ul)
 {
   using X = typename Ocp::X;
   using U = typename Ocp::U;
   constexpr int Nq = Ocp::Nq, Ncr = Ocp::Ncr, Nce = Ocp::Nce;
   static_assert(Nq >= 1 && Ncr >= 1 && Nce >= 1, "flatten_ocp: Nq, Ncr, Nce >= 1");
-  using Theta = detail::FlatEndptFun<X, Nq, 1, true, std::decay_t<decltype(ocp.theta)>, Xl>;
-  using F     = detail::FlatDyn<X, U, std::decay_t<decltype(ocp.f)>, Xl, Ul>;
-  using G     = detail::FlatInnerFun<X, U, Nq, std::decay_t<decltype(ocp.g)>, Xl, Ul>;
-  using CR    = detail::FlatInnerFun<X, U, Ncr, std::decay_t<decltype(ocp.cr)>, Xl, Ul>;
-  using CE    = detail::FlatEndptFun<X, Nq, Nce, false, std::decay_t<decltype(ocp.ce)>, Xl>;
+  using Theta = detail::FlatEndptFun<X, Nq, 1, true, std::decay_t<decltype(ocp.theta)>, Xl, HM>;
+  using F     = detail::FlatDyn<X, U, std::decay_t<decltype(ocp.f)>, Xl, Ul, HM>;
+  using G     = detail::FlatInnerFun<X, U, Nq, std::decay_t<decltype(ocp.g)>, Xl, Ul, HM>;
+  using CR    = detail::FlatInnerFun<X, U, Ncr, std::decay_t<decltype(ocp.cr)>, Xl, Ul, HM>;
+  using CE    = detail::FlatEndptFun<X, Nq, Nce, false, std::decay_t<decltype(ocp.ce)>, Xl, HM>;
   return FlatOCP<X, U, Nq, Ncr, Nce, Theta, F, G, CR, CE>{Theta{ocp.theta, xl}, F{ocp.f, xl, ul},   G{ocp.g, xl, ul}, CR{ocp.cr, xl, ul},
                                                           ocp.crl,              ocp.cru,           CE{ocp.ce, xl},   ocp.cel,
                                                           ocp.ceu};
