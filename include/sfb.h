@@ -546,6 +546,17 @@ sfb_status sfb_mpc_swarm_upload(sfb_mpc_swarm *swarm, int64_t first, int64_t cou
 sfb_status sfb_mpc_swarm_device_records(sfb_mpc_swarm *swarm, double **records, int64_t *record_doubles);
 sfb_status sfb_mpc_swarm_step_resident(sfb_mpc_swarm *swarm, const sfb_qp_params *prm, int warmstart, double *du0,
                                        uint32_t *iter, int32_t *code, double *primal, double *dual);
+/* A re-linearisation pass behind a tick (sequential convex MPC, include/smooth_feedback_amd/mpc_relin.hpp): the resident
+ * tick for FLAT records -- dynamics and running constraint linearised about the plan of the last solve
+ * (sfb_mpc_swarm_device_solution) in the same unknowns, written into the swarm's device record buffer by the caller's kernel
+ * on the null stream.  Flat records are always UNPACKED (the record layout above, whatever the swarm's packing) and are
+ * assembled in the commutative mode whatever the layout's state group: the Jacobians as they are, no ad(f + dxdes) term.
+ * The warm start is always on: every agent starts from the solution it has stored.  An agent whose solve ends Optimal,
+ * MaxTime or MaxIterations takes the new solution (and stores it); any other agent keeps the plan, dual, code and iteration
+ * count it had, so the swarm's solution buffers hold every agent's last accepted plan.  Outputs as
+ * sfb_mpc_swarm_step_resident, of the plans the swarm holds afterwards; same stream and ownership contract. */
+sfb_status sfb_mpc_swarm_step_resident_flat(sfb_mpc_swarm *swarm, const sfb_qp_params *prm, double *du0, uint32_t *iter,
+                                            int32_t *code, double *primal, double *dual);
 
 /* Switch the packing of the per-agent records (layout->jac_keep semantics; NULL = unpacked) of an existing swarm --
  * e.g. back to full records when a linearisation turns out to have a non-zero where the flags said zero.  The swarm's

@@ -33,6 +33,7 @@
 #include "dyn_error.hpp"
 #include "lie.hpp"
 #include "mesh.hpp"
+#include "mpc_relin.hpp"
 #include "qp.hpp"
 #include "time.hpp"
 
@@ -98,6 +99,10 @@ struct MPCParams {
   /// instead of on everything ocp_to_qp stores (dense Jacobian blocks: block_add, utils/sparse.hpp:33-50).  Exact
   /// (explicit zeros contribute exact zeros) and verified per solve on the device, see analyze_solver().
   bool prune_explicit_zeros{true};
+  /// (not in the reference) Sequential convex passes after the tick's solve (mpc_relin.hpp): re-linearise dynamics and
+  /// running constraint about the plan just found, solve again warm-started, `relin_passes` times.  0: the reference's
+  /// single solve.  Acts in MPC::operator(); MPCSwarmDeviceLin::step takes its own count.
+  std::size_t relin_passes{0};
 };
 
 /// mpc.hpp:344-356
@@ -202,7 +207,11 @@ public:
   /// Construct a new MPC (or pass the weights to the constructor) to control with other weights.
   void set_weights(const MPCWeights<X, U> & w) { weights_ = w; }
   const MPCWeights<X, U> & weights() const { return weights_; }
-  void reset_warmstart() { warm_.reset(); }
+  void reset_warmstart()
+  {
+    warm_.reset();
+    relin_warm_.reset();
+  }
 
   // ---- sizes / pattern ----
   int N() const { return mesh_.N_colloc(); }
@@ -568,6 +577,148 @@ private:
   }
 
 public:
+  /// The FLAT record of a plan (mpc_relin.hpp): dynamics and running constraint re-linearised about primal =
+  /// [e_0 .. e_N | v_0 .. v_{N-1}] (a tick's solution), the initial state pinned exactly.  Length and offsets of
+  /// fill_record's unpacked record; to be assembled in the commutative mode (assemble_flat_record, or
+  /// sfb_mpc_swarm_step_resident_flat on the device).  primal == nullptr: the plan e = v = 0.  Thread-safe (const).
+  void fill_flat_record(const T & t, const X & x, const double * primal, double * rec) const
+  {
+    if constexpr (kTimedFunctors) {
+      std::remove_cvref_t<F> fc   = f_;
+      std::remove_cvref_t<CR> crc = cr_;
+      fill_flat_record_with(fc, crc, t, x, primal, rec);
+    } else {
+      fill_flat_record_with(f_, cr_, t, x, primal, rec);
+    }
+  }
+  /// A, l, u of a flat record: the arithmetic of the assembly kernel's commutative mode (sfb_mpc_layout::nparts == 0) in
+  /// its order -- the Jacobians as they are, no ad(f + dxdes) term.
+  void assemble_flat_record(const double * rec, double * Aval, double * l, double * u) const
+  {
+    const int Nn = N();
+    const double tf = prm_.tf;
+    const double *f = rec, *dx = f + Nn * Nx, *dfx = dx + Nn * Nx, *dfu = dfx + Nn * Nx * Nx, *cc = dfu + Nn * Nx * Nu,
+                 *dcx = cc + Nn * Ncr, *dcu = dcx + Nn * Ncr * Nx, *e0 = dcu + Nn * Ncr * Nu, *Jm = e0 + Nx;
+    for (int s = 0, M = 0; s < mesh_.N_ivals(); M += Kmesh, ++s) {
+      const double alpha = mesh_.alpha(s);
+      for (int i = 0; i < Kmesh; ++i) {
+        const int node = M + i;
+        for (int d = 0; d < Nx; ++d) {
+          const int row = dcon_B() + node * Nx + d;
+          int p         = qp_.A_rowptr[row];
+          for (int j = 0; j <= Kmesh; ++j) {
+            const double dc = alpha * mesh_.D(j, i);
+            if (j == i) {
+              for (int c = 0; c < Nx; ++c) {
+                double v = 0.0;
+                v += tf * dfx[(node * Nx + d) * Nx + c];
+                if (c == d) v -= dc;
+                Aval[p++] = v;
+              }
+            } else {
+              double v = 0.0;
+              v -= dc;
+              Aval[p++] = v;
+            }
+          }
+          for (int c = 0; c < Nu; ++c) Aval[p++] = 0.0 + tf * dfu[(node * Nx + d) * Nu + c];
+          l[row] = -tf * (f[node * Nx + d] - dx[node * Nx + d]);
+          u[row] = l[row];
+        }
+      }
+    }
+    for (int node = 0; node < Nn; ++node)
+      for (int d = 0; d < Ncr; ++d) {
+        const int row = crcon_B() + node * Ncr + d;
+        int p         = qp_.A_rowptr[row];
+        for (int c = 0; c < Nx; ++c) Aval[p++] = dcx[(node * Ncr + d) * Nx + c];
+        for (int c = 0; c < Nu; ++c) Aval[p++] = dcu[(node * Ncr + d) * Nu + c];
+        l[row] = crl_[d] - cc[node * Ncr + d];
+        u[row] = cru_[d] - cc[node * Ncr + d];
+      }
+    for (int d = 0; d < Nx; ++d) {
+      const int row = cecon_B() + d;
+      int p         = qp_.A_rowptr[row];
+      for (int c = 0; c < Nx; ++c) Aval[p++] = Jm[d * Nx + c];
+      l[row] = 0.0 - e0[d];
+      u[row] = 0.0 - e0[d];
+    }
+  }
+  /// probe_default plus the structure of the flat Jacobians: the A of flat records about generic non-zero plans (the ad
+  /// and dr_expinv terms fill the group blocks there).  For analyze_solver(keep) of a controller that runs re-linearisation
+  /// passes: without it a pruned plan stays correct (the device check falls back to the whole pattern), but every later
+  /// pass pays the fallback.  Deterministic.
+  void probe_relin(const T & t, std::vector<uint8_t> & keep) const
+  {
+    probe_default(t, keep);
+    std::vector<double> plan((size_t)nvar()), rec((size_t)record_doubles(N())), Av(qp_.A_val.size()), lv(qp_.m), uv(qp_.m);
+    uint64_t lcg = 0xD1B54A32D192ED03ull;
+    auto next    = [&] {
+      lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+      return double(lcg >> 11) / 9007199254740992.0 - 0.5;
+    };
+    for (int s = 0; s < 3; ++s) {
+      const T ts = tplus(t, s * prm_.tf / double(N()));
+      for (auto & v : plan) v = next();
+      TangentX xi{};
+      for (auto & v : xi) v = next();
+      fill_flat_record(ts, rplus(des_->xdes(ts), xi), plan.data(), rec.data());
+      assemble_flat_record(rec.data(), Av.data(), lv.data(), uv.data());
+      probe_values(Av.data(), keep);
+    }
+  }
+
+private:
+  template<class Fn, class CRn>
+  void fill_flat_record_with(Fn & fn, CRn & crn, const T & t, const X & x, const double * primal, double * rec) const
+  {
+    const int Nn = N();
+    const double tf = prm_.tf;
+    double *f = rec, *dx = f + Nn * Nx, *dfx = dx + Nn * Nx, *dfu = dfx + Nn * Nx * Nx, *cc = dfu + Nn * Nx * Nu,
+           *dcx = cc + Nn * Ncr, *dcu = dcx + Nn * Ncr * Nx, *e0 = dcu + Nn * Ncr * Nu, *Jm = e0 + Nx;
+    for (int node = 0; node < Nn; ++node) {
+      const double t_i   = tf * mesh_.node(node);
+      const X xl         = des_->xdes(tplus(t, t_i));
+      const TangentX dxl = des_->dxdes(tplus(t, t_i));
+      const U ul         = des_->udes(tplus(t, t_i));
+      Vec<Nx> ebar{};
+      Vec<Nu> vbar{};
+      if (primal) {
+        for (int d = 0; d < Nx; ++d) ebar[d] = primal[node * Nx + d];
+        for (int d = 0; d < Nu; ++d) vbar[d] = primal[uvar_B() + node * Nu + d];
+      }
+      Vec<Nx> f0;
+      Mat<Nx, Nx> A;
+      Mat<Nx, Nu> B;
+      detail::set_time_if<T>(fn, tplus(t, t_i));
+      detail::relin_dyn_node<X, U>(fn, xl, dxl, ul, ebar, vbar, f0, A, B);
+      for (int d = 0; d < Nx; ++d) {
+        f[node * Nx + d]  = f0[d];
+        dx[node * Nx + d] = 0.0;
+        for (int c = 0; c < Nx; ++c) dfx[(node * Nx + d) * Nx + c] = A(d, c);
+        for (int c = 0; c < Nu; ++c) dfu[(node * Nx + d) * Nu + c] = B(d, c);
+      }
+      if constexpr (Ncr > 0) {
+        Vec<Ncr> c0;
+        Mat<Ncr, Nx> C;
+        Mat<Ncr, Nu> D;
+        detail::set_time_if<T>(crn, tplus(t, t_i));
+        detail::relin_cr_node<X, U, Ncr>(crn, xl, dxl, ul, ebar, vbar, c0, C, D);
+        for (int d = 0; d < Ncr; ++d) {
+          cc[node * Ncr + d] = c0[d];
+          for (int c = 0; c < Nx; ++c) dcx[(node * Ncr + d) * Nx + c] = C(d, c);
+          for (int c = 0; c < Nu; ++c) dcu[(node * Ncr + d) * Nu + c] = D(d, c);
+        }
+      }
+    }
+    const TangentX e = rminus(des_->xdes(t), x);  // = -e_0: the assembled row is  I e_0 = 0 - e
+    for (int d = 0; d < Nx; ++d) {
+      e0[d] = e[d];
+      for (int c = 0; c < Nx; ++c) Jm[d * Nx + c] = (c == d) ? 1.0 : 0.0;
+    }
+  }
+
+public:
   /// mpc.hpp:518   udes(0) (+) primal[uvar_B : +Nu]
   U input_from_primal(const T & t, const double * primal) const
   {
@@ -640,6 +791,8 @@ public:
     if (last_primal_.empty()) throw std::logic_error("MPC::dyn_error: no solution stored (call operator() first)");
     return dyn_error(t, last_primal_.data());
   }
+  /// the plan the last operator() call left, in the QP's unknowns [e_0 .. e_N | v_0 .. v_{N-1}] (empty before the first call)
+  const std::vector<double> & last_primal() const { return last_primal_; }
 
 private:
   std::pair<U, QPSolutionStatus> solve_tick(const T & t, const X & x, std::vector<U> * u_traj, std::vector<X> * x_traj)
@@ -649,10 +802,17 @@ private:
     if (!solver_.analyzed()) {
       std::vector<uint8_t> keep;
       probe_values(qp_.A_val.data(), keep);
-      probe_default(t, keep);
+      if (prm_.relin_passes > 0) probe_relin(t, keep);  // (contains probe_default)
+      else probe_default(t, keep);
       analyze_solver(&keep);
     }
     QPSolution<> sol = solver_.solve(qp_, warm_ ? &*warm_ : nullptr);  // :491
+    if (prm_.relin_passes > 0) {
+      // sequential convex passes (mpc_relin.hpp).  The stored warm start follows :510-516 after every solve; a pass whose
+      // solve fails leaves the previous pass's plan and code.
+      store_warmstart(sol);
+      for (std::size_t pass = 0; pass < prm_.relin_passes; ++pass) relin_pass(t, x, sol);
+    }
     const int Nn = N();
     if (u_traj) {  // :494-500
       u_traj->resize(Nn);
@@ -677,6 +837,28 @@ private:
     const U u0 = input_from_primal(t, sol.primal.data());
     last_primal_.swap(sol.primal);  // what dyn_error(t) audits: handed over, not copied
     return {u0, sol.code};
+  }
+
+  static bool plan_kept(QPSolutionStatus c) { return detail::relin_plan_kept(static_cast<int>(c)); }
+  void store_warmstart(const QPSolution<> & sol)
+  {
+    if (prm_.warmstart && plan_kept(sol.code)) warm_ = sol;
+  }
+  /// one re-linearisation pass: flat record about `sol` (about e = v = 0 when its code is not one the controller keeps),
+  /// assembly in the commutative mode, solve from the stored solution -- the controller's warm start, or with
+  /// MPCParams::warmstart off the last accepted pass (what a device-resident swarm does with its stored solution).
+  /// An accepted solve (Optimal / MaxTime / MaxIterations) replaces `sol` and is stored; any other leaves both.
+  void relin_pass(const T & t, const X & x, QPSolution<> & sol)
+  {
+    relin_rec_.resize((size_t)record_doubles(N()));
+    fill_flat_record_with(f_, cr_, t, x, plan_kept(sol.code) ? sol.primal.data() : nullptr, relin_rec_.data());
+    assemble_flat_record(relin_rec_.data(), qp_.A_val.data(), qp_.l.data(), qp_.u.data());
+    std::optional<QPSolution<>> & stored = prm_.warmstart ? warm_ : relin_warm_;
+    QPSolution<> next = solver_.solve(qp_, stored ? &*stored : nullptr);
+    if (plan_kept(next.code)) {
+      stored = next;
+      sol    = std::move(next);
+    }
   }
 
   // a new linearisation trajectory may have other explicit zeros: looked at by refresh_structure() at the next solve
@@ -774,6 +956,8 @@ private:
   std::vector<uint8_t> keep_analysed_;  // the A_keep mask of the current analysis (empty: whole pattern)
   uint64_t seen_generation_ = 0;        // des_->generation this controller's analysis has looked at
   std::optional<QPSolution<>> warm_;
+  std::optional<QPSolution<>> relin_warm_;  // stored solution of the re-linearisation passes when warmstart is off
+  std::vector<double> relin_rec_;           // the flat record of a pass
 };
 
 /// A swarm of agents running the same MPC (same model, horizon and weights => same QP pattern),

@@ -26,6 +26,7 @@
 #include "detail/device_arena.hpp"
 #include "mesh_device.hpp"
 #include "mpc.hpp"
+#include "mpc_relin.hpp"
 
 namespace smooth_feedback_amd {
 
@@ -105,6 +106,80 @@ __global__ void __launch_bounds__(64) mpc_linearise_kernel(const int64_t B, cons
     }
   }
   if (bad) atomicOr(misfit, 1);
+}
+
+/// The re-linearisation pass of mpc_relin.hpp: one lane per (agent, node) writes its slice of the agent's FLAT record
+/// (unpacked: the offsets of sfb.h at N nodes) about the plan the swarm holds -- primal [B][n] = [e_0 .. e_N | v_0 .. v_{N-1}],
+/// code [B] (sfb_mpc_swarm_device_solution); an agent whose code is not one the swarm keeps is re-linearised about
+/// e = v = 0.  Lane `N` of an agent pins the initial state.  The law is relin_dyn_node / relin_cr_node, the functions the
+/// host's MPC::fill_flat_record calls, forced inline; every loop over matrix entries has compile-time bounds.
+template<class X, class U, int Ncr, class Model>
+__global__ void __launch_bounds__(64) mpc_relinearise_kernel(const int64_t B, const int N, const double tf, const int64_t n, const Model model,
+                                                             const double * __restrict__ tau, const double * __restrict__ t,
+                                                             const X * __restrict__ xs, const double * __restrict__ primal,
+                                                             const int32_t * __restrict__ code, double * __restrict__ records)
+{
+  constexpr int Nx = X::Dof, Nu = U::Dof;
+  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int per     = N + 1;
+  const int64_t b   = gid / per;
+  const int node    = (int)(gid - b * per);
+  if (b >= B) return;
+  const int o_f = 0, o_dx = o_f + N * Nx, o_dfdx = o_dx + N * Nx, o_dfdu = o_dfdx + N * Nx * Nx, o_c = o_dfdu + N * Nx * Nu,
+            o_dcdx = o_c + N * Ncr, o_dcdu = o_dcdx + N * Ncr * Nx, o_e = o_dcdu + N * Ncr * Nu, o_J = o_e + Nx;
+  double * rec = records + b * (int64_t)(o_J + Nx * Nx);
+  if (node < N) {
+    const double ti = t[b] + tf * tau[node];
+    const X xl      = model.xdes(ti);
+    const auto dxl  = model.dxdes(ti);
+    const U ul      = model.udes(ti);
+    const bool kept = relin_plan_kept(code[b]);
+    const double * pe = primal + b * n + (int64_t)node * Nx;
+    const double * pv = primal + b * n + (int64_t)(N + 1) * Nx + (int64_t)node * Nu;
+    Vec<Nx> ebar;
+    Vec<Nu> vbar;
+#pragma unroll
+    for (int d = 0; d < Nx; ++d) ebar[d] = kept ? pe[d] : 0.0;
+#pragma unroll
+    for (int d = 0; d < Nu; ++d) vbar[d] = kept ? pv[d] : 0.0;
+    {
+      Vec<Nx> f0;
+      Mat<Nx, Nx> A;
+      Mat<Nx, Nu> Bm;
+      relin_dyn_node<X, U>(model.f, xl, dxl, ul, ebar, vbar, f0, A, Bm);
+#pragma unroll
+      for (int d = 0; d < Nx; ++d) {
+        rec[o_f + node * Nx + d]  = f0[d];
+        rec[o_dx + node * Nx + d] = 0.0;
+#pragma unroll
+        for (int c = 0; c < Nx; ++c) rec[o_dfdx + (node * Nx + d) * Nx + c] = A(d, c);
+#pragma unroll
+        for (int c = 0; c < Nu; ++c) rec[o_dfdu + (node * Nx + d) * Nu + c] = Bm(d, c);
+      }
+    }
+    if constexpr (Ncr > 0) {
+      Vec<Ncr> c0;
+      Mat<Ncr, Nx> C;
+      Mat<Ncr, Nu> D;
+      relin_cr_node<X, U, Ncr>(model.cr, xl, dxl, ul, ebar, vbar, c0, C, D);
+#pragma unroll
+      for (int d = 0; d < Ncr; ++d) {
+        rec[o_c + node * Ncr + d] = c0[d];
+#pragma unroll
+        for (int c = 0; c < Nx; ++c) rec[o_dcdx + (node * Ncr + d) * Nx + c] = C(d, c);
+#pragma unroll
+        for (int c = 0; c < Nu; ++c) rec[o_dcdu + (node * Ncr + d) * Nu + c] = D(d, c);
+      }
+    }
+  } else {  // e_0 = log(xdes(t)^-1 x) exactly: J = I and e = xdes(t) (-) x = -e_0 (the assembled row is J e_0 = 0 - e)
+    const auto e = rminus(model.xdes(t[b]), xs[b]);
+#pragma unroll
+    for (int d = 0; d < Nx; ++d) {
+      rec[o_e + d] = e[d];
+#pragma unroll
+      for (int c = 0; c < Nx; ++c) rec[o_J + d * Nx + c] = (c == d) ? 1.0 : 0.0;
+    }
+  }
 }
 
 }  // namespace detail
@@ -189,6 +264,50 @@ public:
       codes[(size_t)b] = static_cast<QPSolutionStatus>(code_[(size_t)b]);
     }
   }
+  /// one control tick followed by `passes` re-linearisation passes (sequential convex MPC, mpc_relin.hpp): the tick above,
+  /// then `passes` times mpc_relinearise_kernel about the plans the swarm holds and sfb_mpc_swarm_step_resident_flat, all
+  /// on the null stream.  The host only waits where step() already does, for the small outputs of every solve; nothing is
+  /// allocated.  passes == 0 is step(t, xs, us, codes).  us / codes / iterations() are those of the plans held at the end.
+  /// A prototype analysed with a mask of MPC::probe_relin keeps the passes on the pruned plan.
+  void step(const std::vector<double> & t, const std::vector<X> & xs, std::vector<U> & us, std::vector<QPSolutionStatus> & codes, int passes)
+  {
+    if ((int64_t)t.size() != B_ || (int64_t)xs.size() != B_) throw std::invalid_argument("MPCSwarmDeviceLin: one time and state per agent");
+    us.resize((size_t)B_);
+    codes.resize((size_t)B_);
+    step(t.data(), xs.data(), us.data(), codes.data(), passes);
+  }
+  void step(const double * t, const X * xs, U * us, QPSolutionStatus * codes, int passes)
+  {
+    if (passes < 0) throw std::invalid_argument("MPCSwarmDeviceLin: passes < 0");
+    step(t, xs, us, codes);
+    if (passes == 0) return;
+    const sfb_qp_params c = mpc_.solver().params().to_c();
+    for (int pass = 0; pass < passes; ++pass) {
+      relinearise(nullptr);
+      sfb_check(sfb_mpc_swarm_step_resident_flat(swarm_, &c, du0_.data(), iter_.data(), code_.data(), nullptr, nullptr));
+    }
+    for (int64_t b = 0; b < B_; ++b) {
+      us[(size_t)b]    = mpc_.input_from_du0(t[(size_t)b], &du0_[(size_t)b * Nu]);
+      codes[(size_t)b] = static_cast<QPSolutionStatus>(code_[(size_t)b]);
+    }
+  }
+  /// the kernel of a pass alone, on `stream`: flat records about the swarm's current plans into its device record buffer,
+  /// from the times and states of the last step() (unpacked: MPCT::record_doubles(N) per agent, whatever packed_records())
+  void relinearise(hipStream_t stream)
+  {
+    const double * dprimal = nullptr;
+    const int32_t * dcode  = nullptr;
+    sfb_check(sfb_mpc_swarm_device_solution(swarm_, &dprimal, nullptr, &dcode));
+    const int Nn = mpc_.N();
+    hipLaunchKernelGGL((detail::mpc_relinearise_kernel<X, U, Ncr, Model>), detail::lane_grid(B_ * (Nn + 1)), dim3(64), 0, stream, B_, Nn,
+                       mpc_.params().tf, (int64_t)mpc_.qp().n, model_, dtau_, dt_, dx_, dprimal, dcode, drec_);
+    check(hipGetLastError(), "mpc_relinearise_kernel");
+  }
+  /// the flat records of the last pass (device -> host), [agents][MPCT::record_doubles(N)]
+  void copy_flat_records(double * out) const
+  {
+    check(detail::download(out, drec_, (size_t)B_ * (size_t)MPCT::record_doubles(mpc_.N())), "hipMemcpy(records)");
+  }
   /// what audit() brings back: 8 bytes per agent and per interval
   struct Audit {
     std::vector<double> agent_max;  // [agents] largest interval error of the agent's plan (NaN: the plan has a NaN)
@@ -246,6 +365,7 @@ public:
     if (code) check(detail::download(code, dcode, (size_t)B_), "hipMemcpy(code)");
   }
   int64_t size() const { return B_; }
+  sfb_mpc_swarm * handle() { return swarm_; }
   const std::vector<uint32_t> & iterations() const { return iter_; }
   bool packed_records() const { return packed_; }
   int64_t record_doubles() const { return map_.rec_doubles; }

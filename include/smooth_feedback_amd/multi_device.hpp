@@ -156,6 +156,18 @@ public:
       std::copy(part_[i]->iterations().begin(), part_[i]->iterations().end(), iter_.begin() + s.first);
     });
   }
+  /// ... followed by `passes` re-linearisation passes on every shard (MPCSwarmDeviceLin::step(.., passes)).  An overload of
+  /// its own: a model that never calls it does not instantiate the re-linearisation kernel.
+  void step(const std::vector<double> & t, const std::vector<X> & xs, std::vector<U> & us, std::vector<QPSolutionStatus> & codes, int passes)
+  {
+    if ((int64_t)t.size() != B_ || (int64_t)xs.size() != B_) throw std::invalid_argument("MPCSwarmMultiDeviceLin: one time and state per agent");
+    us.resize((size_t)B_);
+    codes.resize((size_t)B_);
+    cut_.for_each([&](size_t i, const DeviceShards::Shard & s) {
+      part_[i]->step(t.data() + s.first, xs.data() + s.first, us.data() + s.first, codes.data() + s.first, passes);
+      std::copy(part_[i]->iterations().begin(), part_[i]->iterations().end(), iter_.begin() + s.first);
+    });
+  }
   const std::vector<uint32_t> & iterations() const { return iter_; }
 
 private:

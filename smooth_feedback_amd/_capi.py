@@ -189,6 +189,7 @@ def _load():
     L.sfb_mpc_swarm_step_host.argtypes = [vp, C.POINTER(SfbQPParams), dp, dp, i32, dp, dp, dp, dp, dp]
     L.sfb_mpc_swarm_device_records.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.sfb_mpc_swarm_step_resident.argtypes = [vp, C.POINTER(SfbQPParams), i32, dp, dp, dp, dp, dp]
+    L.sfb_mpc_swarm_step_resident_flat.argtypes = [vp, C.POINTER(SfbQPParams), dp, dp, dp, dp, dp]
     L.sfb_mpc_swarm_debug_buffers.argtypes = [vp] + [C.POINTER(C.c_void_p)] * 3
     L.sfb_set_devices.argtypes = [C.POINTER(C.c_int), i32]
     L.sfb_get_devices.argtypes = [C.POINTER(C.c_int), i32, C.POINTER(C.c_int)]

@@ -183,6 +183,7 @@ void fill_params(const sfb_mpc_layout *L, bool shared, sfb::MpcAsmParams &p)
 struct sfb_mpc_swarm {
   sfb_sparse_qp_plan *plan = nullptr;
   sfb::MpcAsmParams rec_own{}, rec_shared{};
+  sfb::MpcAsmParams rec_flat{};  // flat records of a re-linearisation pass: unpacked, commutative (no ad term)
   int64_t rec_full_doubles = 0;  // per-agent record without packing: what the record buffers are sized for
   int64_t agents = 0, shared_doubles = 0;
   int n = 0, m = 0, nnzP = 0, nnzA = 0, nu = 0, uoff = 0, devid = 0;
@@ -190,9 +191,10 @@ struct sfb_mpc_swarm {
   char *mem = nullptr;
   double *Px = nullptr, *q = nullptr, *Ax = nullptr, *l = nullptr, *u = nullptr, *x = nullptr, *y = nullptr, *wx = nullptr,
          *wy = nullptr, *rec = nullptr, *shared = nullptr, *du0 = nullptr, *ws = nullptr;
-  uint32_t *iter = nullptr;
-  int32_t *code = nullptr, *order = nullptr;
-  sfb::MpcAsmDesc *table_own = nullptr, *table_shared = nullptr;  // the assembly kernel's tables (one allocation; mpc_kernel.h)
+  double *xn = nullptr, *yn = nullptr;  // where a re-linearisation pass solves to, before its agents accept or keep
+  uint32_t *iter = nullptr, *itern = nullptr;
+  int32_t *code = nullptr, *order = nullptr, *coden = nullptr;
+  sfb::MpcAsmDesc *table_own = nullptr, *table_shared = nullptr, *table_flat = nullptr;  // the assembly kernel's tables (one allocation; mpc_kernel.h)
   char *h_out = nullptr;          // pinned: [du0 | iter | code] of a tick come back in ONE copy (they are adjacent on the device)
   std::vector<uint32_t> h_iter;   // iteration counts of the last tick (host), for the launch order of the next
   std::vector<int32_t> h_order;
@@ -258,9 +260,15 @@ sfb_status sfb_mpc_swarm_create(sfb_sparse_qp_plan *plan, const sfb_mpc_layout *
   if (st != SFB_OK) return st;
   if (agents < 1 || agents > 0x7FFFFFFFll) return sfb::fail(SFB_ERR_INVALID_ARG, "agents must be in [1, 2^31-1]");
   const sfb::SparsePlanHost &h = sfb::plan_io(plan);
-  sfb::MpcAsmParams p, ps, pfull;
+  sfb::MpcAsmParams p, ps, pfull, pflat;
   fill_params(layout, false, p);
   fill_params(layout, true, ps);
+  {  // flat records: the same transcription as a commutative state with unpacked records
+    sfb_mpc_layout flat = *layout;
+    flat.nparts   = 0;
+    flat.jac_keep = nullptr;
+    fill_params(&flat, false, pflat);
+  }
   pfull = p;
   set_packing(pfull, false, nullptr);  // buffers are sized for unpacked records: the packing may be switched later
   const int n = layout->nx * (p.N + 1) + layout->nu * p.N;
@@ -294,7 +302,7 @@ sfb_status sfb_mpc_swarm_create(sfb_sparse_qp_plan *plan, const sfb_mpc_layout *
   st = sfb::require_device();
   if (st != SFB_OK) return st;
   auto *S = new sfb_mpc_swarm;
-  S->plan = plan; S->rec_own = p; S->rec_shared = ps; S->agents = agents; S->rec_full_doubles = pfull.rec_doubles;
+  S->plan = plan; S->rec_own = p; S->rec_shared = ps; S->rec_flat = pflat; S->agents = agents; S->rec_full_doubles = pfull.rec_doubles;
   S->n = n; S->m = p.m; S->nnzP = h.nnzP; S->nnzA = p.nnzA; S->nu = layout->nu; S->uoff = layout->nx * (p.N + 1);
   S->shared_doubles = sfb_mpc_shared_jac_doubles(layout);
   {
@@ -305,9 +313,9 @@ sfb_status sfb_mpc_swarm_create(sfb_sparse_qp_plan *plan, const sfb_mpc_layout *
   }
   hipError_t e = hipGetDevice(&S->devid);
   const size_t B = (size_t)agents, N = (size_t)n, M = (size_t)p.m;
-  const size_t doubles = B * ((size_t)h.nnzP + N + (size_t)p.nnzA + 2 * M + 2 * (N + M) + (size_t)pfull.rec_doubles + (size_t)layout->nu) + S->wsd +
+  const size_t doubles = B * ((size_t)h.nnzP + N + (size_t)p.nnzA + 2 * M + 3 * (N + M) + (size_t)pfull.rec_doubles + (size_t)layout->nu) + S->wsd +
                          (size_t)S->shared_doubles + (size_t)h.nnzP + N;
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&S->mem), doubles * sizeof(double) + B * 12);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&S->mem), doubles * sizeof(double) + B * 20);
   if (e != hipSuccess) {
     delete S;
     return sfb::hip_fail(e, "hipMalloc(swarm)");
@@ -322,6 +330,8 @@ sfb_status sfb_mpc_swarm_create(sfb_sparse_qp_plan *plan, const sfb_mpc_layout *
   S->y = d; d += B * M;
   S->wx = d; d += B * N;
   S->wy = d; d += B * M;
+  S->xn = d; d += B * N;
+  S->yn = d; d += B * M;
   S->rec = d; d += B * pfull.rec_doubles;
   S->shared = d; d += S->shared_doubles;
   double *stage = d; d += h.nnzP + N;  // one copy of Px and q, replicated below
@@ -330,15 +340,19 @@ sfb_status sfb_mpc_swarm_create(sfb_sparse_qp_plan *plan, const sfb_mpc_layout *
   S->iter = reinterpret_cast<uint32_t *>(d);
   S->code  = reinterpret_cast<int32_t *>(S->iter + B);
   S->order = S->code + B;
+  S->itern = reinterpret_cast<uint32_t *>(S->order + B);
+  S->coden = reinterpret_cast<int32_t *>(S->itern + B);
   S->h_iter.assign(B, 0);
   S->h_order.resize(B);
   do {
     {  // the assembly tables of both record forms
-      std::vector<sfb::MpcAsmDesc> tb(2 * (size_t)p.nnzA);
+      std::vector<sfb::MpcAsmDesc> tb(3 * (size_t)p.nnzA);
       sfb::mpc_build_table(S->rec_own, false, tb.data());
       sfb::mpc_build_table(S->rec_shared, true, tb.data() + p.nnzA);
+      sfb::mpc_build_table(S->rec_flat, false, tb.data() + 2 * (size_t)p.nnzA);
       if ((e = hipMalloc(reinterpret_cast<void **>(&S->table_own), tb.size() * sizeof(sfb::MpcAsmDesc))) != hipSuccess) break;
       S->table_shared = S->table_own + p.nnzA;
+      S->table_flat   = S->table_shared + p.nnzA;
       if ((e = hipMemcpy(S->table_own, tb.data(), tb.size() * sizeof(sfb::MpcAsmDesc), hipMemcpyHostToDevice)) != hipSuccess) break;
     }
     if (h.nnzP > 0 && (e = hipMemcpy(stage, Px, (size_t)h.nnzP * 8, hipMemcpyHostToDevice)) != hipSuccess) break;
@@ -560,6 +574,39 @@ sfb_status sfb_mpc_swarm_step_resident(sfb_mpc_swarm *S, const sfb_qp_params *pr
                                        int32_t *code, double *primal, double *dual)
 {
   return swarm_step_impl(S, prm, nullptr, nullptr, warmstart, du0, iter, code, primal, dual, true);
+}
+
+sfb_status sfb_mpc_swarm_step_resident_flat(sfb_mpc_swarm *S, const sfb_qp_params *prm, double *du0, uint32_t *iter, int32_t *code,
+                                            double *primal, double *dual)
+{
+  if (!S) return sfb::fail(SFB_ERR_INVALID_ARG, "swarm is NULL");
+  if (!prm || !du0 || !code) return sfb::fail(SFB_ERR_INVALID_ARG, "NULL params / output pointer");
+  if (sfb_status sd = check_swarm_device(S); sd != SFB_OK) return sd;
+  std::lock_guard<std::mutex> lk(S->mu);
+  const size_t B = (size_t)S->agents;
+  hipError_t e = hipSuccess;
+  sfb_status st = SFB_OK;
+  do {
+    // the flat records are in the swarm's device buffer (written by the caller's kernel on the null stream, from the plans of
+    // sfb_mpc_swarm_device_solution); everything below is on the null stream behind it
+    if ((e = sfb::mpc_assemble_launch(S->rec_flat, S->agents, S->rec, nullptr, S->Ax, S->l, S->u, nullptr, S->table_flat)) != hipSuccess) break;
+    st = sfb_sparse_qp_solve_batch_ordered(S->plan, prm, S->agents, S->Px, S->q, S->Ax, S->l, S->u, S->wx, S->wy, S->xn, S->yn, nullptr,
+                                           S->itern, S->coden, S->ws, nullptr, nullptr);
+    if (st != SFB_OK) break;
+    if ((e = sfb::mpc_accept_launch(S->agents, S->n, S->m, S->uoff, S->nu, S->xn, S->yn, S->coden, S->itern, S->x, S->y, S->code, S->iter,
+                                    S->wx, S->wy, S->du0, nullptr)) != hipSuccess) break;
+    {  // du0 | iter | code in one copy, as the tick brings them back (the launch order of the next tick stays the tick's own)
+      const size_t nb_u = B * (size_t)S->nu * 8;
+      if ((e = hipMemcpy(S->h_out, S->du0, nb_u + B * 8, hipMemcpyDeviceToHost)) != hipSuccess) break;
+      std::memcpy(du0, S->h_out, nb_u);
+      if (iter) std::memcpy(iter, S->h_out + nb_u, B * 4);
+      std::memcpy(code, S->h_out + nb_u + B * 4, B * 4);
+    }
+    if (primal && (e = hipMemcpy(primal, S->x, B * (size_t)S->n * 8, hipMemcpyDeviceToHost)) != hipSuccess) break;
+    if (dual && (e = hipMemcpy(dual, S->y, B * (size_t)S->m * 8, hipMemcpyDeviceToHost)) != hipSuccess) break;
+  } while (false);
+  if (e != hipSuccess) st = sfb::hip_fail(e, "sfb_mpc_swarm_step_resident_flat");
+  return st;
 }
 
 sfb_status sfb_mpc_swarm_device_records(sfb_mpc_swarm *S, double **records, int64_t *record_doubles)

@@ -250,6 +250,49 @@ __global__ void __launch_bounds__(64) mpc_store_kernel(const int n, const int m,
   }
 }
 
+// after the solve of a re-linearisation pass into (xn, yn, coden, itern): an agent whose code is Optimal / MaxIterations /
+// MaxTime takes the new solution as its plan (x, y, code, iter) and as its warm start (wx, wy); any other keeps what it had.
+// du0 of the plan the agent holds afterwards.  One block per agent, as mpc_store_kernel.
+__global__ void __launch_bounds__(64) mpc_accept_kernel(const int n, const int m, const int uoff, const int nu,
+                                                        const double *__restrict__ xn, const double *__restrict__ yn,
+                                                        const int32_t *__restrict__ coden, const uint32_t *__restrict__ itern,
+                                                        double *__restrict__ x, double *__restrict__ y, int32_t *__restrict__ code,
+                                                        uint32_t *__restrict__ iter, double *__restrict__ wx, double *__restrict__ wy,
+                                                        double *__restrict__ du0)
+{
+  const int64_t b = blockIdx.x;
+  const int lane  = threadIdx.x;
+  const int32_t cd = coden[b];
+  if (cd == SFB_QP_OPTIMAL || cd == SFB_QP_MAX_TIME || cd == SFB_QP_MAX_ITERATIONS) {
+    for (int j = lane; j < n; j += 64) {
+      const double v = xn[b * n + j];
+      x[b * n + j]  = v;
+      wx[b * n + j] = v;
+    }
+    for (int i = lane; i < m; i += 64) {
+      const double v = yn[b * m + i];
+      y[b * m + i]  = v;
+      wy[b * m + i] = v;
+    }
+    for (int c = lane; c < nu; c += 64) du0[b * nu + c] = xn[b * n + uoff + c];
+    if (lane == 0) {
+      code[b] = cd;
+      iter[b] = itern[b];
+    }
+  } else {
+    for (int c = lane; c < nu; c += 64) du0[b * nu + c] = x[b * n + uoff + c];
+  }
+}
+
+hipError_t mpc_accept_launch(int64_t batch, int n, int m, int uoff, int nu, const double *xn, const double *yn, const int32_t *coden,
+                             const uint32_t *itern, double *x, double *y, int32_t *code, uint32_t *iter, double *wx, double *wy,
+                             double *du0, hipStream_t stream)
+{
+  hipLaunchKernelGGL(mpc_accept_kernel, dim3((unsigned)batch), dim3(64), 0, stream, n, m, uoff, nu, xn, yn, coden, itern, x, y,
+                     code, iter, wx, wy, du0);
+  return hipGetLastError();
+}
+
 hipError_t mpc_assemble_launch(const MpcAsmParams &p, int64_t batch, const double *records, const double *shared_jac,
                                double *Ax, double *l, double *u, hipStream_t stream, const MpcAsmDesc *table)
 {

@@ -55,5 +55,10 @@ hipError_t mpc_replicate_launch(const double *src, int64_t len, int64_t batch, d
 // (mpc.hpp:510-516); du0[b] = x[b][uoff : uoff + nu]
 hipError_t mpc_store_launch(int64_t batch, int n, int m, int uoff, int nu, int store, const double *x, const double *y,
                             const int32_t *code, double *wx, double *wy, double *du0, hipStream_t stream);
+// after the solve of a re-linearisation pass into (xn, yn, coden, itern): agents whose new code is Optimal / MaxIterations /
+// MaxTime take it as plan (x, y, code, iter) and warm start (wx, wy), the others keep theirs; du0 of the plan kept
+hipError_t mpc_accept_launch(int64_t batch, int n, int m, int uoff, int nu, const double *xn, const double *yn, const int32_t *coden,
+                             const uint32_t *itern, double *x, double *y, int32_t *code, uint32_t *iter, double *wx, double *wy,
+                             double *du0, hipStream_t stream);
 
 }  // namespace sfb
