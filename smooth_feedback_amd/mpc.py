@@ -67,10 +67,12 @@ class MPCLayout:
         k = self.jac_keep.astype(bool)
         o = np.cumsum([0, nx * nx, nx * nu, ncr * nx, ncr * nu, nx * nx])
         kfx, kfu, kcx, kcu, kJ = [k[o[i]:o[i + 1]] for i in range(5)]
+        # (the block count is spelled out: with ncr = 0 the running-constraint blocks are empty and -1 cannot be inferred)
+        nb = lambda blk: 1 if blk is J else N
         for blk, kk, per in ((dfx, kfx, nx * nx), (dfu, kfu, nx * nu), (dcx, kcx, ncr * nx), (dcu, kcu, ncr * nu), (J, kJ, nx * nx)):
-            if np.any(blk.reshape(B, -1, per)[:, :, ~kk] != 0):
+            if np.any(blk.reshape(B, nb(blk), per)[:, :, ~kk] != 0):
                 raise ValueError("a Jacobian entry outside jac_keep is not zero")
-        pk = lambda blk, kk, per: blk.reshape(B, -1, per)[:, :, kk].reshape(B, -1)
+        pk = lambda blk, kk, per: blk.reshape(B, nb(blk), per)[:, :, kk].reshape(B, -1)
         return np.ascontiguousarray(np.hstack([f, dx, pk(dfx, kfx, nx * nx), pk(dfu, kfu, nx * nu), c, pk(dcx, kcx, ncr * nx),
                                                pk(dcu, kcu, ncr * nu), e, pk(J, kJ, nx * nx)]))
 
@@ -145,6 +147,23 @@ class MPCSwarm:
         cp = (prm or QPSolverParams()).to_c()
         _capi.check(_capi.lib.sfb_mpc_swarm_step_host(self._h, C.byref(cp), _ptr(records), _ptr(shared_jac), int(bool(warmstart)),
                                                       _ptr(du0), _ptr(it), _ptr(code), _ptr(x), _ptr(y)))
+        return (du0, code, it, x, y) if full else (du0, code, it)
+
+    def device_records(self):
+        """sfb_mpc_swarm_device_records: (device pointer of the swarm's record buffer, doubles per record in the current packing)."""
+        p, rd = C.c_void_p(), C.c_int64()
+        _capi.check(_capi.lib.sfb_mpc_swarm_device_records(self._h, C.byref(p), C.byref(rd)))
+        return p.value, rd.value
+
+    def step_resident_flat(self, prm: Optional[QPSolverParams] = None, full=False):
+        """sfb_mpc_swarm_step_resident_flat: a re-linearisation pass on the FULL, flat records the caller wrote into
+        device_records().  Returns (du0 [agents, nu], code, iter[, primal, dual]) of the plans the swarm holds afterwards."""
+        B, L = self.agents, self.layout
+        du0 = np.empty((B, L.nu)); it = np.empty(B, dtype=np.uint32); code = np.empty(B, dtype=np.int32)
+        x = np.empty((B, L.n)) if full else None
+        y = np.empty((B, L.m)) if full else None
+        cp = (prm or QPSolverParams()).to_c()
+        _capi.check(_capi.lib.sfb_mpc_swarm_step_resident_flat(self._h, C.byref(cp), _ptr(du0), _ptr(it), _ptr(code), _ptr(x), _ptr(y)))
         return (du0, code, it, x, y) if full else (du0, code, it)
 
     def debug_buffers(self):
