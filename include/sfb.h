@@ -893,6 +893,103 @@ sfb_status sfb_ocp_nlp_hess_batch_host(const sfb_mesh *mesh, const sfb_ocp_dims 
                                        const double *dFg, const double *HLg, const double *dFcr, const double *HLcr,
                                        const double *d2theta, const double *d2ce_l, double *hess_val);
 
+/* ------------------------------------------------------------------------------------------
+ * Swarm SQP: a solver for a batch of NLPs  min f(x) s.t. xl <= x <= xu, gl <= g(x) <= gu  that share n, m, the CSR pattern
+ * of dg_dx (columns strictly ascending), the upper-triangle CSC pattern of the Lagrangian Hessian (rows strictly ascending,
+ * EVERY diagonal entry present) and the bounds.  The law -- QP of an iteration, the shift ladder that convexifies it, the l1
+ * merit line search, the stopping test -- is DESIGN.md, "Swarm SQP"; the inner solver is the shared-pattern sparse QP solver
+ * above.  Model-free: the caller evaluates f, df, g, the CSR values of dg_dx and the CSC values of the Hessian of
+ * f + lambda . g at the state's (x, lambda) and hands them in as device arrays, [batch] / [batch][len], C order.
+ *
+ * One iteration:  evaluate at x (sfb_nlp_sqp_state) -> sfb_nlp_sqp_direction -> while agents search: sfb_nlp_sqp_trial, evaluate
+ * f and g at x_trial, sfb_nlp_sqp_accept.  An agent that has finished is frozen: no later call changes a bit of its state.
+ * set_start, direction, trial and accept take the caller's stream (`hip_stream`: a hipStream_t, NULL = the null stream) and do
+ * all their work on it -- kernels, the QP solve and the copy of the counts --, under the contract of the `*_batch` entries:
+ * inputs are read behind the stream, outputs are complete for what the stream runs next.  direction and accept WAIT for that
+ * stream (they hand a count back).  One handle serves one stream at a time.  Call order: a direction call starts a new
+ * iteration for every unfinished agent; agents a caller left in line search are taken out of it, uncommitted.
+ * status: a value of NLPSolution::Status (nlp.hpp; 0 Optimal, 1 PrimalInfeasible, 3 MaxIterations, 5 Unknown), or
+ * SFB_NLP_RUNNING while the agent has not finished.
+ * ---------------------------------------------------------------------------------------- */
+#define SFB_NLP_RUNNING (-1)
+typedef struct sfb_nlp_sqp_params {
+  double tol;       /* Optimal when stationarity, violation and complementarity are all <= tol            (1e-6) */
+  int64_t max_iter; /* MaxIterations when an agent has taken this many steps                              (50)   */
+  double kappa;     /* a QP direction d != 0 is accepted only with d.P d >= kappa d.d                     (1e-8) */
+  double mu_first;  /* first non-zero shift of the ladder                                                 (1e-4) */
+  double mu_grow;   /* factor between rungs, > 1                                                          (8)    */
+  double mu_max;    /* an agent whose shift grows beyond this ends Unknown (below mu_first: no shift)  (1e4)  */
+  sfb_qp_params qp; /* the inner solver's (defaults, but eps_abs = eps_rel = 1e-9 and max_iter = 10000)          */
+} sfb_nlp_sqp_params;
+void sfb_nlp_sqp_params_default(sfb_nlp_sqp_params *p);
+
+/* The pattern work, host only:
+ *   the QP's P: BOTH triangles of the Hessian in CSC, rows ascending (the sparse solver takes the entries with col >= row into
+ *     its KKT matrix but multiplies by P as stored in its stopping test, so a P stored as one triangle never reports Optimal),
+ *     with the Hessian value each stored entry copies (P_src) and the slot of every diagonal (P_diag); nnzP = 2 nnzH - n;
+ *   the QP's A: the rows of dg_dx, then one row e_j per variable with a finite xl_j or xu_j, ascending j: nb rows;
+ *   a CSC view of dg_dx: per column its rows ascending and their positions in the CSR value array;
+ *   the variable of every bound row.
+ * A_rowptr [m + nb + 1], A_colind [nnzJ + nb], P_colptr [n + 1], P_rowind, P_src [nnzP], P_diag [n], Jc_colptr [n + 1],
+ * Jc_row, Jc_pos [nnzJ], bound_var [nb].  All ten NULL: only *nb is set.  Errors (SFB_ERR_INVALID_ARG), in this order: bad
+ * sizes (n < 1, m < 0, a NULL pattern or bound array), unsorted or out-of-range indices, a missing diagonal, xl > xu or
+ * gl > gu, a NaN bound. */
+sfb_status sfb_nlp_sqp_qp_pattern(int n, int m, const int32_t *J_rowptr, const int32_t *J_colind, const int32_t *H_colptr,
+                                  const int32_t *H_rowind, const double *xl, const double *xu, const double *gl, const double *gu,
+                                  int32_t *A_rowptr, int32_t *A_colind, int32_t *P_colptr, int32_t *P_rowind, int32_t *P_src,
+                                  int32_t *P_diag, int32_t *Jc_colptr, int32_t *Jc_row, int32_t *Jc_pos, int32_t *bound_var,
+                                  int64_t *nb);
+
+typedef struct sfb_nlp_sqp sfb_nlp_sqp; /* opaque */
+/* Patterns and bounds are host arrays.  params NULL: the defaults.  stage [n + m + nb] (nullable): elimination stages of the
+ * QP plan (sfb_sparse_qp_plan_create_staged; the plan is made with ordering = 1).  Owns the plan, the QP arrays, the solver
+ * workspace and the state of `batch` agents on the current device (the plan's own device copy, some KB of index tables, is uploaded by the first direction call; nothing
+ * else is allocated later).  Errors: those of the pattern
+ * builder, batch < 0, bad params, SFB_ERR_UNSUPPORTED for m + nb == 0; then SFB_ERR_NO_DEVICE.  batch == 0 is legal. */
+sfb_status sfb_nlp_sqp_create(int n, int m, const int32_t *J_rowptr, const int32_t *J_colind, const int32_t *H_colptr,
+                              const int32_t *H_rowind, const double *xl, const double *xu, const double *gl, const double *gu,
+                              int64_t batch, const sfb_nlp_sqp_params *params, const int32_t *stage, sfb_nlp_sqp **solver);
+void sfb_nlp_sqp_destroy(sfb_nlp_sqp *solver);
+/* Any output may be NULL.  nnzH: stored entries of the Hessian pattern; nnzP, nnzA: of the QP's P and A. */
+sfb_status sfb_nlp_sqp_info(const sfb_nlp_sqp *solver, int64_t *batch, int32_t *n, int32_t *m, int32_t *nb, int64_t *nnzH,
+                            int64_t *nnzP, int64_t *nnzA);
+/* x [batch][n], lambda [batch][m], z [batch][n]: device pointers, the multipliers nullable (zero).  Resets shift, penalty,
+ * iteration count, status and the QP warm starts of every agent.  Asynchronous on `hip_stream`. */
+sfb_status sfb_nlp_sqp_set_start(sfb_nlp_sqp *solver, const double *x, const double *lambda, const double *z,
+                                 void *hip_stream);
+/* The stopping test on the current (x, lambda, z), then for the agents that go on the QP of the iteration through the shift
+ * ladder.  f [batch], df [batch][n], g [batch][m], dg_val [batch][nnzJ], hess_val [batch][nnzH]: device pointers.  *active
+ * (host, nullable): agents that now hold a direction and are in line search.  SYNCHRONISES `hip_stream`: the host reads
+ * one count per rung of the ladder (the rejected agents alone are solved again, compacted). */
+sfb_status sfb_nlp_sqp_direction(sfb_nlp_sqp *solver, const double *f, const double *df, const double *g, const double *dg_val,
+                                 const double *hess_val, int64_t *active, void *hip_stream);
+/* x_trial [batch][n] (device) = clip(x + alpha d) for agents in line search, x for the rest.  Asynchronous on `hip_stream`. */
+sfb_status sfb_nlp_sqp_trial(sfb_nlp_sqp *solver, double *x_trial, void *hip_stream);
+/* The Armijo test from f_trial [batch], g_trial [batch][m] (device) at x_trial: commit or halve.  *searching (host, nullable):
+ * agents still in line search.  Synchronises `hip_stream` for that count. */
+sfb_status sfb_nlp_sqp_accept(sfb_nlp_sqp *solver, const double *f_trial, const double *g_trial, int64_t *searching,
+                              void *hip_stream);
+/* Device pointers into the state, any may be NULL: x, z [batch][n], lambda [batch][m], the others [batch]. */
+sfb_status sfb_nlp_sqp_state(sfb_nlp_sqp *solver, const double **x, const double **lambda, const double **z, const int32_t **status,
+                             const int32_t **iter, const double **r_stat, const double **r_pri, const double **r_comp,
+                             const double **mu, const double **alpha, const double **nu);
+/* Host-pointer variants of the five entries above (synchronous, null stream): inputs are staged through a device buffer the
+ * first of these calls allocates (per agent 1 + n + m + nnzJ + nnzH doubles, freed with the handle), outputs are copied back.
+ * What a host front for ONE problem -- solve_nlp_sqp of nlp_solver.hpp -- calls with batch 1.  Any output of _state_host may be
+ * NULL. */
+sfb_status sfb_nlp_sqp_set_start_host(sfb_nlp_sqp *solver, const double *x, const double *lambda, const double *z);
+sfb_status sfb_nlp_sqp_direction_host(sfb_nlp_sqp *solver, const double *f, const double *df, const double *g,
+                                      const double *dg_val, const double *hess_val, int64_t *active);
+sfb_status sfb_nlp_sqp_trial_host(sfb_nlp_sqp *solver, double *x_trial);
+sfb_status sfb_nlp_sqp_accept_host(sfb_nlp_sqp *solver, const double *f_trial, const double *g_trial, int64_t *searching);
+sfb_status sfb_nlp_sqp_state_host(sfb_nlp_sqp *solver, double *x, double *lambda, double *z, int32_t *status, int32_t *iter,
+                                  double *r_stat, double *r_pri, double *r_comp, double *mu, double *alpha, double *nu);
+/* For tests (as sfb_mpc_swarm_debug_buffers): the QP arrays of the LAST rung, compacted -- slot k belongs to agent list[k] --
+ * with its results (d, y, code, iter), and sums = [v1 | phi0 | D | d.d | d.P d], each [batch] by agent.  Any may be NULL. */
+sfb_status sfb_nlp_sqp_debug_buffers(sfb_nlp_sqp *solver, const double **Px, const double **q, const double **Ax, const double **l,
+                                     const double **u, const double **d, const double **y, const int32_t **code,
+                                     const uint32_t **iter, const int32_t **list, const double **sums);
+
 /*
  * Synthetic workload of the reference benchmark: random_qp(m, n, density, rng)
  * (benchmarks/bench_types.hpp:19-41) drawn `batch` times from ONE std::default_random_engine

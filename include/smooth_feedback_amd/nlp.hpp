@@ -1,7 +1,9 @@
 // Nonlinear programs as the collocation front hands them to a solver (reference nlp.hpp): the NLP / HessianNLP concepts
 // and NLPSolution, on this repository's types -- vectors are std::vector<double>, first derivatives MeshCsr (CSR, the
 // form QuadraticProgramSparse::A_* has), second derivatives MeshCsc (upper triangle in CSC, as P_*).  No solver lives
-// here; the reference's is external as well.
+// here (the reference's is external as well): a swarm of NLPs sharing these patterns is solved on the GPU by the swarm SQP
+// solver, sfb_nlp_sqp_* of sfb.h (smooth_feedback_amd/nlp.py), which takes exactly these values as device arrays; solve_nlp_sqp of
+// nlp_solver.hpp runs it for one HessianNLP.
 #pragma once
 #include <concepts>
 #include <cstddef>

@@ -28,7 +28,8 @@
 // The Lagrangian Hessian sigma d2f + d2g(lambda) in one pass is d2l_dx2(x, sigma, lambda): the same pattern, its values written by
 // meshfn::ocp_nlp_hess_value entry by entry over the records of meshfn::ocp_nlp_hess_pattern -- the function and the records the
 // kernel behind sfb_ocp_nlp_hess_batch uses.  d2f_dx2 and d2g_dx2 keep their own code.
-// A problem on Lie groups comes here through flatten_ocp (ocp_flatten.hpp).  Left out: any solver.
+// A problem on Lie groups comes here through flatten_ocp (ocp_flatten.hpp).  The solver is apart: the swarm SQP solver sfb_nlp_sqp_*
+// of sfb.h consumes g, dg_dx and the Lagrangian Hessian of a swarm where sfb_ocp_nlp_batch / _hess_batch leave them.
 #pragma once
 #include <algorithm>
 #include <array>

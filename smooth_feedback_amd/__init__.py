@@ -24,6 +24,7 @@ from .mesh import (PHMesh, mesh_dyn_batch, mesh_dyn_batch_device, mesh_dyn_batch
                    mesh_resample_batch_device, mesh_resample_batch_host, ocp_nlp_batch, ocp_nlp_batch_device, ocp_nlp_batch_host,
                    ocp_nlp_bounds, ocp_nlp_hess_batch, ocp_nlp_hess_batch_device, ocp_nlp_hess_batch_host, ocp_nlp_hess_pattern, ocp_nlp_pattern,
                    ocp_nlp_structure)
+from .nlp import NLPSQPParams, NLPSwarmSQP, NLPSwarmSolution, nlp_sqp_qp_pattern  # noqa: F401
 from .mpc import LIE_RN, LIE_SE2, LIE_SE3, LIE_SO3, MPCLayout, MPCSwarm  # noqa: F401
 
 __version__ = "0.1.0"

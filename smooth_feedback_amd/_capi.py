@@ -70,6 +70,13 @@ class SfbOcpDims(C.Structure):
     _fields_ = [("nx", C.c_int32), ("nu", C.c_int32), ("nq", C.c_int32), ("ncr", C.c_int32), ("nce", C.c_int32)]
 
 
+class SfbNlpSqpParams(C.Structure):
+    """sfb_nlp_sqp_params (include/sfb.h)."""
+
+    _fields_ = [("tol", C.c_double), ("max_iter", C.c_int64), ("kappa", C.c_double), ("mu_first", C.c_double),
+                ("mu_grow", C.c_double), ("mu_max", C.c_double), ("qp", SfbQPParams)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -191,6 +198,21 @@ def _load():
     L.sfb_mpc_swarm_step_resident.argtypes = [vp, C.POINTER(SfbQPParams), i32, dp, dp, dp, dp, dp]
     L.sfb_mpc_swarm_step_resident_flat.argtypes = [vp, C.POINTER(SfbQPParams), dp, dp, dp, dp, dp]
     L.sfb_mpc_swarm_debug_buffers.argtypes = [vp] + [C.POINTER(C.c_void_p)] * 3
+    sqp = C.POINTER(SfbNlpSqpParams)
+    L.sfb_nlp_sqp_params_default.argtypes = [sqp]
+    L.sfb_nlp_sqp_params_default.restype = None
+    L.sfb_nlp_sqp_qp_pattern.argtypes = [i32, i32] + [vp] * 18 + [C.POINTER(C.c_int64)]
+    L.sfb_nlp_sqp_create.argtypes = [i32, i32] + [vp] * 8 + [i64, sqp, vp, C.POINTER(C.c_void_p)]
+    L.sfb_nlp_sqp_destroy.argtypes = [vp]
+    L.sfb_nlp_sqp_destroy.restype = None
+    L.sfb_nlp_sqp_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.sfb_nlp_sqp_set_start.argtypes = [vp, dp, dp, dp, vp]
+    L.sfb_nlp_sqp_direction.argtypes = [vp, dp, dp, dp, dp, dp, C.POINTER(C.c_int64), vp]
+    L.sfb_nlp_sqp_trial.argtypes = [vp, dp, vp]
+    L.sfb_nlp_sqp_accept.argtypes = [vp, dp, dp, C.POINTER(C.c_int64), vp]
+    L.sfb_nlp_sqp_state.argtypes = [vp] + [C.POINTER(C.c_void_p)] * 11
+    L.sfb_nlp_sqp_debug_buffers.argtypes = [vp] + [C.POINTER(C.c_void_p)] * 11
     L.sfb_set_devices.argtypes = [C.POINTER(C.c_int), i32]
     L.sfb_get_devices.argtypes = [C.POINTER(C.c_int), i32, C.POINTER(C.c_int)]
     L.sfb_host_staging_trim.restype = None
