@@ -213,6 +213,11 @@ def _load():
     L.sfb_nlp_sqp_accept.argtypes = [vp, dp, dp, C.POINTER(C.c_int64), vp]
     L.sfb_nlp_sqp_state.argtypes = [vp] + [C.POINTER(C.c_void_p)] * 11
     L.sfb_nlp_sqp_debug_buffers.argtypes = [vp] + [C.POINTER(C.c_void_p)] * 11
+    L.sfb_nlp_sqp_set_start_host.argtypes = [vp, dp, dp, dp]
+    L.sfb_nlp_sqp_direction_host.argtypes = [vp, dp, dp, dp, dp, dp, C.POINTER(C.c_int64)]
+    L.sfb_nlp_sqp_trial_host.argtypes = [vp, dp]
+    L.sfb_nlp_sqp_accept_host.argtypes = [vp, dp, dp, C.POINTER(C.c_int64)]
+    L.sfb_nlp_sqp_state_host.argtypes = [vp] + [vp] * 11
     L.sfb_set_devices.argtypes = [C.POINTER(C.c_int), i32]
     L.sfb_get_devices.argtypes = [C.POINTER(C.c_int), i32, C.POINTER(C.c_int)]
     L.sfb_host_staging_trim.restype = None

@@ -228,9 +228,13 @@ __global__ __launch_bounds__(kWave) void nlp_sqp_accept_kernel(const NlpSqpDev p
   const int lane  = threadIdx.x;
   if (b >= batch || p.phase[b] != 1) return;
   const double alpha = p.alpha[b];
-  const double v1t   = violation_l1(p, g_trial + b * p.m, lane);
-  const double phit  = f_trial[b] + p.nu[b] * v1t;
-  if (phit <= p.phi0[b] + 1e-4 * alpha * p.slope[b]) {  // Armijo on the l1 merit: commit
+  const double *gt   = g_trial + b * p.m;
+  bool bad           = false;  // fmax drops a NaN, so violation_l1 would count a row that did not evaluate as satisfied
+  for (int r = lane; r < p.m; r += kWave) bad = bad || !isfinite(gt[r]);
+  const double v1t  = violation_l1(p, gt, lane);
+  const double phit = f_trial[b] + p.nu[b] * v1t;
+  const bool finite = wave_ballot(bad) == 0ull && isfinite(phit);  // a merit that is not finite is a rejection
+  if (finite && phit <= p.phi0[b] + 1e-4 * alpha * p.slope[b]) {  // Armijo on the l1 merit: commit
     for (int j = lane; j < p.n; j += kWave) {
       const int64_t i = b * p.n + j;
       p.x[i]          = clip(p.x[i] + alpha * p.d[i], p.xl[j], p.xu[j]);

@@ -146,6 +146,53 @@ def judge_sums_ref(pb, Px, d):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# law 3: the step, as pure functions of one agent (solve_ref below calls them: there is one statement of the law)
+# ---------------------------------------------------------------------------------------------------------------------
+ARMIJO, HALVINGS = 1e-4, 10
+
+
+def step_start_ref(pb, f, df, g, d, y, nu_prev):
+    """the part of law 3 that does not depend on alpha -> (nu, phi0, D, dfd, absdfd, k): nu the running maximum over the m
+    constraint rows of y (one multiply, one max), phi0 = f + nu v1(g), D = df.d - nu v1(g) in float64; df.d once more in
+    longdouble with the sum of its absolute terms and its term count, for the slack of a wave-reduced sum"""
+    nu = max(nu_prev, 1.1 * float(np.max(np.abs(np.asarray(y)[:pb.m]), initial=0.0)))
+    v = float(v1_ref(pb, g)[0])
+    terms = np.asarray(df, LD) * np.asarray(d, LD)
+    return nu, f + nu * v, float(np.dot(df, d)) - nu * v, terms.sum(dtype=LD), np.abs(terms).sum(dtype=LD), pb.n
+
+
+def trial_ref(pb, x, d, alpha):
+    return np.fmin(np.fmax(x + alpha * d, pb.xl), pb.xu)
+
+
+def accept_ref(pb, state, ft, gt, mu_first=1e-4):
+    """one trial point of a searching agent.  state: x, lam, z, mu, nu, alpha, iter, status and, of the open search, d, y (the
+    accepted QP solution, mq rows), phi0, D, halvings, searching.  -> the new state: committed (Armijo on the l1 merit; a merit
+    that is not finite -- a NaN or infinite ft or entry of gt -- is a rejection), halved, or Unknown after the tenth halving
+    was rejected too, with alpha left at 2^-10 and nothing else touched.  An agent that is not searching is returned as it is."""
+    s = dict(state)
+    if not s["searching"]:
+        return s
+    alpha = s["alpha"]
+    with np.errstate(invalid="ignore", over="ignore"):
+        phit = ft + s["nu"] * float(v1_ref(pb, gt)[0])
+        ok = bool(np.isfinite(phit)) and bool(phit <= s["phi0"] + ARMIJO * alpha * s["D"])
+    if ok:
+        zq = np.zeros(pb.n)
+        zq[pb.pat["bound_var"]] = np.asarray(s["y"])[pb.m:]
+        s["x"] = trial_ref(pb, s["x"], s["d"], alpha)
+        s["lam"] = s["lam"] + alpha * (np.asarray(s["y"])[:pb.m] - s["lam"])
+        s["z"] = s["z"] + alpha * (zq - s["z"])
+        s["mu"] = s["mu"] / 4.0 if s["mu"] > mu_first else 0.0
+        s["iter"], s["searching"] = s["iter"] + 1, False
+    elif s["halvings"] + 1 > HALVINGS:
+        s["status"], s["searching"] = UNKNOWN, False
+    else:
+        s["halvings"], s["alpha"] = s["halvings"] + 1, alpha / 2.0
+    return s
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # the whole law for one agent
 # ---------------------------------------------------------------------------------------------------------------------
 DEFAULTS = dict(tol=1e-6, max_iter=50, kappa=1e-8, mu_first=1e-4, mu_grow=8.0, mu_max=1e4)
@@ -164,9 +211,6 @@ def solve_ref(pb, evaluate, x0, oracle, lam0=None, z0=None, qp=None, history=Non
     mu = nu = alpha = 0.0
     it, status, solves = 0, RUNNING, 0
     wd, wy = np.zeros(n), np.zeros(mq)
-    bv = pb.pat["bound_var"]
-    clip = lambda v: np.fmin(np.fmax(v, pb.xl), pb.xu)                              # noqa: E731
-    v1 = lambda g: float(v1_ref(pb, g)[0])                                          # noqa: E731
     res = (0.0, 0.0, 0.0)
     while True:
         f, g, df, dg, hess = evaluate(x, lam, True)
@@ -205,25 +249,14 @@ def solve_ref(pb, evaluate, x0, oracle, lam0=None, z0=None, qp=None, history=Non
         if status != RUNNING:
             break
         wd, wy = d.copy(), y.copy()
-        nu = max(nu, 1.1 * float(np.max(np.abs(y[:m]), initial=0.0)))               # law 3
-        v = v1(g)
-        phi0, D = f + nu * v, float(np.dot(df, d)) - nu * v
-        alpha, accepted = 1.0, False
-        for _ in range(11):
-            xt = clip(x + alpha * d)
-            ft, gt = evaluate(xt, lam, False)[:2]
-            if ft + nu * v1(gt) <= phi0 + 1e-4 * alpha * D:
-                accepted = True
-                break
-            alpha = alpha / 2.0
-        if not accepted:
-            status = UNKNOWN
+        nu, phi0, D = step_start_ref(pb, f, df, g, d, y, nu)[:3]                    # law 3
+        st = dict(x=x, lam=lam, z=z, mu=mu, nu=nu, alpha=1.0, iter=it, status=RUNNING, d=d, y=y, phi0=phi0, D=D, halvings=0, searching=True)
+        while st["searching"]:
+            ft, gt = evaluate(trial_ref(pb, st["x"], d, st["alpha"]), lam, False)[:2]
+            st = accept_ref(pb, st, ft, gt, prm["mu_first"])
+        x, lam, z, mu, alpha, it, status = [st[k] for k in ("x", "lam", "z", "mu", "alpha", "iter", "status")]
+        if status != RUNNING:
             break
-        zq = np.zeros(n)
-        zq[bv] = y[m:]
-        x, lam, z = xt, lam + alpha * (y[:m] - lam), z + alpha * (zq - z)
-        mu = mu / 4.0 if mu > prm["mu_first"] else 0.0
-        it += 1
     return dict(x=x, lam=lam, z=z, status=status, iter=it, r_stat=res[0], r_pri=res[1], r_comp=res[2], mu=mu, alpha=alpha, nu=nu,
                 qp_solves=solves)
 

@@ -257,6 +257,43 @@ def test_reference_law_solves_hs71_from_every_start(hs71_reference):
     assert all(max(h[4] for h in r["history"]) > 0.1 for r in runs) and all(r["mu"] <= 1e-3 for r in runs)
 
 
+def test_reference_step_rejects_a_trial_point_that_does_not_evaluate():
+    """law 3 as its own functions (step_start_ref, trial_ref, accept_ref): a NaN or +inf f_trial and a NaN entry of g_trial (in a
+    row with two finite sides, and in one with an infinite side) make the merit non-finite, and that is a rejection -- alpha halves
+    and nothing else of the agent changes -- where the same point with finite values is committed; eleven in a row end the agent
+    Unknown with alpha left at 2^-10, as the law words it (at most 10 halvings)."""
+    pb = R.Problem(3, 2, [0, 1, 2], [0, 0], [0, 1, 2, 3], [0, 1, 2], [-1.0, -np.inf, -1.0], [1.0, np.inf, 1.0], [0.0, -np.inf], [1.0, 1.0])
+    rng = np.random.default_rng(3)
+    x, lam, z, d, y = rng.uniform(-0.5, 0.5, 3), rng.normal(size=2), rng.normal(size=3), rng.uniform(-1.0, 1.0, 3), rng.normal(size=4)
+    f, df, g = 0.3, -d, np.array([0.5, 1.5])
+    nu, phi0, D, dfd, absdfd, k = R.step_start_ref(pb, f, df, g, d, y, 0.25)
+    assert nu == max(0.25, 1.1 * np.abs(y[:2]).max()) and phi0 == f + nu * 0.5 and D == float(np.dot(df, d)) - nu * 0.5 < 0.0
+    assert abs(dfd - R.LD(np.dot(df, d))) <= R.slack(k, absdfd) and k == 3
+    st = dict(x=x, lam=lam, z=z, mu=4e-4, nu=nu, alpha=1.0, iter=2, status=R.RUNNING, d=d, y=y, phi0=phi0, D=D, halvings=0, searching=True)
+    good_f, good_g = phi0 + 2e-4 * D, np.array([0.5, 0.5])
+    done = R.accept_ref(pb, st, good_f, good_g)
+    zq = np.array([y[2], 0.0, y[3]])                                                # variable 1 is free: no bound row, zq = 0
+    assert not done["searching"] and done["iter"] == 3 and done["status"] == R.RUNNING and done["mu"] == 1e-4 and done["alpha"] == 1.0
+    assert np.array_equal(done["x"], R.trial_ref(pb, x, d, 1.0)) and np.array_equal(done["lam"], lam + 1.0 * (y[:2] - lam))
+    assert np.array_equal(done["z"], z + 1.0 * (zq - z))
+    assert R.accept_ref(pb, dict(st, mu=1e-4), good_f, good_g)["mu"] == 0.0         # exactly mu_first goes to 0
+    assert all(v is done[key] for key, v in R.accept_ref(pb, done, -1e300, good_g).items())   # not searching: returned as it is
+    for ft, gt in ((np.nan, good_g), (np.inf, good_g), (good_f, np.array([np.nan, 0.5])), (good_f, np.array([0.5, np.nan]))):
+        s = st
+        for h in range(1, 12):
+            t = R.accept_ref(pb, s, ft, gt)
+            for key in ("x", "lam", "z", "mu", "nu", "iter", "d", "y", "phi0", "D"):
+                assert np.array_equal(t[key], s[key]), (ft, gt, h, key)
+            if h <= 10:
+                assert t["searching"] and t["status"] == R.RUNNING and t["halvings"] == h and t["alpha"] == 2.0 ** -h, (ft, gt, h)
+                half = R.accept_ref(pb, t, phi0 + 2e-4 * t["alpha"] * D, good_g)    # a finite point commits from where the search stands
+                assert not half["searching"] and np.array_equal(half["x"], R.trial_ref(pb, x, d, t["alpha"])), (ft, gt, h)
+                assert np.array_equal(half["z"], z + t["alpha"] * (zq - z))
+            else:
+                assert not t["searching"] and t["status"] == R.UNKNOWN and t["alpha"] == 2.0 ** -10, (ft, gt, h)
+            s = t
+
+
 def test_reference_law_is_local(hs71_reference, oracle):
     """the far starts (2, 2, 2, 2), (5, 1, 1, 5), (3, 4, 2, 1.5): the law is local, and no test here asks it to reach f* from them.
     Measured with this restatement: f* from the first and the third (11 and 13 iterations), another stationary point
