@@ -839,22 +839,21 @@ static sfb_status dense_host_phases_impl(const sfb_qp_params *prm, int64_t batch
   QpBatch d{};
   s.add(&dtr, TR, S::Out, trace); s.add(&dph, PH);  // (16 doubles of phase scratch per item, 6 of them come down)
   sfb::stage_qp(s, B, N * N, N, M * N, M, h, d);
-  sfb::DeviceBlock blk;
-  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
-  hipError_t e = s.upload();
-  if (e == hipSuccess && TR) {  // unused rows keep ITER = -1
-    std::vector<double> init(TR, 0.0);
-    for (size_t r = 0; r < TR; r += 5) init[r] = -1.0;
-    e = sfb::upload(dtr, init.data(), TR);
-  }
-  if (e == hipSuccess && PH) e = hipMemset(dph, 0, PH * 8);
-  if (e == hipSuccess) {
-    st = dense_phases_impl(prm, batch, n, m, d, TR ? dtr : nullptr, trace_rows, PH ? dph : nullptr, nullptr);
-    if (st == SFB_OK && (e = hipDeviceSynchronize()) == hipSuccess && (e = s.download()) == hipSuccess && PH)
-      e = sfb::download(phase_us, dph, B * 6);
-  }
-  if (e != hipSuccess) return hip_fail(e, "sfb_qp_dense_solve_batch_host_trace");
-  return st;
+  const char *entry = "sfb_qp_dense_solve_batch_host_trace";
+  return sfb::staged_call(s, entry, [&]() -> sfb_status {
+    hipError_t e = hipSuccess;
+    if (TR) {  // unused rows keep ITER = -1
+      std::vector<double> init(TR, 0.0);
+      for (size_t r = 0; r < TR; r += 5) init[r] = -1.0;
+      e = sfb::upload(dtr, init.data(), TR);
+    }
+    if (e == hipSuccess && PH) e = hipMemset(dph, 0, PH * 8);
+    if (e != hipSuccess) return hip_fail(e, entry);
+    const sfb_status st = dense_phases_impl(prm, batch, n, m, d, TR ? dtr : nullptr, trace_rows, PH ? dph : nullptr, nullptr);
+    if (st != SFB_OK || !PH) return st;
+    if ((e = hipDeviceSynchronize()) == hipSuccess) e = sfb::download(phase_us, dph, B * 6);
+    return e == hipSuccess ? SFB_OK : hip_fail(e, entry);
+  });
 }
 
 sfb_status sfb_qp_dense_solve_batch_host(const sfb_qp_params *prm, int64_t batch, int n, int m, const double *P,

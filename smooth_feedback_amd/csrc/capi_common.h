@@ -37,7 +37,8 @@ sfb_status run_sharded(int64_t batch, const std::function<sfb_status(int device,
 // Staging of a host-pointer entry point: every array is declared once -- device pointer, count, host pointer and
 // direction -- in the order it lies in the device buffer.  bytes() is what the buffer must hold, bind() hands out the
 // device pointers, upload() / download() copy the In / Out arrays whose host pointer is given, in declaration order, up
-// to the first error.  A NULL host pointer still reserves its space.  Where the memory comes from is the caller's business.
+// to the first error.  A NULL host pointer still reserves its space (add) or leaves the array out (add_opt).  Where the
+// memory comes from is the caller's business.
 class Staging {
 public:
   enum Dir { Scratch = 0, In = 1, Out = 2, InOut = 3 };
@@ -46,6 +47,13 @@ public:
   {
     const int i = arena_.add(dev, count);
     if (i >= 0) host_[i] = {const_cast<std::remove_const_t<T> *>(host), dir};
+  }
+  // an array that is absent when the caller gave no host pointer: no bytes, *dev stays NULL and goes to the device entry as such
+  template<class T>
+  void add_opt(T **dev, size_t count, Dir dir, const std::remove_const_t<T> *host)
+  {
+    *dev = nullptr;
+    if (host) add(dev, count, dir, host);
   }
   size_t bytes() const { return arena_.bytes(); }
   bool bind(void *base) { return arena_.bind(base); }
@@ -71,14 +79,33 @@ using smooth_feedback_amd::detail::DeviceArena;
 using smooth_feedback_amd::detail::DeviceBlock;
 using smooth_feedback_amd::detail::download;
 using smooth_feedback_amd::detail::upload;
-// memory for one call: a block of s.bytes(), bound to s and freed with `blk`
-inline sfb_status stage_per_call(Staging &s, DeviceBlock &blk)
+// memory for one call: a block of s.bytes(), bound to s and freed with `blk`; a HIP failure is reported under `who`
+inline sfb_status stage_per_call(Staging &s, DeviceBlock &blk, const char *who)
 {
   blk = DeviceBlock(s.bytes());
-  if (blk.error() != hipSuccess) return hip_fail(blk.error(), "hipMalloc");
+  if (blk.error() != hipSuccess) return hip_fail(blk.error(), who);
   return s.bind(blk.get()) ? SFB_OK : fail(SFB_ERR_UNSUPPORTED, "more staged arrays than the table holds");
 }
-
+// ... with the In arrays in it (also how tables that stay on the device are made: `blk` is then kept)
+inline sfb_status stage_and_upload(Staging &s, DeviceBlock &blk, const char *who)
+{
+  const sfb_status st = stage_per_call(s, blk, who);
+  if (st != SFB_OK) return st;
+  const hipError_t e = s.upload();
+  return e == hipSuccess ? SFB_OK : hip_fail(e, who);
+}
+// The tail of a host-pointer entry: memory for this call, upload, `call` (the device twin on the null stream; its refusal
+// is returned as it is, nothing comes down), wait for the device, download.
+template<class Call>
+sfb_status staged_call(Staging &s, const char *entry, Call &&call)
+{
+  DeviceBlock blk;
+  sfb_status st = stage_and_upload(s, blk, entry);
+  if (st != SFB_OK || (st = call()) != SFB_OK) return st;
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = s.download();
+  return e == hipSuccess ? SFB_OK : hip_fail(e, entry);
+}
 
 // The arrays of a QP batch as every host-pointer entry stages them, after whatever the caller declared before: the seven
 // inputs, then x, y, obj, iter, code.  sizeP / sizeA: values of P / A per item (dense: n * n and m * n; sparse: the

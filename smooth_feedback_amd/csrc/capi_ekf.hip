@@ -84,18 +84,10 @@ sfb_status sfb_ekf_predict_rk4_batch_host(int64_t batch, int dof, const double *
   S s;
   double *dP, *dA, *dAm, *dAe, *dQ, *ddt;
   s.add(&dP, B * nn, S::InOut, P); s.add(&dA, B * nn, S::In, A);
-  s.add(&dAm, A_mid ? B * nn : 0, S::In, A_mid); s.add(&dAe, A_end ? B * nn : 0, S::In, A_end);
+  s.add_opt(&dAm, B * nn, S::In, A_mid); s.add_opt(&dAe, B * nn, S::In, A_end);
   s.add(&dQ, nQ, S::In, Q); s.add(&ddt, nT, S::In, dt);
-  sfb::DeviceBlock blk;
-  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
-  hipError_t e = s.upload();
-  if (e == hipSuccess) {
-    st = sfb_ekf_predict_rk4_batch(batch, dof, dA, A_mid ? dAm : nullptr, A_end ? dAe : nullptr, dQ, q_shared, ddt,
-                                   dt_shared, dP, nullptr);
-    if (st == SFB_OK && (e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
-  }
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_ekf_predict_rk4_batch_host");
-  return st;
+  return sfb::staged_call(s, "sfb_ekf_predict_rk4_batch_host",
+                          [&] { return sfb_ekf_predict_rk4_batch(batch, dof, dA, dAm, dAe, dQ, q_shared, ddt, dt_shared, dP, nullptr); });
 }
 
 sfb_status sfb_ekf_predict_stepper_batch_host(int stepper, int64_t batch, int dof, const double *A, const double *Q,
@@ -137,26 +129,18 @@ sfb_status sfb_ekf_step_batch_host(int64_t batch, int dof, int ny, const double 
   if (batch == 0) return SFB_OK;
   const size_t B = (size_t)batch, nn = (size_t)dof * dof, mn = (size_t)ny * dof, mm = (size_t)ny * ny;
   using S = sfb::Staging;
-  S s;  // (the arrays of a half that is not asked for take no space)
+  S s;  // (the arrays of a half that is not asked for take no space; ekf_common refuses what the caller left out of the other)
   double *dP, *dA, *dQ, *ddt, *dH, *dR, *dr, *ddelta;
   int32_t *dinfo;
   s.add(&dP, B * nn, S::InOut, P);
-  s.add(&dA, predict ? B * nn : 0, S::In, A); s.add(&dQ, predict ? (q_shared ? nn : B * nn) : 0, S::In, Q);
-  s.add(&ddt, predict ? (dt_shared ? 1 : B) : 0, S::In, dt);
-  s.add(&dH, update ? B * mn : 0, S::In, H); s.add(&dR, update ? (r_shared ? mm : B * mm) : 0, S::In, R);
-  s.add(&dr, update ? B * ny : 0, S::In, r); s.add(&ddelta, update ? B * dof : 0, S::Out, delta);
-  s.add(&dinfo, update && info ? B : 0, S::Out, info);
-  sfb::DeviceBlock blk;
-  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
-  auto given = [](const void *h, auto *d) { return h ? d : nullptr; };  // ekf_common refuses what the caller left out
-  hipError_t e = s.upload();
-  if (e == hipSuccess) {
-    st = ekf_common(batch, dof, ny, given(A, dA), given(Q, dQ), q_shared, given(dt, ddt), dt_shared, given(H, dH), given(R, dR), r_shared,
-                    given(r, dr), dP, given(delta, ddelta), given(info, dinfo), predict, update, nullptr);
-    if (st == SFB_OK && (e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
-  }
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_ekf_step_batch_host");
-  return st;
+  s.add_opt(&dA, predict ? B * nn : 0, S::In, A); s.add_opt(&dQ, predict ? (q_shared ? nn : B * nn) : 0, S::In, Q);
+  s.add_opt(&ddt, predict ? (dt_shared ? 1 : B) : 0, S::In, dt);
+  s.add_opt(&dH, update ? B * mn : 0, S::In, H); s.add_opt(&dR, update ? (r_shared ? mm : B * mm) : 0, S::In, R);
+  s.add_opt(&dr, update ? B * ny : 0, S::In, r); s.add_opt(&ddelta, update ? B * dof : 0, S::Out, delta);
+  s.add_opt(&dinfo, update ? B : 0, S::Out, info);
+  return sfb::staged_call(s, "sfb_ekf_step_batch_host", [&] {
+    return ekf_common(batch, dof, ny, dA, dQ, q_shared, ddt, dt_shared, dH, dR, r_shared, dr, dP, ddelta, dinfo, predict, update, nullptr);
+  });
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -67,40 +68,35 @@ sfb_status dyn_error_check(const sfb_mesh *mesh, int64_t batch, int32_t nx, cons
 // The per-degree tables (once per device) and the interval lists of the meshes seen (per device and mesh content) live
 // on the device, so that an asynchronous launch never outlives what it reads.  A list is a few dozen bytes per
 // interval; when a device holds kMeshesKept distinct meshes its lists are dropped after a synchronise of that device.
-// The cache's lock is held from the lookup to the end of the launch call (with_device_mesh), so a thread that evicts
+// The cache's lock is held from the lookup to the end of the launch call (with_cached), so a thread that evicts
 // never frees a list between another thread's lookup and its launch; what has been launched is covered by the synchronise.
 constexpr size_t kMeshesKept = 64;
+using MeshDims = std::array<int32_t, 5>;  // none for the interval lists, (nx, nu) for the mesh functions, the OCP's five for the NLP
 struct MeshKey {
   int device;
   std::vector<int32_t> K;
   std::vector<uint64_t> tau0;  // bit patterns
-  bool operator<(const MeshKey &o) const { return std::tie(device, K, tau0) < std::tie(o.device, o.K, o.tau0); }
+  MeshDims dims;
+  bool operator<(const MeshKey &o) const { return std::tie(device, dims, K, tau0) < std::tie(o.device, o.dims, o.K, o.tau0); }
 };
+MeshKey mesh_key(int device, const sfb_mesh *mesh, const MeshDims &dims)
+{
+  MeshKey key{device, std::vector<int32_t>(mesh->K, mesh->K + mesh->nivals), std::vector<uint64_t>(mesh->nivals), dims};
+  std::memcpy(key.tau0.data(), mesh->tau0, sizeof(double) * mesh->nivals);
+  return key;
+}
 struct MeshEntry {
   sfb::DeviceBlock blk;
   sfb::MeshDevice dev;
 };
 // what the mesh-function kernels read, per (mesh, nx, nu): nodes, weights, differentiation matrices and mesh_dyn's
 // entry -> row table; kept and dropped by the same rule as the interval lists
-struct MeshFnKey {
-  MeshKey mesh;
-  int32_t nx, nu;
-  bool operator<(const MeshFnKey &o) const { return std::tie(nx, nu, mesh) < std::tie(o.nx, o.nu, o.mesh); }
-};
 struct MeshFnEntry {
   sfb::DeviceBlock blk;
   sfb::MeshFnDevice dev;
 };
 // what the fused NLP kernel reads, per (mesh, dims): the node table, the differentiation matrices and one decode record
 // per output double; kept and dropped by the same rule
-struct OcpNlpKey {
-  MeshKey mesh;
-  int32_t d[5];
-  bool operator<(const OcpNlpKey &o) const
-  {
-    return std::lexicographical_compare(d, d + 5, o.d, o.d + 5) || (std::equal(d, d + 5, o.d) && mesh < o.mesh);
-  }
-};
 struct OcpNlpEntry {
   sfb::DeviceBlock blk;
   L::meshfn::OcpNlpTables dev;
@@ -113,13 +109,42 @@ struct MeshCache {
   std::mutex mu;
   std::map<int, sfb::DeviceBlock> tables;
   std::map<MeshKey, MeshEntry> meshes;
-  std::map<MeshFnKey, MeshFnEntry> fns;
-  std::map<OcpNlpKey, OcpNlpEntry> nlps;
+  std::map<MeshKey, MeshFnEntry> fns;
+  std::map<MeshKey, OcpNlpEntry> nlps;
 };
 MeshCache &cache()
 {
   static MeshCache *c = new MeshCache;  // never destroyed: device memory is not freed behind the runtime's back at exit
   return *c;
+}
+
+// launch(entry) with the entry of (current device, mesh, dims) in one of the cache's maps, under the cache's lock.  An
+// entry that is not there is made by build(entry); when its device already holds kMeshesKept of them, they are dropped
+// first, after a synchronise of that device.
+template<class Entry, class Build, class Launch>
+sfb_status with_cached(std::map<MeshKey, Entry> MeshCache::*which, const sfb_mesh *mesh, const MeshDims &dims, Build &&build, Launch &&launch)
+{
+  int device = 0;
+  hipError_t e = hipGetDevice(&device);
+  if (e != hipSuccess) return sfb::hip_fail(e, "hipGetDevice");
+  MeshCache &c = cache();
+  std::lock_guard<std::mutex> lock(c.mu);
+  std::map<MeshKey, Entry> &map = c.*which;
+  MeshKey key = mesh_key(device, mesh, dims);
+  auto it = map.find(key);
+  if (it == map.end()) {
+    size_t here = 0;
+    for (const auto &m : map) here += m.first.device == device ? 1 : 0;
+    if (here >= kMeshesKept) {
+      if ((e = hipDeviceSynchronize()) != hipSuccess) return sfb::hip_fail(e, "hipDeviceSynchronize");
+      for (auto m = map.begin(); m != map.end();) m = m->first.device == device ? map.erase(m) : std::next(m);
+    }
+    Entry ent;
+    const sfb_status st = build(ent);
+    if (st != SFB_OK) return st;
+    it = map.emplace(std::move(key), std::move(ent)).first;
+  }
+  return launch(it->second);
 }
 
 std::vector<double> build_tables()
@@ -140,34 +165,30 @@ std::vector<double> build_tables()
   return t;
 }
 
-// launch(m) with the device copy of `mesh`, under the cache's lock
-template<class Launch>
-sfb_status with_device_mesh(const sfb_mesh *mesh, Launch &&launch)
+// the per-degree tables of the current device, made at its first call; under the cache's lock
+sfb_status device_tables(const double **out)
 {
-  sfb::MeshDevice out{};
   int device = 0;
   hipError_t e = hipGetDevice(&device);
   if (e != hipSuccess) return sfb::hip_fail(e, "hipGetDevice");
-  MeshCache &c = cache();
-  std::lock_guard<std::mutex> lock(c.mu);
-  auto tb = c.tables.find(device);
-  if (tb == c.tables.end()) {
+  std::map<int, sfb::DeviceBlock> &tables = cache().tables;
+  auto tb = tables.find(device);
+  if (tb == tables.end()) {
     const std::vector<double> t = build_tables();
     sfb::DeviceBlock blk(t.size() * sizeof(double));
     if (blk.error() != hipSuccess) return sfb::hip_fail(blk.error(), "hipMalloc");
     if ((e = sfb::upload(static_cast<double *>(blk.get()), t.data(), t.size())) != hipSuccess) return sfb::hip_fail(e, "mesh tables upload");
-    tb = c.tables.emplace(device, std::move(blk)).first;
+    tb = tables.emplace(device, std::move(blk)).first;
   }
-  MeshKey key{device, std::vector<int32_t>(mesh->K, mesh->K + mesh->nivals), std::vector<uint64_t>(mesh->nivals)};
-  std::memcpy(key.tau0.data(), mesh->tau0, sizeof(double) * mesh->nivals);
-  auto it = c.meshes.find(key);
-  if (it == c.meshes.end()) {
-    size_t here = 0;
-    for (const auto &m : c.meshes) here += m.first.device == device ? 1 : 0;
-    if (here >= kMeshesKept) {
-      if ((e = hipDeviceSynchronize()) != hipSuccess) return sfb::hip_fail(e, "hipDeviceSynchronize");
-      for (auto m = c.meshes.begin(); m != c.meshes.end();) m = m->first.device == device ? c.meshes.erase(m) : std::next(m);
-    }
+  *out = static_cast<const double *>(tb->second.get());
+  return SFB_OK;
+}
+
+// launch(m) with the device copy of `mesh`, under the cache's lock
+template<class Launch>
+sfb_status with_device_mesh(const sfb_mesh *mesh, Launch &&launch)
+{
+  const auto build = [&](MeshEntry &ent) {
     const int32_t n = mesh->nivals;
     std::vector<sfb::MeshIval> iv(n);
     std::vector<int32_t> rows;
@@ -180,57 +201,55 @@ sfb_status with_device_mesh(const sfb_mesh *mesh, Launch &&launch)
       rows.insert(rows.end(), mesh->K[s] + 2, s);
     }
     sfb::Staging st;
-    sfb::MeshIval *div;
-    int32_t *drow;
-    st.add(&div, (size_t)n, sfb::Staging::In, iv.data());
-    st.add(&drow, rows.size(), sfb::Staging::In, rows.data());
-    MeshEntry ent;
-    const sfb_status rc = sfb::stage_per_call(st, ent.blk);
-    if (rc != SFB_OK) return rc;
-    if ((e = st.upload()) != hipSuccess) return sfb::hip_fail(e, "mesh upload");
-    ent.dev = sfb::MeshDevice{n, N, R, div, drow, nullptr};
-    it      = c.meshes.emplace(std::move(key), std::move(ent)).first;
+    ent.dev = sfb::MeshDevice{n, N, R, nullptr, nullptr, nullptr};
+    st.add(&ent.dev.ivals, (size_t)n, sfb::Staging::In, iv.data());
+    st.add(&ent.dev.row_ival, rows.size(), sfb::Staging::In, rows.data());
+    return sfb::stage_and_upload(st, ent.blk, "mesh upload");
+  };
+  return with_cached(&MeshCache::meshes, mesh, MeshDims{}, build, [&](const MeshEntry &ent) {
+    sfb::MeshDevice out = ent.dev;
+    const sfb_status st = device_tables(&out.tables);
+    return st != SFB_OK ? st : launch(out);
+  });
+}
+
+// per node its time and weight, per interval 2 / (tauf - tau0), and the intervals' differentiation matrices one after the
+// other: the expressions of Mesh::interval_nodes / interval_weights / interval_diffmat_unscaled
+struct MeshHostTables {
+  std::vector<double> tau, w, scale, D;
+};
+MeshHostTables mesh_host_tables(const sfb_mesh *mesh)
+{
+  MeshHostTables t;
+  const int32_t n = mesh->nivals;
+  for (int32_t s = 0; s < n; ++s) {
+    const L::detail::LgrTable &T = L::detail::lgr_table(mesh->K[s]);
+    const double tau0 = mesh->tau0[s], tauf = s + 1 < n ? mesh->tau0[s + 1] : 1.0, al = (tauf - tau0) / 2;
+    t.scale.push_back(2. / (tauf - tau0));
+    for (int32_t j = 0; j < mesh->K[s]; ++j) {
+      t.tau.push_back(tau0 + al * (T.tau[j] + 1));
+      t.w.push_back(al * T.w[j]);
+    }
+    t.D.insert(t.D.end(), T.Dus.a.begin(), T.Dus.a.end());
   }
-  out        = it->second.dev;
-  out.tables = static_cast<const double *>(tb->second.get());
-  return launch(out);
+  return t;
 }
 
 // launch(m) with the device tables of (mesh, nx, nu), under the cache's lock
 template<class Launch>
 sfb_status with_device_meshfn(const sfb_mesh *mesh, int32_t nx, int32_t nu, Launch &&launch)
 {
-  int device = 0;
-  hipError_t e = hipGetDevice(&device);
-  if (e != hipSuccess) return sfb::hip_fail(e, "hipGetDevice");
-  MeshCache &c = cache();
-  std::lock_guard<std::mutex> lock(c.mu);
-  MeshFnKey key{MeshKey{device, std::vector<int32_t>(mesh->K, mesh->K + mesh->nivals), std::vector<uint64_t>(mesh->nivals)}, nx, nu};
-  std::memcpy(key.mesh.tau0.data(), mesh->tau0, sizeof(double) * mesh->nivals);
-  auto it = c.fns.find(key);
-  if (it == c.fns.end()) {
-    size_t here = 0;
-    for (const auto &m : c.fns) here += m.first.mesh.device == device ? 1 : 0;
-    if (here >= kMeshesKept) {
-      if ((e = hipDeviceSynchronize()) != hipSuccess) return sfb::hip_fail(e, "hipDeviceSynchronize");
-      for (auto m = c.fns.begin(); m != c.fns.end();) m = m->first.mesh.device == device ? c.fns.erase(m) : std::next(m);
-    }
+  const auto build = [&](MeshFnEntry &ent) {
     const int32_t n = mesh->nivals;
+    const MeshHostTables t = mesh_host_tables(mesh);
     std::vector<sfb::MeshFnIval> iv(n);
     std::vector<int32_t> node_ival;
-    std::vector<double> tau, w, D;
-    int32_t N = 0;
-    for (int32_t s = 0; s < n; ++s) {  // the expressions of Mesh::interval_nodes / interval_weights / interval_diffmat_unscaled
-      const L::detail::LgrTable &T = L::detail::lgr_table(mesh->K[s]);
-      const double tau0 = mesh->tau0[s], tauf = s + 1 < n ? mesh->tau0[s + 1] : 1.0, al = (tauf - tau0) / 2;
-      iv[s] = sfb::MeshFnIval{mesh->K[s], N, (int32_t)D.size(), 0, 2. / (tauf - tau0)};
-      for (int32_t j = 0; j < mesh->K[s]; ++j) {
-        tau.push_back(tau0 + al * (T.tau[j] + 1));
-        w.push_back(al * T.w[j]);
-        node_ival.push_back(s);
-      }
-      D.insert(D.end(), T.Dus.a.begin(), T.Dus.a.end());
+    int32_t N = 0, at = 0;
+    for (int32_t s = 0; s < n; ++s) {
+      iv[s] = sfb::MeshFnIval{mesh->K[s], N, at, 0, t.scale[s]};
+      node_ival.insert(node_ival.end(), mesh->K[s], s);
       N += mesh->K[s];
+      at += (int32_t)L::detail::lgr_table(mesh->K[s]).Dus.a.size();
     }
     const int64_t nnz = L::meshfn::dyn_pattern(n, mesh->K, nx, nu, nullptr, nullptr);
     std::vector<int32_t> rowptr((size_t)N * nx + 1, 0), colind((size_t)nnz), entry_row((size_t)nnz);
@@ -238,47 +257,36 @@ sfb_status with_device_meshfn(const sfb_mesh *mesh, int32_t nx, int32_t nu, Laun
     for (int32_t r = 0; r < N * nx; ++r)
       for (int32_t q = rowptr[r]; q < rowptr[r + 1]; ++q) entry_row[q] = r;
     sfb::Staging st;
-    sfb::MeshFnIval *div;
-    int32_t *dni, *drp, *der;
-    double *dtau, *dw, *dD;
-    st.add(&div, (size_t)n, sfb::Staging::In, iv.data());
-    st.add(&dtau, tau.size(), sfb::Staging::In, tau.data());
-    st.add(&dw, w.size(), sfb::Staging::In, w.data());
-    st.add(&dD, D.size(), sfb::Staging::In, D.data());
-    st.add(&dni, node_ival.size(), sfb::Staging::In, node_ival.data());
-    st.add(&drp, rowptr.size(), sfb::Staging::In, rowptr.data());
-    st.add(&der, entry_row.size(), sfb::Staging::In, entry_row.data());
-    MeshFnEntry ent;
-    const sfb_status rc = sfb::stage_per_call(st, ent.blk);
-    if (rc != SFB_OK) return rc;
-    if ((e = st.upload()) != hipSuccess) return sfb::hip_fail(e, "mesh function tables upload");
-    ent.dev = sfb::MeshFnDevice{n, N, nx, nu, nnz, div, dni, dtau, dw, dD, drp, der};
-    it      = c.fns.emplace(std::move(key), std::move(ent)).first;
-  }
-  return launch(it->second.dev);
+    sfb::MeshFnDevice &d = ent.dev;
+    d.nivals = n; d.N = N; d.nx = nx; d.nu = nu; d.dyn_nnz = nnz;
+    st.add(&d.ivals, (size_t)n, sfb::Staging::In, iv.data());
+    st.add(&d.tau, t.tau.size(), sfb::Staging::In, t.tau.data());
+    st.add(&d.w, t.w.size(), sfb::Staging::In, t.w.data());
+    st.add(&d.D, t.D.size(), sfb::Staging::In, t.D.data());
+    st.add(&d.node_ival, node_ival.size(), sfb::Staging::In, node_ival.data());
+    st.add(&d.dyn_rowptr, rowptr.size(), sfb::Staging::In, rowptr.data());
+    st.add(&d.dyn_entry_row, entry_row.size(), sfb::Staging::In, entry_row.data());
+    return sfb::stage_and_upload(st, ent.blk, "mesh function tables upload");
+  };
+  return with_cached(&MeshCache::fns, mesh, MeshDims{nx, nu}, build, [&](const MeshFnEntry &ent) { return launch(ent.dev); });
 }
 
-// nodes, weights, interval constants and differentiation matrices of a mesh as the NLP law reads them (the expressions
-// of Mesh::interval_nodes / interval_weights / interval_diffmat_unscaled); returns ws
+// the node table and the differentiation matrices of a mesh as the NLP law reads them; returns ws
 double ocp_nlp_host_tables(const sfb_mesh *mesh, std::vector<L::meshfn::OcpNlpNode> &nodes, std::vector<double> &D)
 {
-  const int32_t n = mesh->nivals;
+  MeshHostTables t = mesh_host_tables(mesh);
   int32_t N = 0;
+  for (int32_t s = 0; s < mesh->nivals; N += mesh->K[s++])
+    for (int32_t j = 0; j < mesh->K[s]; ++j) nodes.push_back(L::meshfn::OcpNlpNode{t.tau[N + j], t.w[N + j], t.scale[s], mesh->K[s], N});
+  D = std::move(t.D);
   double wmax = 0.0;
-  for (int32_t s = 0; s < n; ++s) {
-    const L::detail::LgrTable &T = L::detail::lgr_table(mesh->K[s]);
-    const double tau0 = mesh->tau0[s], tauf = s + 1 < n ? mesh->tau0[s + 1] : 1.0, al = (tauf - tau0) / 2;
-    for (int32_t j = 0; j < mesh->K[s]; ++j) {
-      nodes.push_back(L::meshfn::OcpNlpNode{tau0 + al * (T.tau[j] + 1), al * T.w[j], 2. / (tauf - tau0), mesh->K[s], N});
-      wmax = std::max(wmax, nodes.back().w);
-    }
-    D.insert(D.end(), T.Dus.a.begin(), T.Dus.a.end());
-    N += mesh->K[s];
-  }
+  for (const double w : t.w) wmax = std::max(wmax, w);
   return L::meshfn::ocp_nlp_w_scaling(wmax);
 }
 
 L::meshfn::OcpDims to_dims(const sfb_ocp_dims *d) { return L::meshfn::OcpDims{d->nx, d->nu, d->nq, d->ncr, d->nce}; }
+// for Staging::add_opt: the arrays of an empty segment are left out, given or not
+const double *unless_empty(size_t width, const double *a) { return width ? a : nullptr; }
 
 // what every sfb_ocp_nlp_* entry refuses first: the mesh, the batch, the dims, sizes beyond 32-bit indices
 sfb_status ocp_dims_check(const sfb_mesh *mesh, int64_t batch, const sfb_ocp_dims *d)
@@ -319,61 +327,37 @@ template<class Launch>
 sfb_status with_device_ocpnlp_entry(const sfb_mesh *mesh, const sfb_ocp_dims *d, bool hess, Launch &&launch)
 {
   namespace MF = L::meshfn;
-  int device = 0;
-  hipError_t e = hipGetDevice(&device);
-  if (e != hipSuccess) return sfb::hip_fail(e, "hipGetDevice");
-  MeshCache &c = cache();
-  std::lock_guard<std::mutex> lock(c.mu);
-  OcpNlpKey key{MeshKey{device, std::vector<int32_t>(mesh->K, mesh->K + mesh->nivals), std::vector<uint64_t>(mesh->nivals)},
-                {d->nx, d->nu, d->nq, d->ncr, d->nce}};
-  std::memcpy(key.mesh.tau0.data(), mesh->tau0, sizeof(double) * mesh->nivals);
-  auto it = c.nlps.find(key);
-  if (it == c.nlps.end()) {
-    size_t here = 0;
-    for (const auto &m : c.nlps) here += m.first.mesh.device == device ? 1 : 0;
-    if (here >= kMeshesKept) {
-      if ((e = hipDeviceSynchronize()) != hipSuccess) return sfb::hip_fail(e, "hipDeviceSynchronize");
-      for (auto m = c.nlps.begin(); m != c.nlps.end();) m = m->first.mesh.device == device ? c.nlps.erase(m) : std::next(m);
-    }
+  const MF::OcpDims dm = to_dims(d);
+  const auto build = [&](OcpNlpEntry &ent) {
     std::vector<MF::OcpNlpNode> nodes;
     std::vector<double> D;
-    const double ws    = ocp_nlp_host_tables(mesh, nodes, D);
-    const MF::OcpDims dm = to_dims(d);
+    const double ws = ocp_nlp_host_tables(mesh, nodes, D);
     int64_t vb[5], cb[5];
     MF::ocp_nlp_structure((int64_t)nodes.size(), dm, vb, cb);
     const int64_t nnz = MF::ocp_nlp_pattern(mesh->nivals, mesh->K, dm, nullptr, nullptr, nullptr);
     std::vector<MF::OcpNlpItem> items((size_t)(cb[4] + nnz));
     MF::ocp_nlp_pattern(mesh->nivals, mesh->K, dm, nullptr, nullptr, items.data());
     sfb::Staging st;
-    MF::OcpNlpNode *dn;
-    double *dD;
-    MF::OcpNlpItem *di;
-    st.add(&dn, nodes.size(), sfb::Staging::In, nodes.data());
-    st.add(&dD, D.size(), sfb::Staging::In, D.data());
-    st.add(&di, items.size(), sfb::Staging::In, items.data());
-    OcpNlpEntry ent;
-    const sfb_status rc = sfb::stage_per_call(st, ent.blk);
-    if (rc != SFB_OK) return rc;
-    if ((e = st.upload()) != hipSuccess) return sfb::hip_fail(e, "ocp nlp tables upload");
-    ent.dev = MF::OcpNlpTables{dm, (int32_t)nodes.size(), cb[4], nnz, ws, dn, dD, di};
-    it      = c.nlps.emplace(std::move(key), std::move(ent)).first;
-  }
-  OcpNlpEntry &ent = it->second;
-  if (hess && !ent.has_hess) {
-    const MF::OcpDims dm = to_dims(d);
-    const int64_t nnzh   = MF::ocp_nlp_hess_pattern(mesh->nivals, mesh->K, dm, nullptr, nullptr, nullptr);
-    std::vector<MF::OcpNlpHessItem> items((size_t)nnzh);
-    MF::ocp_nlp_hess_pattern(mesh->nivals, mesh->K, dm, nullptr, nullptr, items.data());
-    sfb::Staging st;
-    MF::OcpNlpHessItem *di;
-    st.add(&di, items.size(), sfb::Staging::In, items.data());
-    const sfb_status rc = sfb::stage_per_call(st, ent.hblk);
-    if (rc != SFB_OK) return rc;
-    if ((e = st.upload()) != hipSuccess) return sfb::hip_fail(e, "ocp nlp hessian records upload");
-    ent.hdev     = MF::OcpNlpHessTables{dm, ent.dev.N, ent.dev.m, nnzh, ent.dev.ws, ent.dev.nodes, di};
-    ent.has_hess = true;
-  }
-  return launch(ent);
+    ent.dev = MF::OcpNlpTables{dm, (int32_t)nodes.size(), cb[4], nnz, ws, nullptr, nullptr, nullptr};
+    st.add(&ent.dev.nodes, nodes.size(), sfb::Staging::In, nodes.data());
+    st.add(&ent.dev.D, D.size(), sfb::Staging::In, D.data());
+    st.add(&ent.dev.items, items.size(), sfb::Staging::In, items.data());
+    return sfb::stage_and_upload(st, ent.blk, "ocp nlp tables upload");
+  };
+  return with_cached(&MeshCache::nlps, mesh, MeshDims{d->nx, d->nu, d->nq, d->ncr, d->nce}, build, [&](OcpNlpEntry &ent) {
+    if (hess && !ent.has_hess) {
+      const int64_t nnzh = MF::ocp_nlp_hess_pattern(mesh->nivals, mesh->K, dm, nullptr, nullptr, nullptr);
+      std::vector<MF::OcpNlpHessItem> items((size_t)nnzh);
+      MF::ocp_nlp_hess_pattern(mesh->nivals, mesh->K, dm, nullptr, nullptr, items.data());
+      sfb::Staging st;
+      ent.hdev = MF::OcpNlpHessTables{dm, ent.dev.N, ent.dev.m, nnzh, ent.dev.ws, ent.dev.nodes, nullptr};
+      st.add(&ent.hdev.items, items.size(), sfb::Staging::In, items.data());
+      const sfb_status rc = sfb::stage_and_upload(st, ent.hblk, "ocp nlp hessian records upload");
+      if (rc != SFB_OK) return rc;
+      ent.has_hess = true;
+    }
+    return launch(ent);
+  });
 }
 template<class Launch>
 sfb_status with_device_ocpnlp(const sfb_mesh *mesh, const sfb_ocp_dims *d, Launch &&launch)
@@ -399,10 +383,10 @@ sfb_status ocp_nlp_hess_check(const sfb_mesh *mesh, const sfb_ocp_dims *d, int64
   return SFB_OK;
 }
 
-// what the three mesh-function entries refuse, in this order: the mesh, the batch, negative sizes, an index range the
-// 32-bit patterns cannot hold, a derivative input without its output (or the reverse), a NULL array with work to do
-sfb_status meshfn_check(const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, int32_t nf, const double *t0, const double *tf, bool needs_X,
-                        const double *X, const double *F, const double *dF, double *out_F, double *out_dF)
+// What the three mesh-function entries refuse, in this order: the mesh, the batch, negative sizes, an index range the
+// 32-bit patterns cannot hold (meshfn_sizes_check, shared with their pattern entries; dense_rows: integrate's nf rows over
+// all the variables count as well), a derivative input without its output (or the reverse), a NULL array with work to do
+sfb_status meshfn_sizes_check(const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, int32_t nf, bool dense_rows)
 {
   const sfb_status st = mesh_check(mesh, batch);
   if (st != SFB_OK) return st;
@@ -410,26 +394,39 @@ sfb_status meshfn_check(const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t
   if (nu < 0) return sfb::fail(SFB_ERR_INVALID_ARG, "nu < 0");
   if (nf < 0) return sfb::fail(SFB_ERR_INVALID_ARG, "nf < 0");
   const int64_t N = mesh_nodes(mesh), nv = 2 + (int64_t)nx * (N + 1) + (int64_t)nu * N;
-  if (nv > 0x7fffffff || N * nf * (2 + (int64_t)sfb::kMeshMaxK + nx + nu) > 0x7fffffff || (int64_t)nf * (nv + 1) > 0x7fffffff)
+  if (nv > 0x7fffffff || N * nf * (2 + (int64_t)sfb::kMeshMaxK + nx + nu) > 0x7fffffff || (dense_rows && (int64_t)nf * (nv + 1) > 0x7fffffff))
     return sfb::fail(SFB_ERR_INVALID_ARG, "mesh function: more variables or entries than 32-bit indices hold");
+  return SFB_OK;
+}
+
+sfb_status meshfn_check(const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, int32_t nf, const double *t0, const double *tf, bool needs_X,
+                        const double *X, const double *F, const double *dF, double *out_F, double *out_dF)
+{
+  const sfb_status st = meshfn_sizes_check(mesh, batch, nx, nu, nf, true);
+  if (st != SFB_OK) return st;
   if ((dF == nullptr) != (out_dF == nullptr)) return sfb::fail(SFB_ERR_INVALID_ARG, "dF and the derivative output: both or neither");
   if (batch > 0 && nf > 0 && (!t0 || !tf || !F || !out_F || (needs_X && !X))) return sfb::fail(SFB_ERR_INVALID_ARG, "NULL array");
   return SFB_OK;
 }
 
+// The tail of every pattern entry, behind its own size checks: `both` when one index array is given without the other,
+// nothing to write at all; then the count, which is what the entry returns with
+sfb_status pattern_out_check(const int32_t *ptr, const int32_t *ind, const int64_t *nnz, const char *both)
+{
+  if ((ptr == nullptr) != (ind == nullptr)) return sfb::fail(SFB_ERR_INVALID_ARG, both);
+  if (!ptr && !nnz) return sfb::fail(SFB_ERR_INVALID_ARG, "NULL array");
+  return SFB_OK;
+}
+sfb_status pattern_done(int64_t *nnz, int64_t n)
+{
+  if (nnz) *nnz = n;
+  return SFB_OK;
+}
+
 sfb_status pattern_check(const sfb_mesh *mesh, int32_t nx, int32_t nu, int32_t nf, int32_t *rowptr, int32_t *colind, int64_t *nnz)
 {
-  const sfb_status st = mesh_check(mesh, 0);
-  if (st != SFB_OK) return st;
-  if (nx < 0) return sfb::fail(SFB_ERR_INVALID_ARG, "nx < 0");
-  if (nu < 0) return sfb::fail(SFB_ERR_INVALID_ARG, "nu < 0");
-  if (nf < 0) return sfb::fail(SFB_ERR_INVALID_ARG, "nf < 0");
-  const int64_t N = mesh_nodes(mesh), nv = 2 + (int64_t)nx * (N + 1) + (int64_t)nu * N;
-  if (nv > 0x7fffffff || N * nf * (2 + (int64_t)sfb::kMeshMaxK + nx + nu) > 0x7fffffff)
-    return sfb::fail(SFB_ERR_INVALID_ARG, "mesh function: more variables or entries than 32-bit indices hold");
-  if ((rowptr == nullptr) != (colind == nullptr)) return sfb::fail(SFB_ERR_INVALID_ARG, "rowptr and colind: both or neither");
-  if (!rowptr && !nnz) return sfb::fail(SFB_ERR_INVALID_ARG, "NULL array");
-  return SFB_OK;
+  const sfb_status st = meshfn_sizes_check(mesh, 0, nx, nu, nf, false);
+  return st != SFB_OK ? st : pattern_out_check(rowptr, colind, nnz, "rowptr and colind: both or neither");
 }
 
 enum MeshFn { kEval, kIntegrate, kDyn };
@@ -466,22 +463,15 @@ sfb_status meshfn_host(MeshFn fn, const sfb_mesh *mesh, int64_t batch, int32_t n
                                          : (size_t)L::meshfn::dyn_pattern(mesh->nivals, mesh->K, nx, nu, nullptr, nullptr);
   using S = sfb::Staging;
   S s;
-  double *d0, *d1, *dX = nullptr, *dFv, *ddF = nullptr, *doF, *dodF = nullptr;
+  double *d0, *d1, *dX, *dFv, *ddF, *doF, *dodF;
   s.add(&d0, B, S::In, t0); s.add(&d1, B, S::In, tf);
-  if (fn == kDyn) s.add(&dX, B * (N + 1) * (size_t)nx, S::In, X);
+  s.add_opt(&dX, B * (N + 1) * (size_t)nx, S::In, X);  // (mesh_dyn alone is given one)
   s.add(&dFv, B * N * (size_t)nf, S::In, F);
-  if (dF) s.add(&ddF, B * N * (size_t)nf * nz, S::In, dF);
+  s.add_opt(&ddF, B * N * (size_t)nf * nz, S::In, dF);
   s.add(&doF, B * rows, S::Out, out_F);
-  if (dF) s.add(&dodF, B * dcount, S::Out, out_dF);
-  sfb::DeviceBlock blk;
-  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
-  hipError_t e = s.upload();
-  if (e != hipSuccess) return sfb::hip_fail(e, "mesh function upload");
-  st = meshfn_device(fn, mesh, batch, nx, nu, nf, scale, d0, d1, dX, dFv, ddF, doF, dodF, nullptr);
-  if (st != SFB_OK) return st;
-  if ((e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
-  if (e != hipSuccess) return sfb::hip_fail(e, "mesh function download");
-  return SFB_OK;
+  s.add_opt(&dodF, B * dcount, S::Out, out_dF);
+  return sfb::staged_call(s, "mesh function host entry",
+                          [&] { return meshfn_device(fn, mesh, batch, nx, nu, nf, scale, d0, d1, dX, dFv, ddF, doF, dodF, nullptr); });
 }
 
 }  // namespace
@@ -492,18 +482,14 @@ sfb_status sfb_mesh_eval_pattern(const sfb_mesh *mesh, int32_t nx, int32_t nu, i
 {
   const sfb_status st = pattern_check(mesh, nx, nu, nf, rowptr, colind, nnz);
   if (st != SFB_OK) return st;
-  const int64_t n = L::meshfn::eval_pattern(mesh_nodes(mesh), nx, nu, nf, rowptr, colind);
-  if (nnz) *nnz = n;
-  return SFB_OK;
+  return pattern_done(nnz, L::meshfn::eval_pattern(mesh_nodes(mesh), nx, nu, nf, rowptr, colind));
 }
 
 sfb_status sfb_mesh_dyn_pattern(const sfb_mesh *mesh, int32_t nx, int32_t nu, int32_t *rowptr, int32_t *colind, int64_t *nnz)
 {
   const sfb_status st = pattern_check(mesh, nx, nu, nx, rowptr, colind, nnz);
   if (st != SFB_OK) return st;
-  const int64_t n = L::meshfn::dyn_pattern(mesh->nivals, mesh->K, nx, nu, rowptr, colind);
-  if (nnz) *nnz = n;
-  return SFB_OK;
+  return pattern_done(nnz, L::meshfn::dyn_pattern(mesh->nivals, mesh->K, nx, nu, rowptr, colind));
 }
 
 sfb_status sfb_mesh_eval_batch(const sfb_mesh *mesh, int64_t batch, int32_t nx, int32_t nu, int32_t nf, int scale, const double *t0, const double *tf,
@@ -548,13 +534,10 @@ sfb_status sfb_ocp_nlp_structure(const sfb_mesh *mesh, const sfb_ocp_dims *dims,
 
 sfb_status sfb_ocp_nlp_pattern(const sfb_mesh *mesh, const sfb_ocp_dims *dims, int32_t *rowptr, int32_t *colind, int64_t *nnz)
 {
-  const sfb_status st = ocp_dims_check(mesh, 0, dims);
+  sfb_status st = ocp_dims_check(mesh, 0, dims);
+  if (st == SFB_OK) st = pattern_out_check(rowptr, colind, nnz, "rowptr and colind: both or neither");
   if (st != SFB_OK) return st;
-  if ((rowptr == nullptr) != (colind == nullptr)) return sfb::fail(SFB_ERR_INVALID_ARG, "rowptr and colind: both or neither");
-  if (!rowptr && !nnz) return sfb::fail(SFB_ERR_INVALID_ARG, "NULL array");
-  const int64_t n = L::meshfn::ocp_nlp_pattern(mesh->nivals, mesh->K, to_dims(dims), rowptr, colind, nullptr);
-  if (nnz) *nnz = n;
-  return SFB_OK;
+  return pattern_done(nnz, L::meshfn::ocp_nlp_pattern(mesh->nivals, mesh->K, to_dims(dims), rowptr, colind, nullptr));
 }
 
 sfb_status sfb_ocp_nlp_bounds(const sfb_mesh *mesh, const sfb_ocp_dims *dims, const double *crl, const double *cru, const double *cel,
@@ -610,40 +593,28 @@ sfb_status sfb_ocp_nlp_batch_host(const sfb_mesh *mesh, const sfb_ocp_dims *dims
   const size_t nnz = (size_t)L::meshfn::ocp_nlp_pattern(mesh->nivals, mesh->K, to_dims(dims), nullptr, nullptr, nullptr);
   using S = sfb::Staging;
   S s;
-  double *dx, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr, *d4 = nullptr, *d5 = nullptr, *d6 = nullptr, *d7 = nullptr, *d8 = nullptr, *dg, *ddg = nullptr;
+  double *dx, *d1, *d2, *d3, *d4, *d5, *d6, *d7, *d8, *dg, *ddg;
   s.add(&dx, B * (size_t)vb[4], S::In, x);
   s.add(&d1, B * N * nx, S::In, Ff);
-  if (dg_val) s.add(&d2, B * N * nx * nz, S::In, dFf);
-  if (nq) s.add(&d3, B * N * nq, S::In, Fg);
-  if (nq && dg_val) s.add(&d4, B * N * nq * nz, S::In, dFg);
-  if (ncr) s.add(&d5, B * N * ncr, S::In, Fcr);
-  if (ncr && dg_val) s.add(&d6, B * N * ncr * nz, S::In, dFcr);
-  if (nce) s.add(&d7, B * nce, S::In, ce);
-  if (nce && dg_val) s.add(&d8, B * nce * ne, S::In, dce);
+  s.add_opt(&d2, B * N * nx * nz, S::In, dFf);
+  s.add_opt(&d3, B * N * nq, S::In, unless_empty(nq, Fg)); s.add_opt(&d4, B * N * nq * nz, S::In, unless_empty(nq, dFg));
+  s.add_opt(&d5, B * N * ncr, S::In, unless_empty(ncr, Fcr)); s.add_opt(&d6, B * N * ncr * nz, S::In, unless_empty(ncr, dFcr));
+  s.add_opt(&d7, B * nce, S::In, unless_empty(nce, ce)); s.add_opt(&d8, B * nce * ne, S::In, unless_empty(nce, dce));
   s.add(&dg, B * (size_t)cb[4], S::Out, g);
-  if (dg_val) s.add(&ddg, B * nnz, S::Out, dg_val);
-  sfb::DeviceBlock blk;
-  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
-  hipError_t e = s.upload();
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_ocp_nlp_batch_host upload");
-  st = sfb_ocp_nlp_batch(mesh, dims, batch, dx, d1, d2, d3, d4, d5, d6, d7, d8, dg, ddg, nullptr);
-  if (st != SFB_OK) return st;
-  if ((e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_ocp_nlp_batch_host");
-  return SFB_OK;
+  s.add_opt(&ddg, B * nnz, S::Out, dg_val);
+  return sfb::staged_call(s, "sfb_ocp_nlp_batch_host",
+                          [&] { return sfb_ocp_nlp_batch(mesh, dims, batch, dx, d1, d2, d3, d4, d5, d6, d7, d8, dg, ddg, nullptr); });
 }
 
 sfb_status sfb_ocp_nlp_hess_pattern(const sfb_mesh *mesh, const sfb_ocp_dims *dims, int32_t *colptr, int32_t *rowind, int64_t *nnz)
 {
-  const sfb_status st = ocp_dims_check(mesh, 0, dims);
+  sfb_status st = ocp_dims_check(mesh, 0, dims);
+  if (st == SFB_OK) st = pattern_out_check(colptr, rowind, nnz, "colptr and rowind: both or neither");
   if (st != SFB_OK) return st;
-  if ((colptr == nullptr) != (rowind == nullptr)) return sfb::fail(SFB_ERR_INVALID_ARG, "colptr and rowind: both or neither");
-  if (!colptr && !nnz) return sfb::fail(SFB_ERR_INVALID_ARG, "NULL array");
   const int64_t n = L::meshfn::ocp_nlp_hess_pattern(mesh->nivals, mesh->K, to_dims(dims), nullptr, nullptr, nullptr);
   if (n > 0x7fffffff) return sfb::fail(SFB_ERR_INVALID_ARG, "ocp nlp hessian: more entries than 32-bit indices hold");
   if (colptr) L::meshfn::ocp_nlp_hess_pattern(mesh->nivals, mesh->K, to_dims(dims), colptr, rowind, nullptr);
-  if (nnz) *nnz = n;
-  return SFB_OK;
+  return pattern_done(nnz, n);
 }
 
 sfb_status sfb_ocp_nlp_hess_batch(const sfb_mesh *mesh, const sfb_ocp_dims *dims, int64_t batch, const double *x, const double *lambda,
@@ -684,27 +655,20 @@ sfb_status sfb_ocp_nlp_hess_batch_host(const sfb_mesh *mesh, const sfb_ocp_dims 
   const size_t nnz = (size_t)L::meshfn::ocp_nlp_hess_pattern(mesh->nivals, mesh->K, to_dims(dims), nullptr, nullptr, nullptr);
   using S = sfb::Staging;
   S s;
-  double *dx, *dl, *ds, *d1, *d2, *d3 = nullptr, *d4 = nullptr, *d5 = nullptr, *d6, *d7 = nullptr, *dh;
+  double *dx, *dl, *ds, *d1, *d2, *d3, *d4, *d5, *d6, *d7, *dh;
   s.add(&dx, B * (size_t)vb[4], S::In, x);
   s.add(&dl, B * (size_t)cb[4], S::In, lambda);
   s.add(&ds, B, S::In, sigma);
   s.add(&d1, B * N * nx * nz, S::In, dFf);
   s.add(&d2, B * N * nz * nz, S::In, HLf);
-  if (nq) s.add(&d3, B * N * nq * nz, S::In, dFg);
-  if (nq) s.add(&d4, B * N * nz * nz, S::In, HLg);
-  if (ncr) s.add(&d5, B * N * nz * nz, S::In, HLcr);
+  s.add_opt(&d3, B * N * nq * nz, S::In, unless_empty(nq, dFg)); s.add_opt(&d4, B * N * nz * nz, S::In, unless_empty(nq, HLg));
+  s.add_opt(&d5, B * N * nz * nz, S::In, unless_empty(ncr, HLcr));
   s.add(&d6, B * ne * ne, S::In, d2theta);
-  if (nce) s.add(&d7, B * ne * ne, S::In, d2ce_l);
+  s.add_opt(&d7, B * ne * ne, S::In, unless_empty(nce, d2ce_l));
   s.add(&dh, B * nnz, S::Out, hess_val);
-  sfb::DeviceBlock blk;
-  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
-  hipError_t e = s.upload();
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_ocp_nlp_hess_batch_host upload");
-  st = sfb_ocp_nlp_hess_batch(mesh, dims, batch, dx, dl, ds, d1, d2, d3, d4, nullptr, d5, d6, d7, dh, nullptr);
-  if (st != SFB_OK) return st;
-  if ((e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_ocp_nlp_hess_batch_host");
-  return SFB_OK;
+  return sfb::staged_call(s, "sfb_ocp_nlp_hess_batch_host", [&] {
+    return sfb_ocp_nlp_hess_batch(mesh, dims, batch, dx, dl, ds, d1, d2, d3, d4, nullptr, d5, d6, d7, dh, nullptr);
+  });
 }
 
 sfb_status sfb_mesh_resample_batch(const sfb_mesh *mesh, int64_t batch, int32_t dim, int extend, const double *vals, double *out, void *stream)
@@ -763,15 +727,7 @@ sfb_status sfb_mesh_resample_batch_host(const sfb_mesh *mesh, int64_t batch, int
   S s;
   double *dv, *dout;
   s.add(&dv, B * (N + (extend ? 1 : 0)) * D, S::In, vals); s.add(&dout, B * R * D, S::Out, out);
-  sfb::DeviceBlock blk;
-  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
-  hipError_t e = s.upload();
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_mesh_resample_batch_host upload");
-  st = sfb_mesh_resample_batch(mesh, batch, dim, extend, dv, dout, nullptr);
-  if (st != SFB_OK) return st;
-  if ((e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_mesh_resample_batch_host");
-  return SFB_OK;
+  return sfb::staged_call(s, "sfb_mesh_resample_batch_host", [&] { return sfb_mesh_resample_batch(mesh, batch, dim, extend, dv, dout, nullptr); });
 }
 
 sfb_status sfb_mesh_dyn_error_batch_host(const sfb_mesh *mesh, int64_t batch, int32_t nx, const double *horizon, const double *X, const double *F,
@@ -787,15 +743,7 @@ sfb_status sfb_mesh_dyn_error_batch_host(const sfb_mesh *mesh, int64_t batch, in
   S s;
   double *dh, *dX, *dF, *de;
   s.add(&dh, B, S::In, horizon); s.add(&dX, B * R * D, S::In, X); s.add(&dF, B * R * D, S::In, F); s.add(&de, B * (size_t)mesh->nivals, S::Out, errs);
-  sfb::DeviceBlock blk;
-  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
-  hipError_t e = s.upload();
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_mesh_dyn_error_batch_host upload");
-  st = sfb_mesh_dyn_error_batch(mesh, batch, nx, dh, dX, dF, de, nullptr);
-  if (st != SFB_OK) return st;
-  if ((e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_mesh_dyn_error_batch_host");
-  return SFB_OK;
+  return sfb::staged_call(s, "sfb_mesh_dyn_error_batch_host", [&] { return sfb_mesh_dyn_error_batch(mesh, batch, nx, dh, dX, dF, de, nullptr); });
 }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 // plan, the QP arrays, the solver workspace and the agents' state.  The kernels are in nlp_sqp.hip, the law in DESIGN.md.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -124,57 +125,38 @@ sfb_status sfb_nlp_sqp_create(int n, int m, const int32_t *J_rowptr, const int32
   int64_t wsb = 0;
   if (batch > 0 && (st = sfb_sparse_qp_plan_workspace_bytes(h->plan, batch, &wsb)) != SFB_OK) return drop(st);
 
-  // one allocation: [solver workspace | doubles | 32-bit integers], every part a multiple of 16 bytes from the start
+  // One allocation: [solver workspace | bounds and the agents' state | the compacted QP arrays | 32-bit integers], every
+  // region at a multiple of 16 bytes.  The regions' sizes and every pointer come from these declarations.
   sfb::NlpSqpDev &D = h->dev;
   const size_t B = (size_t)batch, N = (size_t)n, M = (size_t)m, MQ = (size_t)mq, nnzP = (size_t)pt.nnzP, nnzJ = (size_t)pt.nnzJ, nnzA = nnzJ + pt.nb;
-  const size_t ws_bytes = ((size_t)wsb + 15) / 16 * 16;
-  const size_t shared_d = 2 * N + 2 * M;
-  const size_t state_d  = B * (3 * N + M + MQ + 12);
-  const size_t qp_d     = B * (nnzP + N + nnzA + 2 * MQ + 2 * (N + MQ));
-  const size_t doubles  = (shared_d + state_d + qp_d + 1) / 2 * 2;
-  const size_t ints     = 3 * nnzP + (N + 1) + 2 * nnzJ + (size_t)pt.nb + N + 5 * B + 4 * B + 4;
-  if ((e = hipMalloc(reinterpret_cast<void **>(&h->mem), ws_bytes + doubles * 8 + ints * 4)) != hipSuccess) return drop(sfb::hip_fail(e, "hipMalloc(nlp_sqp)"));
+  using S = sfb::Staging;
+  S state, ints;
+  sfb::DeviceArena qp;
+  state.add(&D.xl, N, S::In, xl); state.add(&D.xu, N, S::In, xu); state.add(&D.gl, M, S::In, gl); state.add(&D.gu, M, S::In, gu);
+  state.add(&D.x, B * N); state.add(&D.z, B * N); state.add(&D.d, B * N); state.add(&D.lambda, B * M); state.add(&D.yqp, B * MQ);
+  state.add(&D.mu, B); state.add(&D.nu, B); state.add(&D.alpha, B); state.add(&D.r_stat, B); state.add(&D.r_pri, B); state.add(&D.r_comp, B);
+  state.add(&D.v1, B); state.add(&D.phi0, B); state.add(&D.slope, B); state.add(&D.dd, B); state.add(&D.dPd, B);  // (the debug entry's five sums)
+  qp.add(&h->Px, B * nnzP); qp.add(&h->q, B * N); qp.add(&h->Ax, B * nnzA); qp.add(&h->l, B * MQ); qp.add(&h->u, B * MQ);
+  qp.add(&h->wx, B * N); qp.add(&h->wy, B * MQ); qp.add(&h->xs, B * N); qp.add(&h->ys, B * MQ);
+  ints.add(&D.P_row, nnzP, S::In, pt.P_rowind.data()); ints.add(&D.P_col, nnzP, S::In, P_col.data()); ints.add(&D.P_src, nnzP, S::In, pt.P_src.data());
+  ints.add(&D.Jc_colptr, N + 1, S::In, pt.Jc_colptr.data()); ints.add(&D.Jc_row, nnzJ, S::In, pt.Jc_row.data());
+  ints.add(&D.Jc_pos, nnzJ, S::In, pt.Jc_pos.data()); ints.add(&D.bound_var, (size_t)pt.nb, S::In, pt.bound_var.data());
+  ints.add(&D.bound_row, N, S::In, pt.bound_row.data());
+  ints.add(&D.status, B); ints.add(&D.iter, B); ints.add(&D.phase, B); ints.add(&D.need, B); ints.add(&D.halvings, B);
+  ints.add(&h->qiter, B); ints.add(&h->qcode, B); ints.add(&h->list, B); ints.add(&h->searching, B); ints.add(&h->count, 1);
+  const auto next16 = [](size_t at) { return (at + 15) / 16 * 16; };
+  const size_t state_at = next16((size_t)wsb), qp_at = next16(state_at + state.bytes()), ints_at = next16(qp_at + qp.bytes());
+  if ((e = hipMalloc(reinterpret_cast<void **>(&h->mem), ints_at + ints.bytes())) != hipSuccess) return drop(sfb::hip_fail(e, "hipMalloc(nlp_sqp)"));
   if ((e = hipHostMalloc(reinterpret_cast<void **>(&h->h_count), 16, hipHostMallocDefault)) != hipSuccess) return drop(sfb::hip_fail(e, "hipHostMalloc(nlp_sqp)"));
-  h->ws     = h->mem;
-  double *d = reinterpret_cast<double *>(h->mem + ws_bytes);
-  double *dxl = d; d += N;
-  double *dxu = d; d += N;
-  double *dgl = d; d += M;
-  double *dgu = d; d += M;
-  const auto take = [&d](size_t count) { double *r = d; d += count; return r; };
-  D.x = take(B * N); D.z = take(B * N); D.d = take(B * N); D.lambda = take(B * M); D.yqp = take(B * MQ);
-  D.mu = take(B); D.nu = take(B); D.alpha = take(B); D.r_stat = take(B); D.r_pri = take(B); D.r_comp = take(B); D.v1 = take(B);
-  D.phi0 = take(B); D.slope = take(B); D.dd = take(B); D.dPd = take(B);
-  (void)take(B);
-  h->Px = take(B * nnzP); h->q = take(B * N); h->Ax = take(B * nnzA); h->l = take(B * MQ); h->u = take(B * MQ);
-  h->wx = take(B * N); h->wy = take(B * MQ); h->xs = take(B * N); h->ys = take(B * MQ);
-  int32_t *i = reinterpret_cast<int32_t *>(h->mem + ws_bytes + doubles * 8);
-  const auto upload = [&i, &e](const int32_t *src, size_t count) {
-    int32_t *r = i;
-    i += count;
-    if (e == hipSuccess && count > 0) e = hipMemcpy(r, src, count * 4, hipMemcpyHostToDevice);
-    return r;
-  };
-  D.P_row     = upload(pt.P_rowind.data(), nnzP);
-  D.P_col     = upload(P_col.data(), nnzP);
-  D.P_src     = upload(pt.P_src.data(), nnzP);
-  D.Jc_colptr = upload(pt.Jc_colptr.data(), N + 1);
-  D.Jc_row    = upload(pt.Jc_row.data(), nnzJ);
-  D.Jc_pos    = upload(pt.Jc_pos.data(), nnzJ);
-  D.bound_var = upload(pt.bound_var.data(), (size_t)pt.nb);
-  D.bound_row = upload(pt.bound_row.data(), N);
-  const auto itake = [&i](size_t count) { int32_t *r = i; i += count; return r; };
-  D.status = itake(B); D.iter = itake(B); D.phase = itake(B); D.need = itake(B); D.halvings = itake(B);
-  h->qiter = reinterpret_cast<uint32_t *>(itake(B)); h->qcode = itake(B); h->list = itake(B); h->searching = itake(B); h->count = itake(1);
-  if (e == hipSuccess) e = hipMemcpy(dxl, xl, N * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dxu, xu, N * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess && M > 0) e = hipMemcpy(dgl, gl, M * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess && M > 0) e = hipMemcpy(dgu, gu, M * 8, hipMemcpyHostToDevice);
+  h->ws = h->mem;
+  if (!state.bind(h->mem + state_at) || !qp.bind(h->mem + qp_at) || !ints.bind(h->mem + ints_at))
+    return drop(sfb::fail(SFB_ERR_UNSUPPORTED, "more staged arrays than the table holds"));
+  if ((e = state.upload()) == hipSuccess) e = ints.upload();
   // the state starts defined (all zero, nothing running) until sfb_nlp_sqp_set_start; so do the QP arrays the debug entry shows
-  if (e == hipSuccess) e = hipMemset(h->mem + ws_bytes + shared_d * 8, 0, (doubles - shared_d) * 8);
-  if (e == hipSuccess) e = hipMemset(D.status, 0, (9 * B + 1) * 4);
+  const char *qp_end = h->mem + qp_at + qp.bytes(), *ints_end = h->mem + ints_at + ints.bytes();
+  if (e == hipSuccess) e = hipMemset(D.x, 0, (size_t)(qp_end - reinterpret_cast<const char *>(D.x)));
+  if (e == hipSuccess) e = hipMemset(D.status, 0, (size_t)(ints_end - reinterpret_cast<const char *>(D.status)));
   if (e != hipSuccess) return drop(sfb::hip_fail(e, "sfb_nlp_sqp_create"));
-  D.xl = dxl; D.xu = dxu; D.gl = dgl; D.gu = dgu;
   D.n = n; D.m = m; D.nb = pt.nb; D.mq = mq; D.nnzJ = pt.nnzJ; D.nnzH = pt.nnzH; D.nnzP = pt.nnzP; D.nnzA = (int)nnzA;
   D.max_iter = (int)P.max_iter;
   D.tol = P.tol; D.kappa = P.kappa; D.mu_first = P.mu_first; D.mu_grow = P.mu_grow; D.mu_max = P.mu_max;
@@ -313,25 +295,45 @@ sfb_status sfb_nlp_sqp_debug_buffers(sfb_nlp_sqp *h, const double **Px, const do
 
 // ---- host-pointer variants (synchronous, null stream): what a host front such as solve_nlp_sqp (nlp_solver.hpp) stages through ----
 namespace {
-sfb_status host_stage(sfb_nlp_sqp *h)
+// The staged arrays of the host-pointer entries: three layouts of the one buffer the handle keeps, a call at a time.  They are
+// declared here, so that the buffer's size and every pointer in it come from the same lists.  (trial's output, [batch][n], is
+// the first array of the first layout.)
+struct HostStage {
+  sfb::Staging s;
+  double *a[5];
+};
+using S = sfb::Staging;
+void declare_start(const sfb_nlp_sqp *h, HostStage &g, const double *x, const double *lambda, const double *z)
 {
-  if (h->stage || h->batch == 0) return SFB_OK;
+  const size_t B = (size_t)h->batch, N = (size_t)h->dev.n, M = (size_t)h->dev.m;
+  g.s.add(&g.a[0], B * N, S::In, x); g.s.add(&g.a[1], B * M, S::In, lambda); g.s.add(&g.a[2], B * N, S::In, z);
+}
+void declare_direction(const sfb_nlp_sqp *h, HostStage &g, const double *f, const double *df, const double *gv, const double *dg_val, const double *hess_val)
+{
+  const size_t B = (size_t)h->batch;
   const sfb::NlpSqpDev &D = h->dev;
-  const size_t per = 1 + (size_t)D.n + D.m + D.nnzJ + D.nnzH;
-  const hipError_t e = hipMalloc(reinterpret_cast<void **>(&h->stage), (size_t)h->batch * per * 8);
-  return e == hipSuccess ? SFB_OK : sfb::hip_fail(e, "hipMalloc(nlp_sqp host staging)");
+  g.s.add(&g.a[0], B, S::In, f); g.s.add(&g.a[1], B * D.n, S::In, df); g.s.add(&g.a[2], B * D.m, S::In, gv);
+  g.s.add(&g.a[3], B * D.nnzJ, S::In, dg_val); g.s.add(&g.a[4], B * D.nnzH, S::In, hess_val);
 }
-sfb_status copy_to_device(double *dst, const double *src, size_t count)
+void declare_accept(const sfb_nlp_sqp *h, HostStage &g, const double *f_trial, const double *g_trial)
 {
-  if (!count || !src) return SFB_OK;
-  const hipError_t e = hipMemcpy(dst, src, count * 8, hipMemcpyHostToDevice);
+  const size_t B = (size_t)h->batch;
+  g.s.add(&g.a[0], B, S::In, f_trial); g.s.add(&g.a[1], B * h->dev.m, S::In, g_trial);
+}
+// g's arrays in the handle's staging (made by the first host entry, large enough for every layout), the inputs uploaded
+sfb_status host_stage(sfb_nlp_sqp *h, HostStage &g)
+{
+  if (!h->stage && h->batch > 0) {
+    HostStage start, direction, accept;
+    declare_start(h, start, nullptr, nullptr, nullptr);
+    declare_direction(h, direction, nullptr, nullptr, nullptr, nullptr, nullptr);
+    declare_accept(h, accept, nullptr, nullptr);
+    const hipError_t e = hipMalloc(reinterpret_cast<void **>(&h->stage), std::max({start.s.bytes(), direction.s.bytes(), accept.s.bytes()}));
+    if (e != hipSuccess) return sfb::hip_fail(e, "hipMalloc(nlp_sqp host staging)");
+  }
+  g.s.bind(h->stage);
+  const hipError_t e = g.s.upload();
   return e == hipSuccess ? SFB_OK : sfb::hip_fail(e, "hipMemcpy(host to device)");
-}
-sfb_status copy_to_host_bytes(void *dst, const void *src, size_t bytes)
-{
-  if (!bytes || !dst) return SFB_OK;
-  const hipError_t e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
-  return e == hipSuccess ? SFB_OK : sfb::hip_fail(e, "hipMemcpy(device to host)");
 }
 }  // namespace
 
@@ -340,15 +342,10 @@ sfb_status sfb_nlp_sqp_set_start_host(sfb_nlp_sqp *h, const double *x, const dou
   if (!h) return sfb::fail(SFB_ERR_INVALID_ARG, "handle is NULL");
   if (h->batch > 0 && !x) return sfb::fail(SFB_ERR_INVALID_ARG, "x is NULL");
   if (sfb_status st = check_device(h); st != SFB_OK) return st;
-  if (sfb_status st = host_stage(h); st != SFB_OK) return st;
-  const size_t B = (size_t)h->batch, N = (size_t)h->dev.n, M = (size_t)h->dev.m;
-  double *dx = h->stage, *dl = dx + B * N, *dz = dl + B * M;  // (2 n + m <= 1 + n + m + nnzJ + nnzH: every diagonal is stored)
-  sfb_status st = copy_to_device(dx, x, B * N);
-  if (st == SFB_OK) st = copy_to_device(dl, lambda, B * M);
-  if (st == SFB_OK) st = copy_to_device(dz, z, B * N);
-  if (st != SFB_OK) return st;
-  st = sfb_nlp_sqp_set_start(h, dx, lambda ? dl : nullptr, z ? dz : nullptr, nullptr);
-  if (st != SFB_OK) return st;
+  HostStage g;
+  declare_start(h, g, x, lambda, z);
+  if (sfb_status st = host_stage(h, g); st != SFB_OK) return st;
+  if (sfb_status st = sfb_nlp_sqp_set_start(h, g.a[0], lambda ? g.a[1] : nullptr, z ? g.a[2] : nullptr, nullptr); st != SFB_OK) return st;
   const hipError_t e = hipStreamSynchronize(nullptr);  // the staging is reused by the next call
   return e == hipSuccess ? SFB_OK : sfb::hip_fail(e, "hipStreamSynchronize");
 }
@@ -360,17 +357,10 @@ sfb_status sfb_nlp_sqp_direction_host(sfb_nlp_sqp *h, const double *f, const dou
   if (h->batch > 0 && (!f || !df || !hess_val || (h->dev.m > 0 && !g) || (h->dev.nnzJ > 0 && !dg_val)))
     return sfb::fail(SFB_ERR_INVALID_ARG, "NULL f / df / g / dg_val / hess_val");
   if (sfb_status st = check_device(h); st != SFB_OK) return st;
-  if (sfb_status st = host_stage(h); st != SFB_OK) return st;
-  const size_t B = (size_t)h->batch;
-  const sfb::NlpSqpDev &D = h->dev;
-  double *d_f = h->stage, *d_df = d_f + B, *d_g = d_df + B * D.n, *d_dg = d_g + B * D.m, *d_h = d_dg + B * (size_t)D.nnzJ;
-  sfb_status st = copy_to_device(d_f, f, B);
-  if (st == SFB_OK) st = copy_to_device(d_df, df, B * D.n);
-  if (st == SFB_OK) st = copy_to_device(d_g, g, B * D.m);
-  if (st == SFB_OK) st = copy_to_device(d_dg, dg_val, B * (size_t)D.nnzJ);
-  if (st == SFB_OK) st = copy_to_device(d_h, hess_val, B * (size_t)D.nnzH);
-  if (st != SFB_OK) return st;
-  return sfb_nlp_sqp_direction(h, d_f, d_df, d_g, d_dg, d_h, active, nullptr);
+  HostStage s;
+  declare_direction(h, s, f, df, g, dg_val, hess_val);
+  if (sfb_status st = host_stage(h, s); st != SFB_OK) return st;
+  return sfb_nlp_sqp_direction(h, s.a[0], s.a[1], s.a[2], s.a[3], s.a[4], active, nullptr);
 }
 
 sfb_status sfb_nlp_sqp_trial_host(sfb_nlp_sqp *h, double *x_trial)
@@ -378,9 +368,12 @@ sfb_status sfb_nlp_sqp_trial_host(sfb_nlp_sqp *h, double *x_trial)
   if (!h) return sfb::fail(SFB_ERR_INVALID_ARG, "handle is NULL");
   if (h->batch > 0 && !x_trial) return sfb::fail(SFB_ERR_INVALID_ARG, "x_trial is NULL");
   if (sfb_status st = check_device(h); st != SFB_OK) return st;
-  if (sfb_status st = host_stage(h); st != SFB_OK) return st;
-  if (sfb_status st = sfb_nlp_sqp_trial(h, h->stage, nullptr); st != SFB_OK) return st;
-  return copy_to_host_bytes(x_trial, h->stage, (size_t)h->batch * h->dev.n * 8);
+  HostStage g;
+  g.s.add(&g.a[0], (size_t)h->batch * h->dev.n, S::Out, x_trial);
+  if (sfb_status st = host_stage(h, g); st != SFB_OK) return st;
+  if (sfb_status st = sfb_nlp_sqp_trial(h, g.a[0], nullptr); st != SFB_OK) return st;
+  const hipError_t e = g.s.download();
+  return e == hipSuccess ? SFB_OK : sfb::hip_fail(e, "hipMemcpy(device to host)");
 }
 
 sfb_status sfb_nlp_sqp_accept_host(sfb_nlp_sqp *h, const double *f_trial, const double *g_trial, int64_t *searching)
@@ -388,13 +381,10 @@ sfb_status sfb_nlp_sqp_accept_host(sfb_nlp_sqp *h, const double *f_trial, const 
   if (!h) return sfb::fail(SFB_ERR_INVALID_ARG, "handle is NULL");
   if (h->batch > 0 && (!f_trial || (h->dev.m > 0 && !g_trial))) return sfb::fail(SFB_ERR_INVALID_ARG, "NULL f_trial / g_trial");
   if (sfb_status st = check_device(h); st != SFB_OK) return st;
-  if (sfb_status st = host_stage(h); st != SFB_OK) return st;
-  const size_t B = (size_t)h->batch;
-  double *d_f = h->stage, *d_g = d_f + B;
-  sfb_status st = copy_to_device(d_f, f_trial, B);
-  if (st == SFB_OK) st = copy_to_device(d_g, g_trial, B * h->dev.m);
-  if (st != SFB_OK) return st;
-  return sfb_nlp_sqp_accept(h, d_f, d_g, searching, nullptr);
+  HostStage g;
+  declare_accept(h, g, f_trial, g_trial);
+  if (sfb_status st = host_stage(h, g); st != SFB_OK) return st;
+  return sfb_nlp_sqp_accept(h, g.a[0], g.a[1], searching, nullptr);
 }
 
 sfb_status sfb_nlp_sqp_state_host(sfb_nlp_sqp *h, double *x, double *lambda, double *z, int32_t *status, int32_t *iter, double *r_stat,
@@ -404,18 +394,15 @@ sfb_status sfb_nlp_sqp_state_host(sfb_nlp_sqp *h, double *x, double *lambda, dou
   if (sfb_status st = check_device(h); st != SFB_OK) return st;
   const size_t B = (size_t)h->batch;
   const sfb::NlpSqpDev &D = h->dev;
-  sfb_status st = copy_to_host_bytes(x, D.x, (B * D.n) * 8);
-  if (st == SFB_OK) st = copy_to_host_bytes(lambda, D.lambda, (B * D.m) * 8);
-  if (st == SFB_OK) st = copy_to_host_bytes(z, D.z, (B * D.n) * 8);
-  if (st == SFB_OK) st = copy_to_host_bytes(status, D.status, (B) * 4);
-  if (st == SFB_OK) st = copy_to_host_bytes(iter, D.iter, (B) * 4);
-  if (st == SFB_OK) st = copy_to_host_bytes(r_stat, D.r_stat, (B) * 8);
-  if (st == SFB_OK) st = copy_to_host_bytes(r_pri, D.r_pri, (B) * 8);
-  if (st == SFB_OK) st = copy_to_host_bytes(r_comp, D.r_comp, (B) * 8);
-  if (st == SFB_OK) st = copy_to_host_bytes(mu, D.mu, (B) * 8);
-  if (st == SFB_OK) st = copy_to_host_bytes(alpha, D.alpha, (B) * 8);
-  if (st == SFB_OK) st = copy_to_host_bytes(nu, D.nu, (B) * 8);
-  return st;
+  const struct { void *host; const void *dev; size_t bytes; } rows[] = {
+    {x, D.x, B * D.n * 8}, {lambda, D.lambda, B * D.m * 8}, {z, D.z, B * D.n * 8}, {status, D.status, B * 4}, {iter, D.iter, B * 4},
+    {r_stat, D.r_stat, B * 8}, {r_pri, D.r_pri, B * 8}, {r_comp, D.r_comp, B * 8}, {mu, D.mu, B * 8}, {alpha, D.alpha, B * 8}, {nu, D.nu, B * 8}};
+  for (const auto &r : rows) {
+    if (!r.bytes || !r.host) continue;
+    const hipError_t e = hipMemcpy(r.host, r.dev, r.bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return sfb::hip_fail(e, "hipMemcpy(device to host)");
+  }
+  return SFB_OK;
 }
 
 }  // extern "C"

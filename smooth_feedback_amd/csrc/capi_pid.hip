@@ -109,15 +109,9 @@ sfb_status sfb_pid_step_batch_host(const sfb_pid_group *group, int64_t batch, do
   s.add(&dg, Bd * E, S::In, g_des); s.add(&dvd, Bd * D, S::In, v_des); s.add(&dad, Bd * D, S::In, a_des);
   s.add(&dkp, Bg * D, S::In, kp); s.add(&dkd, Bg * D, S::In, kd); s.add(&dki, Bg * D, S::In, ki);
   s.add(&die, B * D, S::InOut, i_err); s.add(&dtl, B, S::InOut, t_last); s.add(&du, B * D, S::Out, u);
-  sfb::DeviceBlock blk;
-  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
-  hipError_t e = s.upload();
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_pid_step_batch_host upload");
-  st = sfb_pid_step_batch(group, batch, t, dx, dv, dg, dvd, dad, des_shared, dkp, dkd, dki, gains_shared, windup_limit, die, dtl, du, nullptr);
-  if (st != SFB_OK) return st;
-  if ((e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_pid_step_batch_host");
-  return SFB_OK;
+  return sfb::staged_call(s, "sfb_pid_step_batch_host", [&] {
+    return sfb_pid_step_batch(group, batch, t, dx, dv, dg, dvd, dad, des_shared, dkp, dkd, dki, gains_shared, windup_limit, die, dtl, du, nullptr);
+  });
 }
 
 sfb_status sfb_pid_rollout_batch_host(const sfb_pid_group *group, int64_t batch, double t0, double dt, int64_t steps,
@@ -142,18 +136,12 @@ sfb_status sfb_pid_rollout_batch_host(const sfb_pid_group *group, int64_t batch,
   double *dx, *dv, *dg, *dvd, *dkp, *dkd, *dki, *dum, *die, *dtl, *du, *dc;
   s.add(&dx, B * E, S::InOut, x); s.add(&dv, B * D, S::InOut, v);
   s.add(&dg, Bd * E, S::In, g_des0); s.add(&dvd, Bd * D, S::In, v_des);
-  s.add(&dkp, Bg * D, S::In, kp); s.add(&dkd, Bg * D, S::In, kd); s.add(&dki, Bg * D, S::In, ki); s.add(&dum, D, S::In, u_max);
+  s.add(&dkp, Bg * D, S::In, kp); s.add(&dkd, Bg * D, S::In, kd); s.add(&dki, Bg * D, S::In, ki); s.add_opt(&dum, D, S::In, u_max);
   s.add(&die, B * D, S::InOut, i_err); s.add(&dtl, B, S::InOut, t_last); s.add(&du, B * D, S::Out, u_last); s.add(&dc, B, S::Out, cost);
-  sfb::DeviceBlock blk;
-  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
-  hipError_t e = s.upload();
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_pid_rollout_batch_host upload");
-  st = sfb_pid_rollout_batch(group, batch, t0, dt, steps, dx, dv, dg, dvd, des_shared, dkp, dkd, dki, gains_shared, windup_limit,
-                             u_max ? dum : nullptr, die, dtl, du, dc, nullptr);
-  if (st != SFB_OK) return st;
-  if ((e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_pid_rollout_batch_host");
-  return SFB_OK;
+  return sfb::staged_call(s, "sfb_pid_rollout_batch_host", [&] {
+    return sfb_pid_rollout_batch(group, batch, t0, dt, steps, dx, dv, dg, dvd, des_shared, dkp, dkd, dki, gains_shared, windup_limit, dum, die, dtl,
+                                 du, dc, nullptr);
+  });
 }
 
 }  // extern "C"

@@ -136,15 +136,8 @@ sfb_status sfb_spline_fit_cubic_batch_host(const sfb_pid_group *group, int64_t b
   S s;
   double *dtk, *dgk, *dV;
   s.add(&dtk, (tk_shared ? 1 : B) * K, S::In, tk); s.add(&dgk, B * K * E, S::In, gk); s.add(&dV, B * (K - 1) * 3 * D, S::Out, V);
-  sfb::DeviceBlock blk;
-  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
-  hipError_t e = s.upload();
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_spline_fit_cubic_batch_host upload");
-  st = sfb_spline_fit_cubic_batch(group, batch, nknots, dtk, tk_shared, dgk, dV, nullptr);
-  if (st != SFB_OK) return st;
-  if ((e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_spline_fit_cubic_batch_host");
-  return SFB_OK;
+  return sfb::staged_call(s, "sfb_spline_fit_cubic_batch_host",
+                          [&] { return sfb_spline_fit_cubic_batch(group, batch, nknots, dtk, tk_shared, dgk, dV, nullptr); });
 }
 
 sfb_status sfb_spline_eval_batch_host(const sfb_pid_group *group, int64_t batch, int64_t nknots, const double *tk, const double *gk,
@@ -163,17 +156,11 @@ sfb_status sfb_spline_eval_batch_host(const sfb_pid_group *group, int64_t batch,
   S s;
   double *dtk, *dgk, *dV, *dts, *dt, *dg, *dvel, *dacc;
   s.add(&dtk, Bs * K, S::In, tk); s.add(&dgk, Bs * K * E, S::In, gk); s.add(&dV, Bs * (K - 1) * 3 * D, S::In, V);
-  s.add(&dts, ts0 ? B : 0, S::In, ts0); s.add(&dt, (t_shared ? 1 : B) * T, S::In, t);
+  s.add_opt(&dts, B, S::In, ts0); s.add(&dt, (t_shared ? 1 : B) * T, S::In, t);
   s.add(&dg, B * T * E, S::Out, g); s.add(&dvel, B * T * D, S::Out, vel); s.add(&dacc, B * T * D, S::Out, acc);
-  sfb::DeviceBlock blk;
-  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
-  hipError_t e = s.upload();
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_spline_eval_batch_host upload");
-  st = sfb_spline_eval_batch(group, batch, nknots, dtk, dgk, dV, spline_shared, ts0 ? dts : nullptr, nt, dt, t_shared, dg, dvel, dacc, nullptr);
-  if (st != SFB_OK) return st;
-  if ((e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_spline_eval_batch_host");
-  return SFB_OK;
+  return sfb::staged_call(s, "sfb_spline_eval_batch_host", [&] {
+    return sfb_spline_eval_batch(group, batch, nknots, dtk, dgk, dV, spline_shared, dts, nt, dt, t_shared, dg, dvel, dacc, nullptr);
+  });
 }
 
 sfb_status sfb_pid_rollout_spline_batch_host(const sfb_pid_group *group, int64_t batch, double t0, double dt, int64_t steps, double *x,
@@ -197,19 +184,13 @@ sfb_status sfb_pid_rollout_spline_batch_host(const sfb_pid_group *group, int64_t
   double *dx, *dv, *dtk, *dgk, *dV, *dts, *dkp, *dkd, *dki, *dum, *die, *dtl, *du, *dc;
   s.add(&dx, B * E, S::InOut, x); s.add(&dv, B * D, S::InOut, v);
   s.add(&dtk, Bs * K, S::In, tk); s.add(&dgk, Bs * K * E, S::In, gk); s.add(&dV, Bs * (K - 1) * 3 * D, S::In, V);
-  s.add(&dts, ts0 ? B : 0, S::In, ts0);
-  s.add(&dkp, Bg * D, S::In, kp); s.add(&dkd, Bg * D, S::In, kd); s.add(&dki, Bg * D, S::In, ki); s.add(&dum, D, S::In, u_max);
+  s.add_opt(&dts, B, S::In, ts0);
+  s.add(&dkp, Bg * D, S::In, kp); s.add(&dkd, Bg * D, S::In, kd); s.add(&dki, Bg * D, S::In, ki); s.add_opt(&dum, D, S::In, u_max);
   s.add(&die, B * D, S::InOut, i_err); s.add(&dtl, B, S::InOut, t_last); s.add(&du, B * D, S::Out, u_last); s.add(&dc, B, S::Out, cost);
-  sfb::DeviceBlock blk;
-  if ((st = sfb::stage_per_call(s, blk)) != SFB_OK) return st;
-  hipError_t e = s.upload();
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_pid_rollout_spline_batch_host upload");
-  st = sfb_pid_rollout_spline_batch(group, batch, t0, dt, steps, dx, dv, nknots, dtk, dgk, dV, spline_shared, ts0 ? dts : nullptr, dkp, dkd,
-                                    dki, gains_shared, windup_limit, u_max ? dum : nullptr, die, dtl, du, dc, nullptr);
-  if (st != SFB_OK) return st;
-  if ((e = hipDeviceSynchronize()) == hipSuccess) e = s.download();
-  if (e != hipSuccess) return sfb::hip_fail(e, "sfb_pid_rollout_spline_batch_host");
-  return SFB_OK;
+  return sfb::staged_call(s, "sfb_pid_rollout_spline_batch_host", [&] {
+    return sfb_pid_rollout_spline_batch(group, batch, t0, dt, steps, dx, dv, nknots, dtk, dgk, dV, spline_shared, dts, dkp, dkd, dki, gains_shared,
+                                        windup_limit, dum, die, dtl, du, dc, nullptr);
+  });
 }
 
 }  // extern "C"

@@ -108,6 +108,26 @@ def test_zero_widths_and_empty_batches(sfb):
     assert lib.sfb_mesh_dyn_error_batch_host(C.byref(mesh.c), 0, 2, p(out), p(out), p(out), p(errs)) == sfb._capi.SFB_OK and np.all(errs == 7.0)
 
 
+def test_more_meshes_than_a_device_keeps_are_dropped_and_rebuilt_with_the_same_lists(sfb):
+    """70 distinct two-interval meshes through sfb_mesh_dyn_error_batch_host (the entry that reads the interval widths): a
+    device keeps 64 interval lists, so the cache is emptied on the way whatever it held before.  Meshes 0, 1 and 69 called
+    again give the bits of their first run, and mesh 0 stays within the gate against the restatement (random X, F: the
+    errors are of order one, the fixture's "coarse" class)."""
+    K = np.array([2, 3])
+    tau0 = [np.array([0.0, 0.30 + 0.005 * i]) for i in range(70)]
+    rng = np.random.default_rng(64)
+    h, X, F = rng.uniform(0.5, 1.5, 3), rng.uniform(-1, 1, (3, 9, 2)), rng.uniform(-1, 1, (3, 9, 2))
+    meshes = [sfb.PHMesh(K, t) for t in tau0]
+    first = [sfb.mesh_dyn_error_batch_host(m, h, X, F) for m in meshes]
+    for i in (0, 1, 69):
+        assert np.array_equal(sfb.mesh_dyn_error_batch_host(meshes[i], h, X, F), first[i]), i
+    assert len({e.tobytes() for e in first}) == 70                                 # every mesh had a list of its own
+    for b in range(3):
+        want = R.dyn_error(K, tau0[0], h[b], X[b], F[b])
+        assert want.min() > G.CLASS_BOUNDS["coarse"][0]
+        G.check("dynerr.coarse", first[0][b], want, "mesh 0 of 70, agent %d" % b)
+
+
 @pytest.mark.parametrize("name", ["co_three5", "re_u13x12", "ex_mixed"])
 def test_device_pointer_entries_equal_the_host_entries_bit_for_bit(sfb, name):
     import torch

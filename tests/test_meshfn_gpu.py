@@ -152,6 +152,28 @@ def test_two_meshes_used_alternately_keep_their_own_tables(sfb):
         G.check(key + ".dF", want[1][0], G.case(name)[key + ".dF"], name)
 
 
+def test_more_meshes_than_a_device_keeps_are_dropped_and_rebuilt_with_the_same_tables(sfb):
+    """70 distinct two-interval meshes through sfb_mesh_dyn_batch_host (it reads every table: nodes, weights, differentiation
+    matrices, the entry -> row table): a device keeps 64 sets of tables, so the cache is emptied on the way whatever it held
+    before.  Meshes 0, 1 and 69 called again give the bits of their first run, and mesh 0 stays within the gates against
+    the restatement."""
+    K, nx, nu, B = np.array([2, 3]), 2, 1, 3
+    tau0 = [np.array([0.0, 0.30 + 0.005 * i]) for i in range(70)]
+    rng = np.random.default_rng(64)
+    t0, tf = rng.uniform(-1, 0, B), rng.uniform(1, 2, B)
+    X, F, dF = rng.uniform(-1, 1, (B, 6, nx)), rng.uniform(-1, 1, (B, 5, nx)), rng.uniform(-1, 1, (B, 5, nx, 1 + nx + nu))
+    meshes = [sfb.PHMesh(K, t) for t in tau0]
+    first = [sfb.mesh_dyn_batch_host(m, nu, t0, tf, X, F, dF) for m in meshes]
+    for i in (0, 1, 69):
+        again = sfb.mesh_dyn_batch_host(meshes[i], nu, t0, tf, X, F, dF)
+        assert np.array_equal(again[0], first[i][0]) and np.array_equal(again[1], first[i][1]), i
+    assert len({f[0].tobytes() + f[1].tobytes() for f in first}) == 70              # every mesh had tables of its own
+    for b in range(B):
+        want = MR.functions(K, tau0[0], (nx, nu, nx), t0[b], tf[b], X[b], F[b], dF[b], order=1)
+        G.check("dyn.F", first[0][0][b], want["dyn.F"], "mesh 0 of 70, agent %d" % b)
+        G.check("dyn.dF", first[0][1][b], want["dyn.dF"], "mesh 0 of 70, agent %d" % b)
+
+
 def _se2_exp(a, b, th):
     s, c = np.sin(th), np.cos(th)
     A, Bc = (s / th, (1 - c) / th) if abs(th) > 1e-9 else (1.0, 0.0)

@@ -341,6 +341,46 @@ def test_hs71_end_to_end(sfb):
     s2.close()
 
 
+@pytest.mark.parametrize("duals", (True, False))
+def test_host_entries_stage_one_full_step_to_the_bits_of_the_device_entries(sfb, duals):
+    """HS71 with batch 3 (odd, so that every staged array behind the first is only 8-byte aligned): set_start, direction, trial,
+    accept and state through the _host entries on numpy arrays, and the same step through the device-pointer entries on torch
+    tensors, from the same numbers.  The trial point and the eleven arrays of state are equal bit for bit; once with lambda and z
+    given, once with both NULL."""
+    import ctypes as C
+    pb, B, ev = R.hs71_problem(), 3, R.hs71_eval(np)
+    rng = np.random.default_rng(71)
+    x0 = np.ascontiguousarray(R.hs71_starts()[[0, 1, 13]])
+    lam0, z0 = (rng.uniform(0.05, 0.3, (B, pb.m)), rng.uniform(-0.1, 0.1, (B, pb.n))) if duals else (None, None)
+    lam = lam0 if duals else np.zeros((B, pb.m))
+    f, g, df, dg, hess = [np.ascontiguousarray(a) for a in ev(x0, lam, True)]
+    dev, host = _solver(sfb, pb, B, qp_iter=4000), _solver(sfb, pb, B, qp_iter=4000)
+    dev.set_start(T(x0), T(lam0) if duals else None, T(z0) if duals else None)
+    n_dev = dev.direction(T(f), T(df), T(g), T(dg), T(hess))
+    xt_dev = H(dev.trial())
+    ft, gt = [np.ascontiguousarray(a) for a in ev(xt_dev, lam, False)]
+    left_dev = dev.accept(T(ft), T(gt))
+    st_dev = {k: H(v) for k, v in dev.state_views().items()}
+
+    lib, check, n = sfb._capi.lib, sfb._capi.check, C.c_int64()
+    P = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))    # noqa: E731
+    check(lib.sfb_nlp_sqp_set_start_host(host._h, P(x0), P(lam0), P(z0)))
+    check(lib.sfb_nlp_sqp_direction_host(host._h, P(f), P(df), P(g), P(dg), P(hess), C.byref(n)))
+    assert n.value == n_dev == B                                                    # everybody takes the step
+    xt = np.full((B, pb.n), 7.0)
+    check(lib.sfb_nlp_sqp_trial_host(host._h, P(xt)))
+    assert np.array_equal(xt, xt_dev)
+    check(lib.sfb_nlp_sqp_accept_host(host._h, P(ft), P(gt), C.byref(n)))
+    assert n.value == left_dev
+    st = {k: np.full(v.shape, 7, dtype=v.dtype) for k, v in st_dev.items()}
+    check(lib.sfb_nlp_sqp_state_host(host._h, *[st[k].ctypes.data for k in ("x", "lam", "z", "status", "iter", "r_stat", "r_pri", "r_comp", "mu", "alpha", "nu")]))
+    assert len(st) == 11
+    for k in st:
+        assert _same(st[k], st_dev[k]), k
+    dev.close()
+    host.close()
+
+
 def test_batch_zero_is_legal(sfb):
     torch = _torch()
     pb = R.hs71_problem()

@@ -152,6 +152,32 @@ def test_batch_of_zero_writes_nothing(sfb):
     assert np.all(h == 7.0)
 
 
+def test_more_meshes_than_a_device_keeps_are_dropped_and_rebuilt_with_the_same_tables(sfb):
+    """70 distinct two-interval meshes with the dims of "bare" through sfb_ocp_nlp_batch_host, values and Jacobian: a device keeps
+    64 sets of decode tables, so the cache is emptied on the way whatever it held before.  Meshes 0, 1 and 69 called again give
+    the bits of their first run, and mesh 0 stays within the gates against the restatement."""
+    c = G.case("bare")
+    K, dims, B = np.array([2, 3]), c["dims"], 3
+    tau0 = [np.array([0.0, 0.30 + 0.005 * i]) for i in range(70)]
+    x = np.random.default_rng(64).uniform(-1, 1, (B, int(NR.structure(5, dims)[0][4])))
+    x[:, 0] = [0.75, 1.5, 2.25]
+    runs = []
+    for t in tau0:
+        per = [_inputs({**c, "m": {"K": K, "tau0": t}}, xb) for xb in x]
+        a = {k: np.stack([p[k] for p in per]) for k in NAMES}
+        a["x"] = x
+        runs.append((sfb.PHMesh(K, t), a))
+    first = [_run(sfb, mesh, dims, a) for mesh, a in runs]
+    for i in (0, 1, 69):
+        again = _run(sfb, runs[i][0], dims, runs[i][1])
+        assert np.array_equal(again[0], first[i][0]) and np.array_equal(again[1], first[i][1]), i
+    assert len({f[0].tobytes() + f[1].tobytes() for f in first}) == 70              # every mesh had tables of its own
+    for b in range(B):
+        want = NR.nlp(K, tau0[0], dims, c, x[b], order=1)
+        G.check("g", first[0][0][b], want["g"], "mesh 0 of 70, agent %d" % b)
+        G.check("dg", first[0][1][b], want["dg"], "mesh 0 of 70, agent %d" % b)
+
+
 def test_two_meshes_and_dims_used_alternately_keep_their_own_decode_tables(sfb):
     """... and the same mesh with other dims has tables of its own (ref and cross share mesh and dims: one table)"""
     runs = []
